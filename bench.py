@@ -27,6 +27,13 @@ right after and reported as ``one_pipeline``.  The default fp16 + e4m3 kernel se
 (two measure the same; ``--pipelines 2`` forces them).  The ranks of a multi-GPU run
 do the same, each sequence followed on its own stream by the gather of its own half of the pairs (``ShardPlan.split``):
 one gather behind both sequences re-aligns them every step and loses 7 %.
+
+A plain run does only what the headline needs: set-up (load + calibration), the W warm-up steps and the untimed
+clock-settling steps, the K timed steps, and the line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, ...).  ``--full``
+adds everything else the benchmark measures or checks: the shader-clock probe, per-step HIP events, per-kernel times and the
+roofline of the dominant kernel, the one-launch-sequence figure, the output checksums against
+tests/golden/bench_checksums.json, every sub-record (other checkpoint dtype, seq_len 2048, trained-like, O(1) weights, base
+model) and the CPU baseline.  ``--dump-outputs DIR`` writes what the last timed step computed (``dump_outputs``).
 """
 
 from __future__ import annotations
@@ -251,6 +258,28 @@ def output_checksum(prune: torch.Tensor, rank_logits: torch.Tensor, key: str | N
     return got
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(directory: str, prune: np.ndarray, rank_logits: np.ndarray, keep_prob: np.ndarray) -> list[str]:
+    """Write the outputs of the last timed step as ``DIR/<name>.npy`` (float32): ``prune_logits`` [T, 2], ``ranking_logits``
+    [B, nl] and ``keep_prob`` [T] of the packed batch, rows in batch order.  Above DUMP_LIMIT_BYTES in all, the per-token
+    arrays are a fixed, seeded sample of the tokens, whose packed indices go to ``token_index.npy`` (float64)."""
+
+    arrays = {"prune_logits": prune, "ranking_logits": rank_logits, "keep_prob": keep_prob}
+    budget = DUMP_LIMIT_BYTES - 1024  # (room for the .npy headers)
+    if sum(a.nbytes for a in arrays.values()) > budget:
+        per_token = prune.itemsize * prune.shape[1] + keep_prob.itemsize + 8
+        n = max(1, min(len(keep_prob), (budget - rank_logits.nbytes) // per_token))
+        idx = np.sort(np.random.default_rng(0).choice(len(keep_prob), size=n, replace=False))
+        arrays.update(prune_logits=prune[idx], keep_prob=keep_prob[idx], token_index=idx.astype(np.float64))
+    out = Path(directory)
+    out.mkdir(parents=True, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
+    return sorted(arrays)
+
+
 def cpu_baseline(dims: EncoderDims, state, seq_len: int) -> dict:
     """The CPU oracle (torch fp32, SDPA attention = what the reference executes on a CPU device) timed on this
     box's host cores on a bounded sample of the same workload: batch 32 (the reference's default batch_size) x
@@ -308,7 +337,6 @@ def cpu_baseline(dims: EncoderDims, state, seq_len: int) -> dict:
 
 
 def main() -> None:
-    os.environ.setdefault("OPEN_PROVENCE_CALIBRATE_FULL", "1")  # the line reports every candidate of the load-time calibration
     parser = argparse.ArgumentParser()
     parser.add_argument("--gpus", type=int, default=1)
     parser.add_argument("--steps", type=int, default=100)
@@ -358,7 +386,18 @@ def main() -> None:
     parser.add_argument("--exercise-gather", action="store_true",
                         help="test hook: run the N > 1 code path (process group, ShardPlan, gather, MAX all-reduce) on a "
                         "one-rank RCCL group, so that it is executed on hardware even where only one GPU is granted")
+    parser.add_argument("--full", action="store_true",
+                        help="besides the headline, measure and check everything else: shader clock, per-step events, per-kernel "
+                        "times and roofline, the one-launch-sequence figure, output checksums, the sub-records (see the --no-* "
+                        "options) and the CPU baseline.  A plain run sets up, warms up, times the K steps and prints the line")
+    parser.add_argument("--dump-outputs", metavar="DIR", default=None,
+                        help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32; at most 64 MB, "
+                        "a fixed seeded sample of the tokens above that)")
     args = parser.parse_args()
+    if args.write_checksums and not args.full:
+        parser.error("--write-checksums needs --full (a plain run computes no checksums)")
+    if args.full:
+        os.environ.setdefault("OPEN_PROVENCE_CALIBRATE_FULL", "1")  # the line reports every candidate of the load-time calibration
     global _checksum_write_mode
     _checksum_write_mode = bool(args.write_checksums)
 
@@ -452,15 +491,18 @@ def main() -> None:
         return prune, rank_logits
 
     def step():
+        """One timed step -> [(prune_logits, ranking_logits, keep_prob)] of each launch sequence, in row order."""
+
         if not pipes:
-            return step_one()
-        out = None
+            return [(*step_one(), keep_dev)]
+        outs = []
         for part, p_ids, p_cu, p_cu_np, p_max, p_keep, part_plan, p_seg in pipes:
             out = encoder.forward_packed_on(part, p_ids, p_cu, p_cu_np, p_max, keep_prob=p_keep)
             if part_plan is not None:
                 with torch.cuda.stream(encoder.pipeline_stream(part)):
                     part_plan.gather(encoder.segment_means(p_keep, p_seg), out[1], dst=0)
-        return out
+            outs.append((*out, p_keep))
+        return outs
 
     def fence():
         if grouped:
@@ -504,43 +546,53 @@ def main() -> None:
         settle["seconds"] = round(time.perf_counter() - t_settle, 3)
         settle["windows_ms_per_step"] = settle["windows_ms_per_step"][-6:]
     policy = encoder.effective_policy()  # (re-read: the first real batch is the calibration's audit and may have changed the set)
-    # per-step device times from events on the launch stream (the library enqueues on torch's current stream)
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)]
+    # per-step device times from events on the launch stream (the library enqueues on torch's current stream; --full only)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.full else None
     mark_stream = encoder.pipeline_stream(1) if pipes else torch.cuda.current_stream(device)
     t0 = time.perf_counter()
     for i in range(args.steps):
-        marks[i].record(mark_stream)
-        out = step()
-    marks[args.steps].record(mark_stream)
+        if marks is not None:
+            marks[i].record(mark_stream)
+        outs = step()
+    if marks is not None:
+        marks[args.steps].record(mark_stream)
     fence()
     elapsed = time.perf_counter() - t0
-    # the shader clock the chip holds under this load: a SEPARATE pass of the same steps with the one-wave probe beside
-    # it (probed_pass) -- nothing but the steps runs inside the timed region above
-    clock = probed_pass(encoder, step, args.steps, elapsed / args.steps, fence)
-    shader_clock_ghz = clock["value"]
-    step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
+    # what the timed path computed in its last step: the launch sequences' outputs joined in row order
+    timed_prune, timed_rank, timed_keep = (torch.cat([o[i] for o in outs]) if len(outs) > 1 else outs[0][i] for i in range(3))
+    require_finite("the headline workload", timed_prune, timed_rank)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, timed_prune.cpu().numpy(), timed_rank.cpu().numpy(), timed_keep.cpu().numpy())
+    clock = shader_clock_ghz = step_ms = checksum = profile = None
+    prof_steps = 3
+    if args.full:
+        # the shader clock the chip holds under this load: a SEPARATE pass of the same steps with the one-wave probe beside
+        # it (probed_pass) -- nothing but the steps runs inside the timed region above
+        clock = probed_pass(encoder, step, args.steps, elapsed / args.steps, fence)
+        shader_clock_ghz = clock["value"]
+        step_ms = np.array([marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps)])
     if grouped:
         t = torch.tensor([elapsed], dtype=torch.float64, device=device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # outputs of the WHOLE batch as one launch sequence (a step of two launch sequences returns its second half only): what is
-    # tested for finiteness and fingerprinted -- per pair bit-identical to the timed form (tests/test_gpu_calibration.py)
-    out = encoder.forward_packed(ids, cu, cu_np, max_len) if pipes else out
-    require_finite("the headline workload", out[0], out[1])
     finite = True
     wl_shape = f"{n_pairs_rank}x{'varlen' if args.varlen else args.seq_len}"
-    checksum = output_checksum(out[0], out[1], checksum_key(args.model, wl_shape, args.init, args.weights) if world == 1 and args.precision == "bf16x3" else None)
-    # per-kernel HIP-event timing on the launch stream (separate, un-timed passes)
-    encoder.profile_enable(True)
-    encoder.profile_reset()
-    prof_steps = 3
-    for _ in range(prof_steps):
-        encoder.forward_packed(ids, cu, cu_np, max_len)
-    profile = encoder.profile_read()
-    encoder.profile_enable(False)
+    if args.full:
+        # outputs of the WHOLE batch as one launch sequence: what is tested for finiteness and fingerprinted -- per pair
+        # bit-identical to the timed form (tests/test_gpu_calibration.py)
+        out = encoder.forward_packed(ids, cu, cu_np, max_len) if pipes else (timed_prune, timed_rank)
+        require_finite("the headline workload", out[0], out[1])
+        checksum = output_checksum(out[0], out[1], checksum_key(args.model, wl_shape, args.init, args.weights) if world == 1 and args.precision == "bf16x3" else None)
+        # per-kernel HIP-event timing on the launch stream (separate, un-timed passes)
+        encoder.profile_enable(True)
+        encoder.profile_reset()
+        for _ in range(prof_steps):
+            encoder.forward_packed(ids, cu, cu_np, max_len)
+        profile = encoder.profile_read()
+        encoder.profile_enable(False)
 
     one_pipeline = None
-    if pipes and not grouped:  # the same batch as ONE launch sequence on the whole chip
+    if args.full and pipes and not grouped:  # the same batch as ONE launch sequence on the whole chip
         for _ in range(args.warmup):
             step_one()
         torch.cuda.synchronize(device)
@@ -563,7 +615,7 @@ def main() -> None:
     flops_pair = flops_forward / n_pairs_rank
     whole_tflops = pairs_per_s / world * flops_pair / 1e12  # per GPU
 
-    dominant = max(profile.items(), key=lambda kv: kv[1]["total_ms"])[0]
+    dominant = max(profile.items(), key=lambda kv: kv[1]["total_ms"])[0] if profile else None
     H, I = dims.hidden_size, dims.intermediate_size
     n_layers = dims.num_layers
     n_global = sum(dims.layer_is_global)
@@ -707,21 +759,23 @@ def main() -> None:
                          "(rounds 1-3: 4 B per token)") if grouped else None,
             "algorithmic_gflop_per_pair": flops_pair / 1e9,
             "outputs_finite": finite,
-            "output_checksum": checksum,
         },
         "roofline": roofline,
-        "kernel_ms_per_forward": {k: v["total_ms"] / prof_steps for k, v in profile.items()},
     }
+    if args.full:
+        line["config"]["output_checksum"] = checksum
+        line["kernel_ms_per_forward"] = {k: v["total_ms"] / prof_steps for k, v in profile.items()}
     if one_pipeline is not None:
         line["one_pipeline"] = one_pipeline
-    line["shader_clock_ghz"] = {**clock, "source": "one-wave probe (s_memtime / s_memrealtime) on its own stream during a SEPARATE "
-                                "pass of the same steps (the timed loop carries no probe; ms_per_step_with_probe vs ms_per_step "
-                                "is the A/B of what the probe costs); the 2.5 PFLOP/s peak assumes 2.4 GHz"}
-    if roofline is not None:
-        roofline["shader_clock_ghz"] = shader_clock_ghz
-    line["step_ms"] = {"median": float(np.median(step_ms)), "p10": float(np.percentile(step_ms, 10)),
-                       "p90": float(np.percentile(step_ms, 90)), "source": "HIP events on the launch stream" + (" of the second half-batch" if pipes else "") + ", rank 0"}
-    if world == 1 and not args.varlen and args.seq_len != 2048 and not args.no_long:
+    if args.full:
+        line["shader_clock_ghz"] = {**clock, "source": "one-wave probe (s_memtime / s_memrealtime) on its own stream during a SEPARATE "
+                                    "pass of the same steps (the timed loop carries no probe; ms_per_step_with_probe vs ms_per_step "
+                                    "is the A/B of what the probe costs); the 2.5 PFLOP/s peak assumes 2.4 GHz"}
+        if roofline is not None:
+            roofline["shader_clock_ghz"] = shader_clock_ghz
+        line["step_ms"] = {"median": float(np.median(step_ms)), "p10": float(np.percentile(step_ms, 10)),
+                           "p90": float(np.percentile(step_ms, 90)), "source": "HIP events on the launch stream" + (" of the second half-batch" if pipes else "") + ", rank 0"}
+    if args.full and world == 1 and not args.varlen and args.seq_len != 2048 and not args.no_long:
         # north_star also asks for seq_len 2048: same model, same token count per step (sub-record, not the headline)
         long_pairs = max(1, args.pairs * args.seq_len // 2048)
         rows_l = synth_pair_batch(dims, long_pairs, 2048, seed=1234)
@@ -813,11 +867,11 @@ def main() -> None:
         enc_o.close()
         return sub
 
-    if world == 1 and not args.varlen and not args.no_other_dtype:
+    if args.full and world == 1 and not args.varlen and not args.no_other_dtype:
         # the same workload with the OTHER checkpoint dtype, timed by the same command (sub-record, not the headline)
         other = "bf16" if args.weights == "fp32" else "fp32"
         line[f"{other}_checkpoint"] = sub_record(args.init, other, f"the {other}-checkpoint sub-record")
-    if world == 1 and not args.varlen and args.init == "refinit" and args.model == "xsmall" and not args.no_trained_like:
+    if args.full and world == 1 and not args.varlen and args.init == "refinit" and args.model == "xsmall" and not args.no_trained_like:
         # A proxy for a TRAINED checkpoint (none can be downloaded here): heavy-tailed rows, LayerNorm gains in [0.1, 10],
         # outlier hidden channels at 30-100 x, Zipf embedding norms; token ids Zipf-distributed (synthetic.trained_like_state_dict,
         # zipf_token_rows).  Which kernel set the load-time calibration gives it, what the first-batch audit says, what it
@@ -884,14 +938,14 @@ def main() -> None:
                                  "frac": flops_per_forward[dom_t] / lpf_t / (in_step_t * 1e-3) / 1e12 / BF16_MFMA_PEAK_TFLOPS}
         enc_t.close()
         line["trained_like"] = rec_t
-    if world == 1 and not args.varlen and args.init != "o1" and not args.no_worst_case:
+    if args.full and world == 1 and not args.varlen and args.init != "o1" and not args.no_worst_case:
         # The worst case for an operand format: every GEMM weight of O(1) magnitude (`value` of rounds 1-4).  No checkpoint of
         # the reference looks like this (its initialisation and its trained weights are ~0.02) -- on such weights every dropped
         # correction term costs >= 7e-3 on a logit, the calibration keeps the all-terms kernel sets, and this is their price.
         line["worst_case_o1_weights"] = {w: sub_record("o1", w, f"the O(1)-weights sub-record ({w} checkpoint)") for w in ("fp32", "bf16")}
         line["worst_case_o1_weights"]["what"] = ("the same batch on synthetic weights of O(1) magnitude (synthetic.synth_state_dict; `value` of rounds 1-4): "
                                                  "op_calibrate finds no cheaper kernel set within 1e-4 there and the all-terms sets run")
-    if world == 1 and not args.varlen and args.model == "xsmall" and not args.no_base:
+    if args.full and world == 1 and not args.varlen and args.model == "xsmall" and not args.no_base:
         # the panel path (base dims: hidden 512, 19 layers) on the same batch, both checkpoint dtypes (sub-record; the
         # full record of that model is `bench.py --model base`)
         dims_b = named_dims("base")
@@ -965,7 +1019,7 @@ def main() -> None:
             del state_b
             sub_b[f"{wdt}_checkpoint"] = rec
         line["base_model"] = sub_b
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(dims, state, args.seq_len)
     try:  # RCCL prints its banner through C stdio (block-buffered on a pipe): flush it so the JSON line comes last
         import ctypes

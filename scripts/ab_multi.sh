@@ -2,21 +2,23 @@
 # Same-box A/B of several builds of the library on the whole forward: scripts/ab_multi.sh "<lib1> <lib2> ..." [bench args]
 # ("tree" = the library in the tree); three alternations, prints value + the whole-layer kernel's time per forward.
 LIBS=$1; shift
-mkdir -p gpurun_out/abm
+export OUT=${BENCH_OUT:-bench_out}  # where the bench lines go
+mkdir -p $OUT/abm
 for i in 1 2 3; do
   for L in $LIBS; do
     if [ "$L" = tree ]; then
-      python bench.py --steps 60 --no-cpu-baseline --no-long --no-base --no-other-dtype "$@" > gpurun_out/abm/tree_$i.json 2>/dev/null
+      python bench.py --full --steps 60 --no-cpu-baseline --no-long --no-base --no-other-dtype "$@" > $OUT/abm/tree_$i.json 2>/dev/null
     else
-      OPEN_PROVENCE_HIP_LIB=ab_libs/$L.so OPEN_PROVENCE_HIP_LIB_ANY_ABI=1 python bench.py --steps 60 --no-cpu-baseline --no-long --no-base --no-other-dtype "$@" > gpurun_out/abm/${L}_$i.json 2>/dev/null
+      OPEN_PROVENCE_HIP_LIB=ab_libs/$L.so OPEN_PROVENCE_HIP_LIB_ANY_ABI=1 python bench.py --full --steps 60 --no-cpu-baseline --no-long --no-base --no-other-dtype "$@" > $OUT/abm/${L}_$i.json 2>/dev/null
     fi
   done
 done
 python - $LIBS <<'PY'
-import json,glob,sys
+import json,glob,os,sys
+OUT=os.environ["OUT"]
 for L in sys.argv[1:]:
     vals=[]
-    for f in sorted(glob.glob(f"gpurun_out/abm/{L}_*.json")):
+    for f in sorted(glob.glob(f"{OUT}/abm/{L}_*.json")):
         try:
             d=json.loads(open(f).read().strip().splitlines()[-1])
         except Exception as e:

@@ -2,15 +2,18 @@
 M=${1:-base}
 W=${2:-bf16}
 S=${3:-20}
+export OUT=${BENCH_OUT:-bench_out}  # where the bench lines go
+mkdir -p $OUT
 for i in 1 2; do
-  timeout 600 python bench.py --model $M --steps $S --no-cpu-baseline --no-long --no-other-dtype --weights $W > gpurun_out/abp_${M}_${W}_nof8_$i.json 2>gpurun_out/abp_err.log
-  OPEN_PROVENCE_PANEL_F8=1 timeout 600 python bench.py --model $M --steps $S --no-cpu-baseline --no-long --no-other-dtype --weights $W > gpurun_out/abp_${M}_${W}_f8_$i.json 2>>gpurun_out/abp_err.log
+  timeout 600 python bench.py --full --model $M --steps $S --no-cpu-baseline --no-long --no-other-dtype --weights $W > $OUT/abp_${M}_${W}_nof8_$i.json 2>$OUT/abp_err.log
+  OPEN_PROVENCE_PANEL_F8=1 timeout 600 python bench.py --full --model $M --steps $S --no-cpu-baseline --no-long --no-other-dtype --weights $W > $OUT/abp_${M}_${W}_f8_$i.json 2>>$OUT/abp_err.log
 done
 python - $M $W <<'PY'
-import json,glob,sys
+import json,glob,os,sys
+OUT=os.environ["OUT"]
 M,W=sys.argv[1:3]
 for tag in ("nof8","f8"):
-    for f in sorted(glob.glob(f"gpurun_out/abp_{M}_{W}_{tag}_*.json")):
+    for f in sorted(glob.glob(f"{OUT}/abp_{M}_{W}_{tag}_*.json")):
         try:
             d=json.loads(open(f).read().strip().splitlines()[-1])
         except Exception as e:

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/pmc_$TAG
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
-rocprofv3 --kernel-trace --output-format csv --pmc $COUNTERS -d $OUT -o pmc -- python bench.py --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/run.log 2>&1
+rocprofv3 --kernel-trace --output-format csv --pmc $COUNTERS -d $OUT -o pmc -- python bench.py --full --steps 2 --warmup 1 --no-cpu-baseline "$@" > $OUT/run.log 2>&1
 python - "$OUT" <<'PY'
 import csv, glob, os, sys
 from collections import defaultdict

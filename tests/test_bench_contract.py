@@ -17,7 +17,7 @@ REQUIRED = {"metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step
 @pytest.mark.gpu
 def test_bench_json_line_contract():
     proc = subprocess.run(
-        [sys.executable, str(REPO_ROOT / "bench.py"), "--pairs", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+        [sys.executable, str(REPO_ROOT / "bench.py"), "--pairs", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"],
         capture_output=True, text=True, timeout=600,
     )
     assert proc.returncode == 0, proc.stderr[-2000:]
@@ -82,7 +82,7 @@ def test_bench_two_launch_sequences_with_the_bf16_kernel_sets():
 
     proc = subprocess.run(
         [sys.executable, str(REPO_ROOT / "bench.py"), "--pairs", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-         "--no-long", "--no-base", "--no-other-dtype", "--no-worst-case", "--init", "o1", "--weights", "bf16"],
+         "--no-long", "--no-base", "--no-other-dtype", "--no-worst-case", "--init", "o1", "--weights", "bf16", "--full"],
         capture_output=True, text=True, timeout=600, env={**os.environ, "OPEN_PROVENCE_NO_F8": "1"},
     )
     assert proc.returncode == 0, proc.stderr[-2000:]
@@ -99,7 +99,7 @@ def test_bench_multi_gpu_code_path_on_a_one_rank_group():
 
     proc = subprocess.run(
         [sys.executable, str(REPO_ROOT / "bench.py"), "--pairs", "8", "--steps", "2", "--warmup", "1", "--no-cpu-baseline",
-         "--no-long", "--no-base", "--no-worst-case", "--exercise-gather"],
+         "--no-long", "--no-base", "--no-worst-case", "--exercise-gather", "--full"],
         capture_output=True, text=True, timeout=600,
     )
     assert proc.returncode == 0, proc.stderr[-2000:]
@@ -145,3 +145,77 @@ def test_bench_help_prints():
 
     proc = subprocess.run([sys.executable, str(REPO_ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
     assert proc.returncode == 0 and "--steps" in proc.stdout and "--varlen" in proc.stdout, proc.stderr[-1500:]
+
+
+@pytest.mark.gpu
+def test_plain_bench_run_is_the_headline_only_and_dumps_the_timed_outputs(tmp_path):
+    """Without --full the line carries the headline and nothing measured beside it; --dump-outputs writes what the last timed
+    step computed, and two runs with the same arguments write the same arrays."""
+
+    import numpy as np
+
+    lines, dumps = [], []
+    for run in range(2):
+        out_dir = tmp_path / f"run{run}"
+        proc = subprocess.run(
+            [sys.executable, str(REPO_ROOT / "bench.py"), "--pairs", "8", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out_dir)],
+            capture_output=True, text=True, timeout=600,
+        )
+        assert proc.returncode == 0, proc.stderr[-2000:]
+        found = [ln for ln in proc.stdout.splitlines() if ln.strip().startswith("{")]
+        assert len(found) == 1, proc.stdout[-2000:]
+        lines.append(json.loads(found[0]))
+        dumps.append({p.stem: np.load(p) for p in sorted(out_dir.glob("*.npy"))})
+    line = lines[0]
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"} <= set(line)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["unit"] == "pairs/s" and line["higher_is_better"] is True
+    assert abs(line["value"] - 8 * 3 / (line["ms_per_step"] * 3 / 1e3)) / line["value"] < 1e-6
+    assert "fp16 single pass" in line["dtype"] and line["config"]["outputs_finite"] is True
+    for extra in ("bf16_checkpoint", "worst_case_o1_weights", "seq_len_2048", "trained_like", "base_model", "cpu_baseline",
+                  "one_pipeline", "shader_clock_ghz", "step_ms", "kernel_ms_per_forward"):
+        assert extra not in line, extra
+    assert "output_checksum" not in line["config"] and line["roofline"] is None
+    d = dumps[0]
+    assert set(d) == {"prune_logits", "ranking_logits", "keep_prob"}
+    total = line["config"]["pairs_per_gpu"] * 512
+    assert d["prune_logits"].shape == (total, 2) and d["ranking_logits"].shape == (8, 1) and d["keep_prob"].shape == (total,)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in d.values())
+    p = d["prune_logits"].astype(np.float64)
+    np.testing.assert_allclose(d["keep_prob"], 1.0 / (1.0 + np.exp(p[:, 0] - p[:, 1])), atol=1e-5)
+    for name in d:
+        np.testing.assert_array_equal(dumps[1][name], d[name])
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_above_the_cap(tmp_path, monkeypatch):
+    """bench.dump_outputs (CPU: the function alone): every array as <name>.npy; above the cap a fixed, seeded sample of the
+    tokens with their packed indices, the same on every call."""
+
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_under_test", REPO_ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    assert bench.DUMP_LIMIT_BYTES == 64 * 2**20
+    rng = np.random.default_rng(3)
+    prune = rng.standard_normal((1000, 2)).astype(np.float32)
+    rank = rng.standard_normal((4, 1)).astype(np.float32)
+    keep = rng.random(1000).astype(np.float32)
+    assert bench.dump_outputs(str(tmp_path / "all"), prune, rank, keep) == ["keep_prob", "prune_logits", "ranking_logits"]
+    np.testing.assert_array_equal(np.load(tmp_path / "all" / "prune_logits.npy"), prune)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 8192)
+    for tag in ("a", "b"):
+        assert "token_index" in bench.dump_outputs(str(tmp_path / tag), prune, rank, keep)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").glob("*.npy")) <= 8192
+    idx = np.load(tmp_path / "a" / "token_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "prune_logits.npy"), prune[idx.astype(np.int64)])
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "keep_prob.npy"), keep[idx.astype(np.int64)])
+    for f in (tmp_path / "a").glob("*.npy"):
+        np.testing.assert_array_equal(np.load(f), np.load(tmp_path / "b" / f.name))
+
+
+def test_bench_help_names_the_full_and_dump_options():
+    proc = subprocess.run([sys.executable, str(REPO_ROOT / "bench.py"), "--help"], capture_output=True, text=True, timeout=300)
+    assert proc.returncode == 0 and "--full" in proc.stdout and "--dump-outputs" in proc.stdout, proc.stderr[-1500:]
