@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define OP_ABI_VERSION 9 /* 9: kernel sets 8 / 9 layer by layer (op_calibration.mlp_layers / mlp_layers_err, OP_CAL_WHOLE_DEPTH, op_mlp_correction_layers, op_select_mlp_correction_layers); 8: op_calibration.flags (OP_CAL_FULL_REPORT; the search stops at the first candidate that holds otherwise), op_calibrate validates its batch before it touches the handle, op_load_weight of a GEMM weight drops a pinned / calibrated kernel set; 7: kernel sets 10 / 11 (fp16 attention inside the fp16 + e4m3 sets), op_calibration holds 16 candidates; 6: op_select_kernel_set, op_calibrate, kernel set 7 ("f16": single-pass fp16 operands); 5: op_set_compact_operands (run-time fallback to the (hi, lo) bf16 kernel sets); 4: kernel set 3 (fp16 + e4m3 operands), flag NO_F8; 3: op_segment_means, flags LAYER_M32 / NO_HEAD_FUSION (struct layouts as in 2) */
+#define OP_ABI_VERSION 10 /* 10: op_hidden_request, op_forward_packed_hidden (per-call hidden states on the kernels of op_forward_packed); 9: kernel sets 8 / 9 layer by layer (op_calibration.mlp_layers / mlp_layers_err, OP_CAL_WHOLE_DEPTH, op_mlp_correction_layers, op_select_mlp_correction_layers); 8: op_calibration.flags (OP_CAL_FULL_REPORT; the search stops at the first candidate that holds otherwise), op_calibrate validates its batch before it touches the handle, op_load_weight of a GEMM weight drops a pinned / calibrated kernel set; 7: kernel sets 10 / 11 (fp16 attention inside the fp16 + e4m3 sets), op_calibration holds 16 candidates; 6: op_select_kernel_set, op_calibrate, kernel set 7 ("f16": single-pass fp16 operands); 5: op_set_compact_operands (run-time fallback to the (hi, lo) bf16 kernel sets); 4: kernel set 3 (fp16 + e4m3 operands), flag NO_F8; 3: op_segment_means, flags LAYER_M32 / NO_HEAD_FUSION (struct layouts as in 2) */
 #define OP_MAX_LAYERS 128
 
 typedef struct op_handle op_handle;
@@ -271,6 +271,34 @@ int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_se
                       const int32_t* cu_seqlens_host, int n_seqs, int total_tokens, int max_seqlen,
                       float* prune_logits_dev, float* rank_logits_dev, float* keep_prob_dev,
                       void* workspace_dev, size_t workspace_bytes, void* hip_stream);
+
+/* Replaces: output_hidden_states=True of the reference forward (standalone.py:1689, 1727), per call.  One forward
+ * exactly as op_forward_packed enqueues it -- the same kernels, bit-identical logits -- that also writes the hidden states
+ * `req` selects.  Entry 0 is the embedding LayerNorm output, entry i (1 <= i < num_layers) the output of layer i-1, entry
+ * num_layers the final_norm output (op_config.prune_pre_final_norm = 0) or the un-normalised output of the last layer (= 1):
+ * hidden_states[-1] of the reference under each transformers line, the pruning head's input either way.
+ *   select   host array of num_layers + 1 flags (entry i = hidden_states[i]), or NULL = every entry
+ *   out_dev  the selected entries in order, each
+ *              pad_width == 0: packed [total_tokens][hidden]
+ *              pad_width  > 0: padded [n_seqs][pad_width][hidden], token t of sequence s at [s][t - cu[s]]; positions at or
+ *                              beyond a sequence's length are NOT written (the caller zeroes them); pad_width >= max_seqlen
+ *   dtype    OP_HIDDEN_F32, or OP_HIDDEN_BF16 = the fp32 state rounded to nearest even
+ * The request lives for this call only (no handle state): the call is as stream-safe as op_forward_packed.  A wrong
+ * struct_bytes, an unknown dtype, a pad_width below max_seqlen, or out_dev == NULL with an entry selected (of a non-empty
+ * batch) return
+ * OP_ERR_INVALID before anything is enqueued.  req == NULL is op_forward_packed. */
+enum op_hidden_dtype { OP_HIDDEN_F32 = 0, OP_HIDDEN_BF16 = 1 };
+typedef struct op_hidden_request {
+  uint32_t struct_bytes; /* sizeof(op_hidden_request) */
+  int32_t dtype;         /* enum op_hidden_dtype */
+  int32_t pad_width;     /* 0: packed [n_sel][total_tokens][H]; > 0: padded [n_sel][n_seqs][pad_width][H] */
+  const uint8_t* select; /* host array of num_layers + 1 flags, or NULL = all; entry i = hidden_states[i] */
+  void* out_dev;         /* written in the order of the selected entries */
+} op_hidden_request;
+int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev,
+                             const int32_t* cu_seqlens_host, int n_seqs, int total_tokens, int max_seqlen,
+                             float* prune_logits_dev, float* rank_logits_dev, float* keep_prob_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req);
 
 /* Replaces: the per-fragment `float(block_probs[start:end].mean())` of the reference's post-processing
  * (standalone.py:3075-3082), evaluated on the device on the keep-probabilities a forward left there:

@@ -12,7 +12,7 @@ import os
 from pathlib import Path
 
 OP_MAX_LAYERS = 128
-OP_ABI_VERSION = 9
+OP_ABI_VERSION = 10
 
 OP_OK = 0
 OP_ERR_INVALID, OP_ERR_UNSUPPORTED, OP_ERR_HIP, OP_ERR_STATE, OP_ERR_WORKSPACE, OP_ERR_NOMEM = -1, -2, -3, -4, -5, -6
@@ -59,6 +59,7 @@ EXPORTED_SYMBOLS = (
     "op_calibrate",
     "op_workspace_bytes",
     "op_forward_packed",
+    "op_forward_packed_hidden",
     "op_segment_means",
     "op_debug_capture_hidden",
     "op_profile_enable",
@@ -120,6 +121,20 @@ class OpCalibration(ctypes.Structure):
     ]
 
 
+class OpHiddenRequest(ctypes.Structure):
+    """``op_hidden_request``: the hidden states one ``op_forward_packed_hidden`` call writes."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("dtype", ctypes.c_int32),
+        ("pad_width", ctypes.c_int32),
+        ("select", ctypes.POINTER(ctypes.c_uint8)),
+        ("out_dev", ctypes.c_void_p),
+    ]
+
+
+OP_HIDDEN_F32, OP_HIDDEN_BF16 = 0, 1
+
 OP_CAL_FULL_REPORT = 1
 OP_CAL_WHOLE_DEPTH = 2
 
@@ -168,6 +183,9 @@ def load_library() -> ctypes.CDLL:
     lib.op_workspace_bytes.argtypes = [vp, ci, ci, ci]
     lib.op_forward_packed.restype = ci
     lib.op_forward_packed.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, cs, vp]
+    if hasattr(lib, "op_forward_packed_hidden"):
+        lib.op_forward_packed_hidden.restype = ci
+        lib.op_forward_packed_hidden.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, cs, vp, ctypes.POINTER(OpHiddenRequest)]
     lib.op_effective_policy.restype = ci
     lib.op_effective_policy.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ci)]
     if hasattr(lib, "op_set_compact_operands"):  # (absent only in an older library loaded for a same-box A/B, see below)

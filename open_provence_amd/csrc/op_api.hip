@@ -311,6 +311,14 @@ int clear_lo(Launcher& L, u16* base, int unit, size_t n_pairs) {
   return L.end();
 }
 
+// A validated per-call hidden-state request (op_forward_packed_hidden): the output slot of every entry (-1: not selected)
+struct HiddenReq {
+  char* out;
+  int bf16, pad;
+  size_t entry_bytes;     // one entry: [total_tokens][H] or [n_seqs][pad][H] elements of the dtype
+  std::vector<int> slot;  // [num_layers + 1]
+};
+
 struct AttnPlan {
   int waves_g;  // waves per block of the full-attention layers (8 or 4); sliding-window layers always use 4
   int items_g;  // work items (sequence, query block) of a full-attention layer
@@ -328,6 +336,7 @@ struct ChunkPass {
   int s0, ns, rows, max_len, total_tokens;
   const AttnPlan& plan;
   float *prune_out, *rank_out, *keep_prob;
+  const HiddenReq* hid;  // per-call hidden-state request, or nullptr
 
   int H, I;
   bool fp_layout;  // fragment-packed activations, attn_fp_kernel
@@ -345,11 +354,13 @@ struct ChunkPass {
   bool layer_fused, head_in_last_layer;
   bool pair_layers;  // whole-layer launches as wave pairs on 32x32x16 MFMAs (opk_layer16p.hip.h)
   bool head_done = false;
+  int hidden_stored = -1;  // the hidden-state entry the last layer launch stored itself (wave-pair kernel), -1: none
 
   ChunkPass(op_handle* h_, Launcher& L_, const Workspace& ws_, const int32_t* ids_dev_, const int32_t* cu_dev_, int s0_, int ns_, int rows_,
-            int max_len_, int total_tokens_, const AttnPlan& plan_, float* prune_out_, float* rank_out_, float* keep_prob_)
+            int max_len_, int total_tokens_, const AttnPlan& plan_, float* prune_out_, float* rank_out_, float* keep_prob_,
+            const HiddenReq* hid_)
       : h(h_), L(L_), ws(ws_), ids_dev(ids_dev_), cu_dev(cu_dev_), s0(s0_), ns(ns_), rows(rows_), max_len(max_len_),
-        total_tokens(total_tokens_), plan(plan_), prune_out(prune_out_), rank_out(rank_out_), keep_prob(keep_prob_) {
+        total_tokens(total_tokens_), plan(plan_), prune_out(prune_out_), rank_out(rank_out_), keep_prob(keep_prob_), hid(hid_) {
     H = h->H;
     I = h->I;
     // Row path: exactly the computed rows, rounded to the 128-row block -- no slack rows: a 131072-row batch is 1024
@@ -448,6 +459,24 @@ struct ChunkPass {
     OP_TRY(L.begin(PK_CAPTURE));
     hipLaunchKernelGGL(capture_rows_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, ws.row_tok, H, r_pad,
                        h->capture + (size_t)index * total_tokens * H);
+    return L.end();
+  }
+
+  // Per-call hidden-state request.  Nothing below depends on it but these stores: the kernels are the ones a forward without a
+  // request runs.  Entry `index` is copied from the residual stream rows a launch has just written; ln: through final_norm
+  // first (entry N, post-norm convention).  Two launches store their entry from their own epilogue instead: the wave-pair
+  // kernel (layer16p_hout_kernel; between two of its launches x is tiled) and the last whole-layer launch with the head fused,
+  // which writes no x (rowgemm_hout_kernel).
+  void* hidden_entry(int index) const {
+    if (!hid || hid->slot[index] < 0) return nullptr;
+    return hid->out + (size_t)hid->slot[index] * hid->entry_bytes;
+  }
+  int hidden(int index, const float* ln = nullptr) {
+    void* dst = hidden_entry(index);
+    if (!dst) return OP_OK;
+    OP_TRY(L.begin(PK_CAPTURE));
+    hipLaunchKernelGGL(hidden_rows_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, ln, h->cfg.norm_eps, H, r_pad,
+                       ws.row_tok, ws.row_seq, ws.row_pos, s0, hid->pad, hid->bf16, dst);
     return L.end();
   }
 
@@ -568,6 +597,7 @@ struct ChunkPass {
       if (!opl::launch_row_qkv0(st, rp, H / 32, small_blocks, h->pi, row_grid)) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
       OP_TRY(L.end());
       OP_TRY(clear_qkv());
+      if (embed_in_qkv0) OP_TRY(hidden(0));  // (the embedding rows were written by the launch above)
     }  // else: q/k/v of this layer were produced by the fused kernel that closed layer li-1
     OP_TRY(attention(is_global));
 
@@ -608,7 +638,8 @@ struct ChunkPass {
       // below one 128-row block per CU too, where the other launches switch to 64-row blocks (small_blocks): 4 - 8 % faster
       // forwards from 512 to 32 k tokens than the 8 x 16 kernel's 64-row form (profiles/r06_small_request.txt).  The last layer keeps the 8 x 16 kernel (it ends with final_norm + the pruning head).  Between two
       // wave-pair launches the residual stream is TILED (coalesced 1 KiB loads / stores): the first one reads rows, the last
-      // one writes rows.  Hidden-state capture reads rows after every layer: it keeps the 8 x 16 kernel.
+      // one writes rows.  Hidden-state capture reads rows after every layer: it keeps the 8 x 16 kernel.  A per-call
+      // hidden-state request does not change the kernel: its entry li + 1 is stored from this launch's epilogue (layer16p_hout_kernel).
       if (pair_layers && with_qkv) {
         Layer32Params lp;
         memset(&lp, 0, sizeof(lp));
@@ -632,8 +663,18 @@ struct ChunkPass {
         lp.rope_cos = h->rope_cos[gl];
         lp.rope_sin = h->rope_sin[gl];
         lp.max_pos = h->max_pos;
+        lp.hid_out = hidden_entry(li + 1);
+        if (lp.hid_out) {
+          lp.row_tok = ws.row_tok;
+          lp.row_seq = ws.row_seq;
+          lp.hid_bf16 = hid->bf16;
+          lp.hid_pad = hid->pad;
+          lp.hid_s0 = s0;
+          hidden_stored = li + 1;
+        }
         OP_TRY(L.begin(PK_FUSED_LAYER));
-        if (!opl::launch_layer16p(st, lp, f16, true, /*xin_t=*/li > 0, /*xout_t=*/li + 2 < h->N, (unsigned)(r_pad / ROW_BM)))
+        if (!opl::launch_layer16p(st, lp, f16, true, /*xin_t=*/li > 0, /*xout_t=*/li + 2 < h->N, (unsigned)(r_pad / ROW_BM),
+                                  lp.hid_out != nullptr))
           return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
         OP_TRY(L.end());
         return OP_OK;
@@ -668,10 +709,17 @@ struct ChunkPass {
         rl.fin_cls = ws.cls;
         rl.fin_pre_norm = h->cfg.prune_pre_final_norm ? 1 : 0;
         head_done = true;
+        rl.hid_out = hidden_entry(h->N);  // (entry N from the head's epilogue: this launch writes no x)
+        if (rl.hid_out) {
+          rl.hid_bf16 = hid->bf16;
+          rl.hid_pad = hid->pad;
+          rl.hid_s0 = s0;
+        }
       }
       OP_TRY(L.begin(PK_FUSED_LAYER));
       if (!opl::launch_row_layer_fused(st, rl, H / 32, h->pi, with_qkv, (unsigned)(r_pad / ROW_BM),
-                                       (h->cfg.flags & OP_FLAG_LAYER_8X16) != 0 || (opl::kPolicies[h->pi].wi & 1) == 0))
+                                       (h->cfg.flags & OP_FLAG_LAYER_8X16) != 0 || (opl::kPolicies[h->pi].wi & 1) == 0,
+                                       rl.hid_out != nullptr))
         return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
       OP_TRY(L.end());
       return OP_OK;
@@ -930,6 +978,8 @@ struct ChunkPass {
   int heads() {
     const int mean_pool = h->cfg.pooling == OP_POOL_MEAN ? 1 : 0;
     if (!head_done) {
+      // (before final_ln_prune_kernel: under mean pooling it writes the normalised rows over x)
+      OP_TRY(hidden(h->N, h->cfg.prune_pre_final_norm ? nullptr : h->final_norm));
       OP_TRY(L.begin(PK_FINAL_LN_PRUNE));
       hipLaunchKernelGGL(final_ln_prune_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, h->final_norm, h->cfg.norm_eps, H,
                          r_pad, ws.row_tok, ws.row_seq, ws.row_pos, h->prune_w, h->prune_b, prune_out, keep_prob,
@@ -948,11 +998,15 @@ struct ChunkPass {
 
   int run() {
     OP_TRY(prologue());
+    if (!embed_in_qkv0) OP_TRY(hidden(0));
     for (int li = 0; li < h->N; ++li) {
       OP_TRY(capture(li));
       if (h->row_path) OP_TRY(row_layer(li));
       else if (h->panel_path) OP_TRY(panel_layer(li));
       else OP_TRY(tiled_layer(li));
+      // output of layer li = entry li + 1 (entry N is the head's input: heads() / the last whole-layer launch), unless the
+      // wave-pair launch stored it from its epilogue
+      if (li + 1 < h->N && hidden_stored != li + 1) OP_TRY(hidden(li + 1));
     }
     return heads();
   }
@@ -960,8 +1014,8 @@ struct ChunkPass {
 
 int forward_chunk(op_handle* h, Launcher& L, const Workspace& ws, const int32_t* ids_dev, const int32_t* cu_dev, int s0,
                   int ns, int rows, int max_len, int total_tokens, const AttnPlan& plan, float* prune_out, float* rank_out,
-                  float* keep_prob) {
-  return ChunkPass(h, L, ws, ids_dev, cu_dev, s0, ns, rows, max_len, total_tokens, plan, prune_out, rank_out, keep_prob).run();
+                  float* keep_prob, const HiddenReq* hid) {
+  return ChunkPass(h, L, ws, ids_dev, cu_dev, s0, ns, rows, max_len, total_tokens, plan, prune_out, rank_out, keep_prob, hid).run();
 }
 
 }  // namespace
@@ -1960,9 +2014,10 @@ int op_profile_read(op_handle* h, op_profile_entry* entries, int max_entries) {
   return n;
 }
 
-int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
-                      int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
-                      void* workspace, size_t workspace_bytes, void* hip_stream) {
+// op_forward_packed, and op_forward_packed_hidden with its validated request (hid; nullptr: none)
+static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
+                               int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
+                               void* workspace, size_t workspace_bytes, void* hip_stream, const HiddenReq* hid) {
   if (!h) return fail(nullptr, OP_ERR_INVALID, "op_forward_packed: NULL handle");
   if (n_seqs < 0 || total_tokens < 0 || max_seqlen < 0) return fail(h, OP_ERR_INVALID, "negative size");
   if (n_seqs == 0 || total_tokens == 0) {
@@ -2040,7 +2095,7 @@ int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_de
     plan.items_l = count_items(4);
     if (rows > 0) {
       OP_TRY(forward_chunk(h, L, ws, ids_dev, cu_dev, s0, s1 - s0, rows, max_len, total_tokens, plan, prune_out, rank_out,
-                           keep_prob));
+                           keep_prob, hid));
     } else {
       // only empty sequences in this chunk
       OP_HIP(h, hipMemsetAsync(rank_out + (size_t)s0 * h->nl, 0, (size_t)(s1 - s0) * h->nl * sizeof(float), stream));
@@ -2048,6 +2103,47 @@ int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_de
     s0 = s1;
   }
   return OP_OK;
+}
+
+int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
+                      int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
+                      void* workspace, size_t workspace_bytes, void* hip_stream) {
+  return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
+                             workspace, workspace_bytes, hip_stream, nullptr);
+}
+
+int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
+                             int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
+                             void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req) {
+  if (req) {  // (the request's own fields first: none of them needs the handle)
+    if (req->struct_bytes != sizeof(op_hidden_request))
+      return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: op_hidden_request.struct_bytes is %u, expected %zu", req->struct_bytes,
+                  sizeof(op_hidden_request));
+    if (req->dtype != OP_HIDDEN_F32 && req->dtype != OP_HIDDEN_BF16)
+      return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: unknown dtype %d", req->dtype);
+    if (req->pad_width < 0 || (req->pad_width > 0 && req->pad_width < max_seqlen))
+      return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: pad_width %d below max_seqlen %d", req->pad_width, max_seqlen);
+  }
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_forward_packed_hidden: NULL handle");
+  if (!req)
+    return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
+                               workspace, workspace_bytes, hip_stream, nullptr);
+  HiddenReq hid;
+  hid.out = reinterpret_cast<char*>(req->out_dev);
+  hid.bf16 = req->dtype == OP_HIDDEN_BF16 ? 1 : 0;
+  hid.pad = req->pad_width;
+  hid.slot.assign((size_t)h->N + 1, -1);
+  int n_sel = 0;
+  for (int i = 0; i <= h->N; ++i)
+    if (!req->select || req->select[i]) hid.slot[i] = n_sel++;
+  const size_t rows = hid.pad > 0 ? (size_t)std::max(n_seqs, 0) * (size_t)hid.pad : (size_t)std::max(total_tokens, 0);
+  if (rows > (size_t)INT32_MAX)  // (destination rows are 32-bit indices in the kernels' epilogues)
+    return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: %zu destination rows per entry exceed 2^31 - 1", rows);
+  hid.entry_bytes = rows * (size_t)h->H * (hid.bf16 ? 2 : 4);
+  if (n_sel > 0 && hid.entry_bytes > 0 && !hid.out)
+    return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: out_dev is NULL with %d entries selected", n_sel);
+  return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
+                             workspace, workspace_bytes, hip_stream, n_sel > 0 ? &hid : nullptr);
 }
 
 }  // extern "C"

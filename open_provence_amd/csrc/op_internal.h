@@ -65,19 +65,21 @@ bool launch_row_geglu_fused(hipStream_t st, const opk::RowGemmParams& p, int ks,
 bool launch_row_qkv_fused(hipStream_t st, const opk::RowGemmParams& p, int ks, bool small, int pi, unsigned grid);
 bool launch_kstream(hipStream_t st, const opk::KStreamParams& p, int nf, int pi, unsigned grid);
 // one kernel per layer: x += o Wo^T; x += GeGLU(LN(x) Wi^T) Wo^T; (with_qkv) next layer's q / k / v^T.  128-row blocks.
+// hout (the last layer with the head fused, p.fin_ln set): also store entry N of a hidden-state request (RowGemmParams::hid_out).
 bool has_row_layer_fused(int pi);
 bool launch_row_layer_fused(hipStream_t st, const opk::RowGemmParams& p, int ks, int pi, bool with_qkv, unsigned grid,
-                            bool waves8);
+                            bool waves8, bool hout = false);
 // ... of the "f16 + fp8" kernel set (hidden 128 / 256)
-bool launch_row_layer_f8(hipStream_t st, const opk::RowGemmParams& p, int ks, bool with_qkv, unsigned grid);
-bool launch_row_layer_f8w(hipStream_t st, const opk::RowGemmParams& p, int ks, bool with_qkv, unsigned grid);  // kernel set 4
+bool launch_row_layer_f8(hipStream_t st, const opk::RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool hout);
+bool launch_row_layer_f8w(hipStream_t st, const opk::RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool hout);  // kernel set 4
 // ... of the "f16" kernel set (PI_F16): the layer-0 q / k / v projection and the whole-layer kernel with fp16 operands
 bool launch_row_qkv0_h16(hipStream_t st, const opk::RowGemmParams& p, int ks, bool small, unsigned grid);
-bool launch_row_layer_h16(hipStream_t st, const opk::RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool waves8);
+bool launch_row_layer_h16(hipStream_t st, const opk::RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool waves8, bool hout);
 // the same launch on the 32x32x16 shape (hidden = 256; kernel sets 1 and 2)
 bool has_layer32(int pi);
 bool launch_layer32(hipStream_t st, const opk::Layer32Params& p, int pi, bool with_qkv, unsigned grid);
-bool launch_layer16p(hipStream_t st, const opk::Layer32Params& p, bool h16, bool with_qkv, bool xin_t, bool xout_t, unsigned grid);
+bool launch_layer16p(hipStream_t st, const opk::Layer32Params& p, bool h16, bool with_qkv, bool xin_t, bool xout_t, unsigned grid,
+                     bool hout = false);
 // waves x kt: (8, 2) and (4, 2) full attention / long and short sequences, (4, 1) sliding window.
 // zero_p_lo (pi == 0 only): the policy has no lo(p) x hi(v) term.
 // f16_in_f8_out (kernel sets 10 / 11; pi = PI_F16_F8 / PI_F16_F8_W): the fp16 single-pass kernels of PI_F16 on fp16 q / k / v^T,

@@ -18,6 +18,18 @@ void launch_shape(hipStream_t st, const RowGemmParams& p, bool small, unsigned g
     hipLaunchKernelGGL((rowgemm_kernel<KS, EPI, PRO, T1, T2, OLO, 4, 2>), dim3(grid), dim3(256), 0, st, p);
 }
 
+// The last whole-layer launch (no next q / k / v): rowgemm_kernel, or -- hout: a hidden-state request wants entry N, which the
+// launch with the head fused never writes back -- rowgemm_hout_kernel, the same instantiation with the head epilogue's stores.
+template <int KS, int T1, int WAVES, int MF, int TW, int TM, int F8 = 0, bool H16 = false>
+void launch_last_layer(hipStream_t st, const RowGemmParams& p, unsigned grid, bool hout) {
+  if (hout)
+    hipLaunchKernelGGL((rowgemm_hout_kernel<KS, RE_NONE, RP_MLP, T1, 0, 0, WAVES, MF, TW, TM, F8, H16>), dim3(grid), dim3(WAVES * 64), 0,
+                       st, p);
+  else
+    hipLaunchKernelGGL((rowgemm_kernel<KS, RE_NONE, RP_MLP, T1, 0, 0, WAVES, MF, TW, TM, F8, H16>), dim3(grid), dim3(WAVES * 64), 0,
+                       st, p);
+}
+
 template <int EPI, int PRO, int T1, int T2, int OLO>
 bool launch_ks(hipStream_t st, const RowGemmParams& p, int ks, bool small, unsigned grid) {
   if (ks == 8) launch_shape<8, EPI, PRO, T1, T2, OLO>(st, p, small, grid);
@@ -87,7 +99,7 @@ bool launch_kstream(hipStream_t st, const KStreamParams& p, int nf, int pi, unsi
 // whose weights are single-plane only (bf16 checkpoints / bf16x2 / bf16), 4 waves x 32 rows per block, one block per CU.
 namespace {
 template <int PI, int KS>
-bool launch_layer_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid, bool waves8) {
+bool launch_layer_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid, bool waves8, bool hout) {
   constexpr Policy P = kPolicies[PI];
   if constexpr ((P.wi & 2) != 0 || (P.mlp_out & 2) != 0) {
     return false;
@@ -96,21 +108,19 @@ bool launch_layer_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsi
       hipLaunchKernelGGL((rowgemm_kernel<KS, RE_QKV, RP_MLP, P.attn_out, P.wqkv, qkv_olo(P), 8, 1, P.wi, P.mlp_out>), dim3(grid),
                          dim3(512), 0, st, p);
     else if (waves8)
-      hipLaunchKernelGGL((rowgemm_kernel<KS, RE_NONE, RP_MLP, P.attn_out, 0, 0, 8, 1, P.wi, P.mlp_out>), dim3(grid), dim3(512), 0,
-                         st, p);
+      launch_last_layer<KS, P.attn_out, 8, 1, P.wi, P.mlp_out>(st, p, grid, hout);
     else if (with_qkv)
       hipLaunchKernelGGL((rowgemm_kernel<KS, RE_QKV, RP_MLP, P.attn_out, P.wqkv, qkv_olo(P), 4, 2, P.wi, P.mlp_out>), dim3(grid),
                          dim3(256), 0, st, p);
     else
-      hipLaunchKernelGGL((rowgemm_kernel<KS, RE_NONE, RP_MLP, P.attn_out, 0, 0, 4, 2, P.wi, P.mlp_out>), dim3(grid), dim3(256), 0,
-                         st, p);
+      launch_last_layer<KS, P.attn_out, 4, 2, P.wi, P.mlp_out>(st, p, grid, hout);
     return true;
   }
 }
 template <int PI>
-bool launch_layer_pi(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool waves8) {
-  if (ks == 8) return launch_layer_ks<PI, 8>(st, p, with_qkv, grid, waves8);
-  if (ks == 4) return launch_layer_ks<PI, 4>(st, p, with_qkv, grid, waves8);
+bool launch_layer_pi(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool waves8, bool hout) {
+  if (ks == 8) return launch_layer_ks<PI, 8>(st, p, with_qkv, grid, waves8, hout);
+  if (ks == 4) return launch_layer_ks<PI, 4>(st, p, with_qkv, grid, waves8, hout);
   return false;
 }
 }  // namespace
@@ -119,11 +129,12 @@ bool has_row_layer_fused(int pi) {
   return pi == PI_F16_F8_W || pi == PI_F16 || (pi >= 0 && pi < N_POLICIES && (kPolicies[pi].wi & 2) == 0 && (kPolicies[pi].mlp_out & 2) == 0);
 }
 
-bool launch_row_layer_fused(hipStream_t st, const RowGemmParams& p, int ks, int pi, bool with_qkv, unsigned grid, bool waves8) {
-  if (pi == PI_F16_F8) return !waves8 && launch_row_layer_f8(st, p, ks, with_qkv, grid);
-  if (pi == PI_F16_F8_W) return !waves8 && launch_row_layer_f8w(st, p, ks, with_qkv, grid);
-  if (pi == PI_F16) return launch_row_layer_h16(st, p, ks, with_qkv, grid, waves8);
-#define OPL_CALL(PI) (launch_layer_pi<PI>(st, p, ks, with_qkv, grid, waves8))
+bool launch_row_layer_fused(hipStream_t st, const RowGemmParams& p, int ks, int pi, bool with_qkv, unsigned grid, bool waves8, bool hout) {
+  if (hout && (with_qkv || p.fin_ln == nullptr)) return false;  // (entry N is stored by the head epilogue of the last launch only)
+  if (pi == PI_F16_F8) return !waves8 && launch_row_layer_f8(st, p, ks, with_qkv, grid, hout);
+  if (pi == PI_F16_F8_W) return !waves8 && launch_row_layer_f8w(st, p, ks, with_qkv, grid, hout);
+  if (pi == PI_F16) return launch_row_layer_h16(st, p, ks, with_qkv, grid, waves8, hout);
+#define OPL_CALL(PI) (launch_layer_pi<PI>(st, p, ks, with_qkv, grid, waves8, hout))
   OPL_SWITCH(OPL_CALL)
 #undef OPL_CALL
 }
@@ -133,20 +144,19 @@ bool launch_row_layer_fused(hipStream_t st, const RowGemmParams& p, int ks, int 
 // Whole-layer kernel of the "f16 + fp8" kernel set (4 waves x 32 rows, one block per CU, 132 KiB of LDS).
 namespace {
 template <int KS>
-void launch_layer_f8_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid) {
+void launch_layer_f8_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid, bool hout) {
   constexpr Policy P = kPolicies[PI_F16_F8];
   if (with_qkv)
     hipLaunchKernelGGL((rowgemm_kernel<KS, RE_QKV, RP_MLP, P.attn_out, P.wqkv, qkv_olo(P), 4, 2, P.wi, P.mlp_out, 1>), dim3(grid),
                        dim3(256), 0, st, p);
   else
-    hipLaunchKernelGGL((rowgemm_kernel<KS, RE_NONE, RP_MLP, P.attn_out, 0, 0, 4, 2, P.wi, P.mlp_out, 1>), dim3(grid), dim3(256), 0,
-                       st, p);
+    launch_last_layer<KS, P.attn_out, 4, 2, P.wi, P.mlp_out, 1>(st, p, grid, hout);
 }
 }  // namespace
 
-bool launch_row_layer_f8(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid) {
-  if (ks == 8) launch_layer_f8_ks<8>(st, p, with_qkv, grid);
-  else if (ks == 4) launch_layer_f8_ks<4>(st, p, with_qkv, grid);
+bool launch_row_layer_f8(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool hout) {
+  if (ks == 8) launch_layer_f8_ks<8>(st, p, with_qkv, grid, hout);
+  else if (ks == 4) launch_layer_f8_ks<4>(st, p, with_qkv, grid, hout);
   else return false;
   return true;
 }
@@ -156,20 +166,19 @@ bool launch_row_layer_f8(hipStream_t st, const RowGemmParams& p, int ks, bool wi
 // Whole-layer kernel of kernel set 4: fp32-valued weights, fp16 + e4m3 operands with the weights' lo part (F8 = 2).
 namespace {
 template <int KS>
-void launch_layer_f8w_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid) {
+void launch_layer_f8w_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid, bool hout) {
   constexpr Policy P = kPolicies[PI_F16_F8_W];
   if (with_qkv)
     hipLaunchKernelGGL((rowgemm_kernel<KS, RE_QKV, RP_MLP, P.attn_out, P.wqkv, qkv_olo(P), 4, 2, P.wi, P.mlp_out, 2>), dim3(grid),
                        dim3(256), 0, st, p);
   else
-    hipLaunchKernelGGL((rowgemm_kernel<KS, RE_NONE, RP_MLP, P.attn_out, 0, 0, 4, 2, P.wi, P.mlp_out, 2>), dim3(grid), dim3(256), 0,
-                       st, p);
+    launch_last_layer<KS, P.attn_out, 4, 2, P.wi, P.mlp_out, 2>(st, p, grid, hout);
 }
 }  // namespace
 
-bool launch_row_layer_f8w(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid) {
-  if (ks == 8) launch_layer_f8w_ks<8>(st, p, with_qkv, grid);
-  else if (ks == 4) launch_layer_f8w_ks<4>(st, p, with_qkv, grid);
+bool launch_row_layer_f8w(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool hout) {
+  if (ks == 8) launch_layer_f8w_ks<8>(st, p, with_qkv, grid, hout);
+  else if (ks == 4) launch_layer_f8w_ks<4>(st, p, with_qkv, grid, hout);
   else return false;
   return true;
 }
@@ -184,15 +193,15 @@ void launch_qkv0_h16_ks(hipStream_t st, const RowGemmParams& p, bool small, unsi
   else hipLaunchKernelGGL((rowgemm_kernel<KS, RE_QKV, RP_SPLIT, 0, 0, 0, 4, 2, 0, 0, 0, true>), dim3(grid), dim3(256), 0, st, p);
 }
 template <int KS>
-void launch_layer_h16_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid, bool waves8) {
+void launch_layer_h16_ks(hipStream_t st, const RowGemmParams& p, bool with_qkv, unsigned grid, bool waves8, bool hout) {
   if (waves8 && with_qkv)
     hipLaunchKernelGGL((rowgemm_kernel<KS, RE_QKV, RP_MLP, 0, 0, 0, 8, 1, 0, 0, 0, true>), dim3(grid), dim3(512), 0, st, p);
   else if (waves8)
-    hipLaunchKernelGGL((rowgemm_kernel<KS, RE_NONE, RP_MLP, 0, 0, 0, 8, 1, 0, 0, 0, true>), dim3(grid), dim3(512), 0, st, p);
+    launch_last_layer<KS, 0, 8, 1, 0, 0, 0, true>(st, p, grid, hout);
   else if (with_qkv)
     hipLaunchKernelGGL((rowgemm_kernel<KS, RE_QKV, RP_MLP, 0, 0, 0, 4, 2, 0, 0, 0, true>), dim3(grid), dim3(256), 0, st, p);
   else
-    hipLaunchKernelGGL((rowgemm_kernel<KS, RE_NONE, RP_MLP, 0, 0, 0, 4, 2, 0, 0, 0, true>), dim3(grid), dim3(256), 0, st, p);
+    launch_last_layer<KS, 0, 4, 2, 0, 0, 0, true>(st, p, grid, hout);
 }
 }  // namespace
 
@@ -203,9 +212,9 @@ bool launch_row_qkv0_h16(hipStream_t st, const RowGemmParams& p, int ks, bool sm
   return true;
 }
 
-bool launch_row_layer_h16(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool waves8) {
-  if (ks == 8) launch_layer_h16_ks<8>(st, p, with_qkv, grid, waves8);
-  else if (ks == 4) launch_layer_h16_ks<4>(st, p, with_qkv, grid, waves8);
+bool launch_row_layer_h16(hipStream_t st, const RowGemmParams& p, int ks, bool with_qkv, unsigned grid, bool waves8, bool hout) {
+  if (ks == 8) launch_layer_h16_ks<8>(st, p, with_qkv, grid, waves8, hout);
+  else if (ks == 4) launch_layer_h16_ks<4>(st, p, with_qkv, grid, waves8, hout);
   else return false;
   return true;
 }

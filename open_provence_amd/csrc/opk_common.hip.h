@@ -570,5 +570,17 @@ constexpr int T_LEFT_LO = 1;
 constexpr int T_RIGHT_LO = 2;
 __host__ __device__ constexpr int term_count(int t) { return 1 + (t & 1) + ((t >> 1) & 1); }
 
+// Per-call hidden-state request (op_forward_packed_hidden).  Destination row of a packed row: its token index (packed
+// output, pad = 0) or [global sequence s0 + seq][position] (padded output, pad = its width).
+__device__ __forceinline__ size_t hidden_dst_row(int tok, int seq, int pos, int pad, int s0) {
+  return pad > 0 ? (size_t)(s0 + seq) * (size_t)pad + (size_t)pos : (size_t)tok;
+}
+// four consecutive features of one row at element offset `elem` of the request's output: fp32, or bf16 rounded to nearest
+// even (v_cvt_pk_bf16_f32).  Plain vector stores.
+__device__ __forceinline__ void hidden_store4(void* out, int bf16, size_t elem, float a, float b, float c, float d) {
+  if (bf16) *reinterpret_cast<uint2*>(reinterpret_cast<u16*>(out) + elem) = make_uint2(pack_bf16x2(a, b), pack_bf16x2(c, d));
+  else *reinterpret_cast<float4*>(reinterpret_cast<float*>(out) + elem) = make_float4(a, b, c, d);
+}
+
 
 }  // namespace opk

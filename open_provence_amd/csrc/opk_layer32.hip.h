@@ -102,6 +102,13 @@ struct Layer32Params {
   const float* rope_cos;
   const float* rope_sin;
   int max_pos;
+  // per-call hidden-state request (layer16p_hout_kernel only): the layer's output rows also go to hid_out in token order
+  const int32_t* row_tok;  // packed row -> token index (< 0: padding row)
+  const int32_t* row_seq;  // packed row -> sequence index within the chunk
+  void* hid_out;           // the entry of the request this layer's output is
+  int hid_bf16;            // 1: bf16 (round to nearest even), 0: fp32
+  int hid_pad;             // 0: token order [tokens][H]; > 0: [sequence][hid_pad][H]
+  int hid_s0;              // global index of the chunk's first sequence
 };
 
 // NT = hidden / 32.  QKV: the next layer's q / k / v^T follow (false: the last layer).  ALO: the activation-side

@@ -37,7 +37,9 @@ namespace opk {
 // fp16 packs (pack_*_kernel with f16 = 1), activations converted with v_cvt_pk_f16_f32, products on v_mfma_f32_16x16x32_f16.
 // One block of rowgemm_kernel: the instantiation's constants, the state its phases hand to each other -- all of it registers of
 // the calling wave once inlined -- and the phases as member functions (run() is the kernel body).
-template <int KS, int EPI, int PRO, int T1, int T2, int OLO, int WAVES, int MF, int TW, int TM, int F8, bool H16>
+// HOUT (rowgemm_hout_kernel, the last layer with the head fused): entry N of a per-call hidden-state request is stored from the
+// head's epilogue (rowgemm_final_head); every other instantiation has HOUT = false and is unchanged by it.
+template <int KS, int EPI, int PRO, int T1, int T2, int OLO, int WAVES, int MF, int TW, int TM, int F8, bool H16, bool HOUT = false>
 struct RowGemmBlock {
   static constexpr bool WLO = F8 == 2;
   static_assert(!H16 || (F8 == 0 && T1 == 0 && T2 == 0 && OLO == 0 && TW == 0 && TM == 0 && PRO != RP_KSTREAM && EPI != RE_GEGLU),
@@ -315,7 +317,7 @@ struct RowGemmBlock {
       } else {
         mlp_phase();
         if constexpr (EPI == RE_NONE) {
-          if (FIN_HEAD && p.fin_ln != nullptr) rowgemm_final_head<KS, MF>(p, sLn, m0, l15, g, acc1);
+          if (FIN_HEAD && p.fin_ln != nullptr) rowgemm_final_head<KS, MF, HOUT>(p, sLn, m0, l15, g, acc1);
           else residual_ln(no_, yes_, no_, nullptr);  // acc1 = x + o Wo^T + h Wo^T: the layer's output
           OPK_STAMP(4);
           OPK_DUMP();
@@ -360,8 +362,8 @@ struct RowGemmBlock {
 
 }  // namespace opk
 
-#define OPK_RG_TPL template <int KS, int EPI, int PRO, int T1, int T2, int OLO, int WAVES, int MF, int TW, int TM, int F8, bool H16>
-#define OPK_RG_BLOCK RowGemmBlock<KS, EPI, PRO, T1, T2, OLO, WAVES, MF, TW, TM, F8, H16>
+#define OPK_RG_TPL template <int KS, int EPI, int PRO, int T1, int T2, int OLO, int WAVES, int MF, int TW, int TM, int F8, bool H16, bool HOUT>
+#define OPK_RG_BLOCK RowGemmBlock<KS, EPI, PRO, T1, T2, OLO, WAVES, MF, TW, TM, F8, H16, HOUT>
 #include "opk_rowgemm_phase1.hip.h"
 #include "opk_rowgemm_mlp.hip.h"
 #include "opk_rowgemm_qkv_pairs.hip.h"
@@ -376,6 +378,18 @@ namespace opk {
 template <int KS, int EPI, int PRO, int T1, int T2, int OLO, int WAVES, int MF = 2, int TW = 0, int TM = 0, int F8 = 0, bool H16 = false>
 __global__ __launch_bounds__(WAVES * 64, PRO == RP_MLP ? (WAVES == 8 ? 2 : 1) : ((MF == 1 && WAVES == 8) ? 4 : 2)) void rowgemm_kernel(RowGemmParams p) {
   using Block = RowGemmBlock<KS, EPI, PRO, T1, T2, OLO, WAVES, MF, TW, TM, F8, H16>;
+  __shared__ __attribute__((aligned(16))) u16 sW[2][Block::STAGE_ALLOC];
+  __shared__ __attribute__((aligned(16))) float sLn[Block::SLN_SIZE];
+  Block block(p, sW, sLn);
+  block.run();
+}
+
+// The last whole-layer launch with the head fused (RE_NONE, RP_MLP, p.fin_ln set) when the forward carries a hidden-state request
+// for entry N: rowgemm_kernel's instantiation plus the stores of rowgemm_final_head<.., HOUT = true>.
+template <int KS, int EPI, int PRO, int T1, int T2, int OLO, int WAVES, int MF = 2, int TW = 0, int TM = 0, int F8 = 0, bool H16 = false>
+__global__ __launch_bounds__(WAVES * 64, PRO == RP_MLP ? (WAVES == 8 ? 2 : 1) : ((MF == 1 && WAVES == 8) ? 4 : 2)) void rowgemm_hout_kernel(RowGemmParams p) {
+  static_assert(EPI == RE_NONE && PRO == RP_MLP, "entry N is stored by the head epilogue of the last whole-layer launch");
+  using Block = RowGemmBlock<KS, EPI, PRO, T1, T2, OLO, WAVES, MF, TW, TM, F8, H16, true>;
   __shared__ __attribute__((aligned(16))) u16 sW[2][Block::STAGE_ALLOC];
   __shared__ __attribute__((aligned(16))) float sLn[Block::SLN_SIZE];
   Block block(p, sW, sLn);

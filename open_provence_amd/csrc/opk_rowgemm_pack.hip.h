@@ -87,6 +87,12 @@ struct RowGemmParams {
   const float* emb_table;    // [vocab][H] fp32
   const int32_t* emb_ids;    // [tokens]
   int emb_vocab;
+  // RP_MLP + RE_NONE with fin_ln, rowgemm_hout_kernel only: entry N of a per-call hidden-state request (op_forward_packed_hidden)
+  // -- the rows the head reads (normalised, or the raw rows under fin_pre_norm) also go to hid_out, 8 features per lane
+  void* hid_out;
+  int hid_bf16;  // 1: bf16 (round to nearest even), 0: fp32
+  int hid_pad;   // 0: token order [tokens][H]; > 0: [sequence][hid_pad][H]
+  int hid_s0;    // global index of the chunk's first sequence (row_seq is chunk-local)
 };
 
 // source row of packed row `pr` (0..31) of chunk `c`

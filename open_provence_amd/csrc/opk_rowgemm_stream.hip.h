@@ -187,7 +187,9 @@ __device__ __forceinline__ T& pick_ref(T& a, T& b) {
 // as rowgemm_kernel's layer_ln; the head's two dot products ride on the normalised values (or, fin_pre_norm, on the raw row), the
 // four lanes of a row are summed, the lane of column group 0 writes the token's logits and keep-probability.
 // sLn: [mlp_norm | final_norm | pruning head row 0 | row 1] weights in LDS; acc1: the block's rows (x after the MLP).
-template <int KS, int MF>
+// HOUT (rowgemm_hout_kernel): the row the head reads -- normalised, or the raw row under fin_pre_norm -- also goes to entry N of
+// the per-call hidden-state request (RowGemmParams::hid_out), 8 consecutive features per lane and k-step.
+template <int KS, int MF, bool HOUT = false>
 __device__ __forceinline__ void rowgemm_final_head(const RowGemmParams& p, const float* sLn, int m0, int l15, int g,
                                                    const f32x4 (&acc1)[2 * KS][MF]) {
   constexpr int K = KS * 32, NF1 = 2 * KS;
@@ -201,6 +203,8 @@ __device__ __forceinline__ void rowgemm_final_head(const RowGemmParams& p, const
     const int row = m0 + mf * 16 + l15;
     const int tok = p.row_tok[row];
     const bool is_cls = tok >= 0 && p.row_pos[row] == 0;
+    size_t hid_row = 0;
+    if constexpr (HOUT) hid_row = tok >= 0 ? hidden_dst_row(tok, p.row_seq[row], p.row_pos[row], p.hid_pad, p.hid_s0) * K : 0;
     f32x2 v[2 * NF1];
 #pragma unroll
     for (int nf = 0; nf < NF1; ++nf) {
@@ -245,6 +249,16 @@ __device__ __forceinline__ void rowgemm_final_head(const RowGemmParams& p, const
         const f32x2 src = pre ? v[4 * ks + j] : y[j];
         d0[j & 1] = pk_fma(src, pa[j], d0[j & 1]);
         d1[j & 1] = pk_fma(src, pc[j], d1[j & 1]);
+      }
+      if constexpr (HOUT) {
+        if (tok >= 0) {
+          f32x2 hv[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) hv[j] = pre ? v[4 * ks + j] : y[j];
+          const size_t e = hid_row + ks * 32 + g * 8;
+          hidden_store4(p.hid_out, p.hid_bf16, e, hv[0].x, hv[0].y, hv[1].x, hv[1].y);
+          hidden_store4(p.hid_out, p.hid_bf16, e + 4, hv[2].x, hv[2].y, hv[3].x, hv[3].y);
+        }
       }
       if (is_cls) {  // one row in a sequence: the ranking head's input
         float* dst = p.fin_cls + (size_t)p.row_seq[row] * K + ks * 32 + g * 8;

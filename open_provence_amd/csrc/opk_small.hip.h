@@ -199,6 +199,30 @@ __global__ __launch_bounds__(256) void capture_rows_kernel(const float* __restri
   row_store_f32(rv, out + (size_t)tok * H, H, lane);
 }
 
+// One entry of a per-call hidden-state request (op_forward_packed_hidden): the residual stream rows of real tokens to the
+// request's output in its dtype (fp32 / bf16) and layout (token order, or [s0 + seq][pad][H]).  lnw != nullptr: the row goes
+// through final_norm first, with final_ln_prune_kernel's arithmetic.
+__global__ __launch_bounds__(256) void hidden_rows_kernel(const float* __restrict__ x, const float* __restrict__ lnw, float eps,
+                                                          int H, int r_pad, const int32_t* __restrict__ row_tok,
+                                                          const int32_t* __restrict__ row_seq, const int32_t* __restrict__ row_pos,
+                                                          int s0, int pad, int bf16, void* __restrict__ out) {
+  const int lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= r_pad) return;
+  const int tok = row_tok[row];
+  if (tok < 0) return;
+  RowVec rv;
+  row_load(x + (size_t)row * H, H, lane, rv);
+  if (lnw) row_layer_norm(rv, lnw, H, lane, eps);
+  const size_t base = hidden_dst_row(tok, row_seq[row], row_pos[row], pad, s0) * (size_t)H;
+  const int nchunk = H >> 2;
+#pragma unroll
+  for (int k = 0; k < LN_MAX_CHUNKS; ++k) {
+    const int c = lane + 64 * k;
+    if (c < nchunk) hidden_store4(out, bf16, base + 4 * c, rv.v[k].x, rv.v[k].y, rv.v[k].z, rv.v[k].w);
+  }
+}
+
 // final_norm + OpenProvenceHead Linear(H, 2) on every real token (standalone.py:446-448); keeps the
 // normalised row for the ranking head (CLS row or, for mean pooling, every row -- written over x).
 // pre_norm: the pruning head reads the row BEFORE final_norm (hidden_states[-1] of transformers 4.x, see

@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import os
 from contextlib import contextmanager
+from dataclasses import dataclass
 from typing import Iterator, Mapping, Sequence
 
 import numpy as np
@@ -35,6 +36,21 @@ _ENV_FLAGS = {
     "OPEN_PROVENCE_PANEL_F8_WI": _lib.OP_FLAG_PANEL_F8_WI,
     "OPEN_PROVENCE_NO_LAYER_PAIRS": _lib.OP_FLAG_NO_LAYER_PAIRS,
 }
+
+
+@dataclass(frozen=True)
+class HiddenRequest:
+    """The hidden states one forward returns beside its logits (``op_forward_packed_hidden``).
+
+    ``layers``: the entries 0 .. num_layers to write (entry 0 = embedding LayerNorm output, entry i = output of layer i-1, entry
+    num_layers = the pruning head's input: the ``final_norm`` output, or the raw last layer under ``prune_pre_final_norm``);
+    None = all of them.  ``dtype``: ``torch.float32`` or ``torch.bfloat16`` (the fp32 state rounded to nearest even).
+    ``pad_width``: 0 = packed ``[n_sel, total_tokens, H]``; > 0 = padded ``[n_sel, n_seqs, pad_width, H]`` (zeros beyond each
+    sequence's length; at least ``max_seqlen``)."""
+
+    layers: "Sequence[int] | None" = None
+    dtype: torch.dtype = torch.float32
+    pad_width: int = 0
 
 
 def parse_precision(precision: "str | Mapping[str, int]") -> tuple[int, list[int]]:
@@ -380,17 +396,19 @@ class HipEncoder:
             )
         return bool(changed.value)
 
-    def forward_packed_checked(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None):
+    def forward_packed_checked(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None):
         """``forward_packed`` + the range guard: on kernel sets 3 / 4 the outputs are tested for NaN / Inf (one device
         reduction, one synchronisation) and a non-finite batch is repeated on the (hi, lo) bf16 sets.  On those sets
-        nothing is tested: whatever comes out is what the reference's arithmetic gives."""
+        nothing is tested: whatever comes out is what the reference's arithmetic gives.  With a ``hidden`` request the
+        result is ``(prune, rank, hidden_states)``, the states of the forward whose logits are returned."""
 
-        prune, rank = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob)
+        out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden)
         if self.f8_active():
+            prune, rank = out[0], out[1]
             ok = torch.isfinite(rank).all() & torch.isfinite(prune).all()
             if not bool(ok.item()) and self.fall_back_from_f8("forward"):
-                prune, rank = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob)
-        return prune, rank
+                out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden)
+        return out
 
     # -- forward ---------------------------------------------------------------------------------
     def _ensure_workspace(self, n_seqs: int, total_tokens: int, max_seqlen: int) -> torch.Tensor:
@@ -435,10 +453,14 @@ class HipEncoder:
         cu_seqlens_host: np.ndarray,
         max_seqlen: int,
         keep_prob: torch.Tensor | None = None,
-    ) -> tuple[torch.Tensor, torch.Tensor]:
+        hidden: "HiddenRequest | None" = None,
+    ) -> tuple[torch.Tensor, ...]:
         """``ids[T]`` / ``cu_seqlens[B+1]`` int32 on this device -> (prune_logits[T, 2], rank_logits[B, nl]) fp32.
         ``keep_prob`` (optional, fp32 ``[T]`` on this device) additionally receives
-        ``softmax(prune_logits, -1)[:, 1]``, evaluated in the head kernel.
+        ``softmax(prune_logits, -1)[:, 1]``, evaluated in the head kernel.  ``hidden`` (a :class:`HiddenRequest`): the
+        result is ``(prune, rank, hidden_states)``, the selected entries written by the same kernels in one device buffer
+        (packed ``[n_sel, T, H]`` or padded ``[n_sel, B, pad_width, H]``, zeros at padding); the logits are bit-identical
+        to those of the same forward without the request.
 
         Asynchronous on the current torch stream of ``self.device``."""
 
@@ -446,10 +468,11 @@ class HipEncoder:
         cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
         if cu_host.shape[0] != n_seqs + 1:
             raise ValueError("cu_seqlens_host length mismatch")
+        req = self._hidden_request(hidden, n_seqs, total, int(max_seqlen)) if hidden is not None else None
         prune = torch.empty((total, 2), dtype=torch.float32, device=self.device)
         rank = torch.empty((n_seqs, self.dims.num_labels), dtype=torch.float32, device=self.device)
         if n_seqs == 0:
-            return prune, rank
+            return (prune, rank) if req is None else (prune, rank, req[0])
         ws = self._ensure_workspace(n_seqs, total, int(max_seqlen))
         if self._capture is not None:
             self._capture = torch.zeros(
@@ -461,9 +484,41 @@ class HipEncoder:
             stream = torch.cuda.current_stream(self.device).cuda_stream
             self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, int(max_seqlen),
                                  prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None,
-                                 ws, stream)
-            self._maybe_audit(ids, cu_seqlens, cu_host, n_seqs, total, int(max_seqlen), prune, rank, keep_prob, ws, stream)
-        return prune, rank
+                                 ws, stream, req[1] if req is not None else None)
+            self._maybe_audit(ids, cu_seqlens, cu_host, n_seqs, total, int(max_seqlen), prune, rank, keep_prob, ws, stream,
+                              req[1] if req is not None else None)
+        return (prune, rank) if req is None else (prune, rank, req[0])
+
+    def _hidden_request(self, hidden: "HiddenRequest", n_seqs: int, total: int, max_seqlen: int):
+        """-> (output tensor, ``_lib.OpHiddenRequest``) of one forward; the struct keeps its select array alive."""
+
+        if not isinstance(hidden, HiddenRequest):
+            raise TypeError("hidden must be a HiddenRequest")
+        n_entries = self.dims.num_layers + 1
+        layers = range(n_entries) if hidden.layers is None else [int(i) for i in hidden.layers]
+        if any(i < 0 or i >= n_entries for i in layers):
+            raise ValueError(f"hidden.layers must lie in 0 .. {n_entries - 1} (entry {n_entries - 1} = the pruning head's input)")
+        selected = sorted(set(layers))
+        dtypes = {torch.float32: _lib.OP_HIDDEN_F32, torch.bfloat16: _lib.OP_HIDDEN_BF16}
+        if hidden.dtype not in dtypes:
+            raise ValueError("hidden.dtype must be torch.float32 or torch.bfloat16")
+        pad = int(hidden.pad_width)
+        if pad < 0 or (pad > 0 and pad < max_seqlen):
+            raise ValueError(f"hidden.pad_width must be 0 (packed) or at least max_seqlen ({max_seqlen}), got {pad}")
+        H = self.dims.hidden_size
+        if pad > 0:  # (positions beyond a sequence's length are not written)
+            out = torch.zeros((len(selected), n_seqs, pad, H), dtype=hidden.dtype, device=self.device)
+        else:
+            out = torch.empty((len(selected), total, H), dtype=hidden.dtype, device=self.device)
+        flags = (ctypes.c_uint8 * n_entries)(*[1 if i in selected else 0 for i in range(n_entries)])
+        req = _lib.OpHiddenRequest()
+        req.struct_bytes = ctypes.sizeof(_lib.OpHiddenRequest)
+        req.dtype = dtypes[hidden.dtype]
+        req.pad_width = pad
+        req.select = ctypes.cast(flags, ctypes.POINTER(ctypes.c_uint8))
+        req.out_dev = ctypes.c_void_p(out.data_ptr()) if out.numel() else None
+        req._flags = flags  # (keeps the array alive as long as the struct)
+        return out, req
 
     # -- the audit under a process group: ONE verdict for all ranks (sharding.collective_audit) -----------------------
     @property
@@ -520,11 +575,11 @@ class HipEncoder:
                           RuntimeWarning, stacklevel=3)
         return after
 
-    def _maybe_audit(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream) -> None:
+    def _maybe_audit(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req=None) -> None:
         """The first-real-batch audit of a synthetically calibrated kernel set, from EITHER forward entry point
         (``forward_packed`` / ``forward_packed_on``).  Skipped -- and left pending -- for batches under 64 tokens, while hidden
-        states are captured, and while the stream is being captured into a hipGraph (the audit synchronises and switches the
-        handle's kernel set in the middle of the forward)."""
+        states are captured (the debug hook; a per-call request is audited like any batch), and while the stream is being
+        captured into a hipGraph (the audit synchronises and switches the handle's kernel set in the middle of the forward)."""
 
         if not self.__dict__.get("_audit_pending") or total < 64 or self._capture is not None:
             return
@@ -532,15 +587,17 @@ class HipEncoder:
             return
         if torch.cuda.is_current_stream_capturing():
             return
-        self._audit_first_batch(ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream)
+        self._audit_first_batch(ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req)
 
-    def _audit_first_batch(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream) -> None:
+    def _audit_first_batch(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream,
+                           hidden_req=None) -> None:
         """The calibration ran on synthetic token ids; the FIRST real batch a calibrated model sees is its audit: the same
         batch once more through the reference kernel set of the calibration, max |logit difference| against what the chosen
         set just returned.  Within ``audit_factor`` (3) x the calibration tolerance -- 3e-4, still 3 x inside the path's bar;
         the forward fuzz puts the worst row of other inputs at <= 2.7 x a calibration batch's maximum -- the choice stands
         (one synchronisation, two extra forwards, once per load).  Beyond it, or non-finite: the model goes back to the
-        default selection of ``op_weights_ready`` for good, warns, and THIS batch is recomputed there before it is returned."""
+        default selection of ``op_weights_ready`` for good, warns, and THIS batch is recomputed there before it is returned
+        (with the caller's hidden-state request, ``hidden_req``: the reference forward of the audit itself writes none)."""
 
         self.__dict__["_audit_pending"] = False
         cal = self.calibration or {}
@@ -576,7 +633,8 @@ class HipEncoder:
             RuntimeWarning, stacklevel=4,
         )
         self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, max_seqlen,
-                             prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None, ws, stream)
+                             prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None, ws, stream,
+                             hidden_req)
 
     def _check_packed_inputs(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, keep_prob: torch.Tensor | None) -> tuple[int, int]:
         """Shared argument checks of forward_packed / forward_packed_on -> (total_tokens, n_seqs)."""
@@ -594,10 +652,12 @@ class HipEncoder:
         return total, int(cu_seqlens.numel()) - 1
 
     def _forward_native(self, ids_ptr, cu_ptr, cu_host: np.ndarray, n_seqs: int, total: int, max_seqlen: int,
-                        prune_ptr, rank_ptr, keep_ptr, ws: torch.Tensor, stream: int) -> None:
+                        prune_ptr, rank_ptr, keep_ptr, ws: torch.Tensor, stream: int, hidden_req=None) -> None:
         base = ws.data_ptr()
         aligned = (base + 255) // 256 * 256
-        code = self.lib.op_forward_packed(
+        extra = () if hidden_req is None else (ctypes.byref(hidden_req),)
+        entry = self.lib.op_forward_packed if hidden_req is None else self.lib.op_forward_packed_hidden
+        code = entry(
             self._handle,
             ctypes.c_void_p(ids_ptr),
             ctypes.c_void_p(cu_ptr),
@@ -611,8 +671,9 @@ class HipEncoder:
             ctypes.c_void_p(aligned),
             ctypes.c_size_t(ws.numel() - (aligned - base)),
             ctypes.c_void_p(stream),
+            *extra,
         )
-        _lib.check(self.lib, self._handle, code, "op_forward_packed")
+        _lib.check(self.lib, self._handle, code, "op_forward_packed" if hidden_req is None else "op_forward_packed_hidden")
 
     def _split_streams(self) -> dict:
         """Two HIP streams of their own (hipExtStreamCreateWithCUMask with the full mask: own hardware queues, no CU partition since
@@ -661,6 +722,7 @@ class HipEncoder:
         cu_seqlens_host: np.ndarray,
         max_seqlen: int,
         keep_prob: torch.Tensor | None = None,
+        hidden: "HiddenRequest | None" = None,
     ) -> tuple[torch.Tensor, torch.Tensor]:
         """``forward_packed`` enqueued on pipeline ``part`` (0 or 1): its own HIP stream (own hardware queue; the whole chip
         since round 6, see ``_split_streams``) and its own workspace -- nothing is ordered against the caller's current stream or the other
@@ -675,6 +737,8 @@ class HipEncoder:
             raise ValueError("part must be 0 or 1")
         if self._capture is not None:
             raise RuntimeError("hidden-state capture is not available on the pipelined path (use forward_packed)")
+        if hidden is not None:
+            raise NotImplementedError("hidden-state requests are not available on the pipelined path (use forward_packed(hidden=...))")
         total, n_seqs = self._check_packed_inputs(ids, cu_seqlens, keep_prob)
         cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
         if cu_host.shape[0] != n_seqs + 1:

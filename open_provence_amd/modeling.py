@@ -33,7 +33,7 @@ import torch
 
 from . import pipeline as pl
 from .config import DEFAULT_PROCESS_THRESHOLD, EncoderDims, OpenProvenceConfig
-from .engine import HipEncoder, require_gpu
+from .engine import HiddenRequest, HipEncoder, require_gpu
 from .packing import pack_padded, pack_rows, unpack_to_padded
 from .pipeline import ContextState, FragmentRecord, RawPrediction
 from .splitters import SentenceSplitter, is_builtin_splitter, resolve_sentence_splitter
@@ -495,11 +495,18 @@ class OpenProvenceModel:
         attention_mask: torch.Tensor | None = None,
         labels: torch.Tensor | None = None,
         return_dict: bool | None = None,
+        output_hidden_states: bool | None = None,
         **kwargs: Any,
     ) -> OpenProvenceOutput | tuple[torch.Tensor, ...]:
         """``input_ids[B, L]`` (+ right-padded ``attention_mask``) -> ``ranking_logits[B, nl]`` and
         ``pruning_logits[B, L, 2]`` (fp32, on the GPU; zeros at padding positions).  ``token_type_ids`` and
-        other HF kwargs are accepted and ignored, as ModernBERT ignores them."""
+        other HF kwargs are accepted and ignored, as ModernBERT ignores them.
+
+        ``output_hidden_states=True``: ``hidden_states`` is a tuple of num_layers + 1 fp32 tensors ``[B, L, H]`` (zeros at
+        padding positions) as the reference returns them (standalone.py:1689, 1727): the embedding LayerNorm output, the
+        output of every layer, and last the pruning head's input (``final_norm`` output, or the raw last layer under
+        ``prune_pre_final_norm``).  They are views of one device buffer ``[N + 1, B, L, H]`` that the forward's own
+        kernels write; the logits are bit-identical to those of the same call without the flag."""
 
         if input_ids is None:
             raise ValueError("input_ids must be provided")
@@ -512,12 +519,20 @@ class OpenProvenceModel:
         ids = torch.from_numpy(ids_np).to(dev)
         cu = torch.from_numpy(cu_np).to(dev)
         # (the fp16 + e4m3 kernel sets are range-guarded: a non-finite result is repeated on the (hi, lo) bf16 sets)
-        prune, rank = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len)
+        hidden_states = None
+        if output_hidden_states:
+            prune, rank, hidden = self.encoder.forward_packed_checked(
+                ids, cu, cu_np, max_len, hidden=HiddenRequest(dtype=torch.float32, pad_width=width)
+            )
+            # ([N + 1, B, L, H]; with L = 0 the request is packed and empty: the same shape, no data)
+            hidden_states = tuple(hidden.reshape(hidden.shape[0], int(input_ids.shape[0]), width, hidden.shape[-1]).unbind(0))
+        else:
+            prune, rank = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len)
         pruning_logits = unpack_to_padded(prune, cu_np, width)
         if return_dict is not None and not return_dict:
             return (rank, pruning_logits)
         return OpenProvenceOutput(
-            loss=None, logits=rank, ranking_logits=rank, pruning_logits=pruning_logits, hidden_states=None, attentions=None
+            loss=None, logits=rank, ranking_logits=rank, pruning_logits=pruning_logits, hidden_states=hidden_states, attentions=None
         )
 
     def __call__(self, *args: Any, **kwargs: Any):
@@ -2093,8 +2108,9 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
         super().__init__(config, **kwargs)
         self.num_labels = config.num_pruning_labels
 
-    def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, **kwargs: Any):
-        base = OpenProvenceModel.forward(self, input_ids=input_ids, attention_mask=attention_mask, labels=labels, return_dict=True)
+    def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, output_hidden_states=None, **kwargs: Any):
+        base = OpenProvenceModel.forward(self, input_ids=input_ids, attention_mask=attention_mask, labels=labels, return_dict=True,
+                                         output_hidden_states=output_hidden_states)
         if return_dict is not None and not return_dict:
             return (base["pruning_logits"],)
         return OpenProvenceOutput(
@@ -2102,7 +2118,7 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
             logits=base["pruning_logits"],
             pruning_logits=base["pruning_logits"],
             ranking_logits=base["ranking_logits"],
-            hidden_states=None,
+            hidden_states=base["hidden_states"],
             attentions=None,
         )
 

@@ -1,6 +1,7 @@
 #!/usr/bin/env python
-"""Fingerprint of the row-path kernels' ISA: per kernel the instruction count, register counts, scratch, and a hash of the
-mnemonic sequence (register names ignored).  Usage: isa_fp.py <csrc dir> <out json>"""
+"""Fingerprint of the row-path kernels' ISA (op_launch_row.hip, every part) and of the whole-layer / attention units
+(op_launch_layer32.hip: the 32x32x16 and wave-pair kernels; op_launch_attn.hip): per kernel the instruction count, register
+counts, scratch, and a hash of the mnemonic sequence (register names ignored).  Usage: isa_fp.py <csrc dir> <out json>"""
 import hashlib, json, re, subprocess, sys, tempfile
 from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
@@ -9,13 +10,17 @@ csrc = Path(sys.argv[1]); out = Path(sys.argv[2])
 flags = "--offload-arch=gfx950 -O3 -std=c++17 -fno-slp-vectorize --cuda-device-only -S".split()
 tmp = Path(tempfile.mkdtemp())
 
-def unit(part):
-    dst = tmp / f"row{part}.s"
-    subprocess.run(["hipcc", *flags, f"-DOPL_ROW_PART={part}", "-o", str(dst), str(csrc / "op_launch_row.hip")], check=True, capture_output=True)
+UNITS = [(f"row{part}", "op_launch_row.hip", [f"-DOPL_ROW_PART={part}"]) for part in range(7)]
+UNITS += [("layer32", "op_launch_layer32.hip", []), ("attn", "op_launch_attn.hip", [])]
+
+def unit(u):
+    name, src, defines = u
+    dst = tmp / f"{name}.s"
+    subprocess.run(["hipcc", *flags, *defines, "-o", str(dst), str(csrc / src)], check=True, capture_output=True)
     return dst.read_text()
 
-with ThreadPoolExecutor(7) as pool:
-    texts = list(pool.map(unit, range(7)))
+with ThreadPoolExecutor(len(UNITS)) as pool:
+    texts = list(pool.map(unit, UNITS))
 fp = {}
 for t in texts:
     for m in re.finditer(r"^(_ZN3opk[^:\s]+):[^\n]*\n(.*?)\n\.Lfunc_end\d+:", t, re.S | re.M):
