@@ -28,7 +28,9 @@ What the kernels compute on purpose and the model restates (rather than a bound 
     at 3-term bf16 (sets 1 / 0 too); o is written in the fp16 + e4m3 format for the output projection, and the
     whole-layer kernel carries the MLP activation h as an fp16 (hi, lo) pair (K is streamed 32 at a time: too short for
     the e4m3 shape) against fp16(W) (set 3) plus fp16(W - fp16(W)) (set 4): schemes f16x2 / f16x3.  The panel path keeps
-    every family of those sets in the fp16 + e4m3 format.
+    every family of those sets in the fp16 + e4m3 format;
+  * kernel sets 8 / 9 under a layer mask (op_select_mlp_correction_layers): a layer outside the mask runs the "f16" set's
+    MLP -- single-plane fp16 LN(x), Wi and MLP output projection on the fp16 packs (``Arith.mlp_layers``).
 
 Not modelled (below the 1e-6 floor of the comparison, or outside what a contraction sees): fp32 accumulation order,
 fp32 LayerNorm / GELU / RoPE / softmax exponent, the fp32 residual stream, fp16 subnormal flushing of p below 2^-24.
@@ -148,6 +150,9 @@ BF16_WEIGHT_SETS = tuple(n for n, t in KERNEL_SETS.items()
 # composite set -> the set whose kernels it replaces in some families (a composite silently running them must be seen)
 BASE_SET = {"bf16x3+wi-f16-f8-w": "bf16x3", "bf16-weights+wi-f16-f8": "bf16-weights", "f16+mlp-f16-f8-w": "f16",
             "f16+mlp-f16-f8": "f16", "f16-f8-w+attn-f16": "f16-f8-w", "f16-f8+attn-f16": "f16-f8"}
+# kernel sets 8 / 9 take a per-layer mask: outside it the two MLP families run at the "f16" set's scheme
+MLP_FAMILIES = ("wi", "mlp_out")
+MASKED_SETS = ("f16+mlp-f16-f8-w", "f16+mlp-f16-f8")
 # row path (hidden <= 256): (layer 0's wqkv scheme, mlp_out scheme) of sets 3 / 4 -- see the module docstring
 ROW_PATH = {"f16-f8": ("bf16x2", "f16x2"), "f16-f8-w": ("bf16x3", "f16x3")}
 
@@ -159,18 +164,24 @@ class Arith:
     schemes: Mapping[str, Scheme]
     layer0_wqkv: "Scheme | None" = None
     window_delta: int = 0  # added to half_window of the sliding-window layers (mutation: -1 = one key short)
+    # kernel sets 8 / 9 layer by layer (op_select_mlp_correction_layers): the layers whose MLP keeps the fp16 + e4m3
+    # format; in every other layer wi and mlp_out run on the "f16" set's kernels.  None = the whole depth.
+    mlp_layers: "frozenset[int] | None" = None
 
     def scheme(self, family: str, layer: int) -> Scheme:
         if family == "wqkv" and layer == 0 and self.layer0_wqkv is not None:
             return self.layer0_wqkv
+        if family in MLP_FAMILIES and self.mlp_layers is not None and layer not in self.mlp_layers:
+            return SCHEMES["f16"]
         return self.schemes[family]
 
     def with_family(self, family: str, scheme: Scheme) -> "Arith":
         return replace(self, schemes={**self.schemes, family: scheme})
 
 
-def arith_for(kernel_set: str, path: str = "row") -> Arith:
-    """The model of ``kernel_set`` ("exact" or a name of :data:`KERNEL_SETS`) on ``path`` ("row" / "panel" / "tiled")."""
+def arith_for(kernel_set: str, path: str = "row", mlp_layers: "Sequence[int] | None" = None) -> Arith:
+    """The model of ``kernel_set`` ("exact" or a name of :data:`KERNEL_SETS`) on ``path`` ("row" / "panel" / "tiled").
+    ``mlp_layers``: the layer mask of kernel sets 8 / 9 (the layers that keep the fp16 + e4m3 MLP; None = all)."""
 
     if kernel_set == "exact":
         return Arith({f: SCHEMES["exact"] for f in FAMILIES})
@@ -178,7 +189,10 @@ def arith_for(kernel_set: str, path: str = "row") -> Arith:
     layer0 = None
     if path == "row" and kernel_set in ROW_PATH:
         layer0, table["mlp_out"] = ROW_PATH[kernel_set]
-    return Arith({f: SCHEMES[v] for f, v in table.items()}, SCHEMES[layer0] if layer0 else None)
+    if mlp_layers is not None and kernel_set not in MASKED_SETS:
+        raise ValueError(f"a layer mask applies to {MASKED_SETS}, not to {kernel_set!r}")
+    return Arith({f: SCHEMES[v] for f, v in table.items()}, SCHEMES[layer0] if layer0 else None,
+                 mlp_layers=None if mlp_layers is None else frozenset(int(li) for li in mlp_layers))
 
 
 # -- forward ----------------------------------------------------------------------------------------------------------------
@@ -437,3 +451,28 @@ def bf16_valued(state: Mapping[str, torch.Tensor]) -> dict[str, torch.Tensor]:
     their error and hide every smaller departure of the kernels."""
 
     return {k: v.to(torch.bfloat16).to(torch.float32) for k, v in state.items()}
+
+
+MLP_ISOLATING_SHIFT = 8
+
+
+def mlp_isolating_state_dict(state: Mapping[str, torch.Tensor], shift: int = MLP_ISOLATING_SHIFT) -> dict[str, torch.Tensor]:
+    """Every ``attn.Wo.weight`` x 2^-shift, put on fp16's grid and held as fp32 (apply after :func:`peaked_state_dict` /
+    :func:`bf16_valued`).  A power of two changes no operand's rounding pattern; it shrinks what the attention side adds to
+    the residual stream, and that side's error with it, 2^shift-fold, so the MLP's arithmetic dominates every entry's error:
+    the correction terms of the MLP of kernel sets 8 - 11, invisible under their single-pass fp16 attention side on the plain
+    weights, come out at 5 - 18 x the bound (tests/test_arith_model.py).
+
+    Why fp16's grid: the library refuses every kernel set with an fp16 weight plane when the part of a tensor that fp16's
+    subnormal grid loses carries more than 2^-36 of the tensor's energy (note_f16_fit in opk_common.hip.h).  A uniform
+    (+-sqrt(3 / H)) tensor x 2^-8 loses about 2^-29 at H = 512.  Rounded onto the grid the loss is zero, and the model and
+    the kernels read identical weights.  The recipe is for the sets whose weight hi plane is fp16 (3, 4, 8 - 11): the damped
+    tensor is fp16-valued, not bf16-valued.  Single elements of it are fp16 subnormals and underflow in the weight's e4m3
+    plane (stored x 2^6); the model converts them as torch does (gradual underflow, RNE); that branch is damped 2^shift-fold, and the kernels'
+    attention-output entries agree with the model on every damped case (profiles/kernel_set_conformance.txt)."""
+
+    out = dict(state)
+    for name, t in state.items():
+        if name.endswith("attn.Wo.weight"):
+            out[name] = (t.to(torch.float32) * 2.0**-shift).to(torch.float16).to(torch.float32)
+    return out

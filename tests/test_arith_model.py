@@ -3,14 +3,23 @@ rounded, the inputs of the GPU conformance tests reach the branches they are mea
 apply would see a subtly wrong kernel.
 
 Mutations: each lo term dropped, each fp16 family on bf16, the sliding window one key short, the e4m3 lo scale off by one,
-emulated on the GPU test's own models, rows and O(1) weights (bf16-valued for the sets without a lo(W) term, as there).
-157 of 188 exceed the bound.  The 31 that do not are listed in UNDETECTED with the reason; they are all on the sets
-whose single-pass fp16 attention (10, 11) or attention side (8, 9) dominates their error, plus the bf16 rounding of an
-MLP activation that the row path carries as an fp16 pair.  The test fails if that list is wrong in either direction.
+emulated on the GPU test's own models, rows and O(1) weights (bf16-valued for the sets without a lo(W) term, as there) --
+plain and, for the sets the GPU test runs on it, MLP-isolating (every attn.Wo x 2^-8: am.mlp_isolating_state_dict).  A
+mutation counts as seen when either recipe's bound sees it.  On the default models (row, panel512) 177 of 188 exceed a
+bound; the plain recipe alone misses 31, and the 20 of those that sit in the Wi GEMM or the MLP output projection of the
+composite sets 8 - 11 come out at 5 - 18 x on the MLP-isolating one.  The 11 that stay are listed in UNDETECTED with the
+reason: the q / k / v and output projections' correction terms of sets 10 / 11, at the size of the single-plane fp16
+rounding of q, k, v^T and p next to them, and the bf16 rounding of an MLP activation that the row path carries as an fp16
+pair.  On the added shapes (768 x 1152, hidden 128, 256 x 320) 93 of 100 exceed a bound and the 7 that do not carry the
+same names.  The test fails if the list is wrong in either direction.  Detections under 1.2 x are printed as thin.
+
+The layer mask of kernel sets 8 / 9: the model of a mask equals its neighbours' up to the first layer where they differ and
+is separated from them behind it (figures printed: the yardstick of tests/test_kernel_set_masks.py).
 """
 
 from __future__ import annotations
 
+import dataclasses
 import math
 
 import numpy as np
@@ -147,26 +156,29 @@ def test_window_edges_land_on_and_between_tile_boundaries(window):
 SENS_CASES = [("row", s) for s in ("bf16x3", "bf16-weights", "bf16", "f16-f8", "f16-f8-w", "f16")] + [
     ("panel512", s) for s in ("f16-f8", "f16-f8-w", "bf16x3+wi-f16-f8-w", "bf16-weights+wi-f16-f8", "f16+mlp-f16-f8-w",
                               "f16+mlp-f16-f8", "f16-f8-w+attn-f16", "f16-f8+attn-f16")]
+# ... and the shapes the conformance test adds, under the sets they add
+SHAPE_SENS_CASES = [("engte", "f16-f8-w"), ("engte", "f16+mlp-f16-f8-w"), ("engte", "f16-f8-w+attn-f16"),
+                    ("row128", "f16-f8-w"), ("row128", "f16"), ("row320", "f16-f8-w")]
+THIN = 1.2  # a mutation detected at less than this x the bound is printed as thin (no assertion hangs on it)
 
-# Mutations the GPU test's bound cannot see on its O(1) inputs (the model, rows and weights of its default case), per
-# (model, set).  Each is a correction term well below the error of a cheaper family of the same set.
-_UNDETECTED: dict[tuple[str, str], list[str]] = {
-    # the whole-layer kernel carries h as an fp16 (hi, lo) pair: a bf16 pair is as exact
-    ("row", "f16-f8"): ["bf16 for fp16: mlp_out"],
-    ("row", "f16-f8-w"): ["bf16 for fp16: mlp_out"],
-    # the single-pass fp16 attention side dominates the error of the MLP's correction terms
-    ("panel512", "f16+mlp-f16-f8-w"): ["drop left lo: mlp_out", "drop left lo: wi", "drop right lo: mlp_out", "drop right lo: wi",
-                                       "lo shift off by one: mlp_out", "lo shift off by one: wi"],
-    ("panel512", "f16+mlp-f16-f8"): ["drop left lo: mlp_out", "drop left lo: wi", "lo shift off by one: mlp_out", "lo shift off by one: wi"],
-    # the single-pass fp16 attention dominates the error of the weight GEMMs' correction terms
-    ("panel512", "f16-f8-w+attn-f16"): ["drop left lo: attn_out", "drop left lo: mlp_out", "drop left lo: wi", "drop left lo: wqkv",
-                                        "drop right lo: attn_out", "drop right lo: mlp_out", "drop right lo: wi", "drop right lo: wqkv",
-                                        "lo shift off by one: attn_out", "lo shift off by one: mlp_out", "lo shift off by one: wi",
-                                        "lo shift off by one: wqkv"],
-    ("panel512", "f16-f8+attn-f16"): ["drop left lo: attn_out", "drop left lo: mlp_out", "drop left lo: wi", "lo shift off by one: attn_out",
-                                      "lo shift off by one: mlp_out", "lo shift off by one: wi", "lo shift off by one: wqkv"],
+# Mutations the GPU test's bounds cannot see on its O(1) inputs, plain or MLP-isolating (attn.Wo x 2^-8), per (model, set).
+_ROW_PAIR = "the whole-layer kernel carries h as an fp16 (hi, lo) pair: a bf16 pair is as exact"
+_ATTN_SIDE = ("q, k, v^T and p are rounded to single-plane fp16 right behind the q / k / v projection and right in front of the "
+              "output projection, at the same 2^-12 relative size as the terms dropped")
+_UNDETECTED: dict[tuple[str, str], tuple[str, list[str]]] = {
+    ("row", "f16-f8"): (_ROW_PAIR, ["bf16 for fp16: mlp_out"]),
+    ("row", "f16-f8-w"): (_ROW_PAIR, ["bf16 for fp16: mlp_out"]),
+    ("panel512", "f16-f8-w+attn-f16"): (_ATTN_SIDE, ["drop left lo: attn_out", "drop left lo: wqkv", "drop right lo: attn_out",
+                                                     "drop right lo: wqkv", "lo shift off by one: attn_out", "lo shift off by one: wqkv"]),
+    ("panel512", "f16-f8+attn-f16"): (_ATTN_SIDE, ["drop left lo: attn_out", "lo shift off by one: attn_out", "lo shift off by one: wqkv"]),
+    # the added shapes: a subset of the same names, for the same reasons
+    # ("drop right lo: wqkv" is seen there, thinly: 1.04 x on the plain recipe)
+    ("engte", "f16-f8-w+attn-f16"): (_ATTN_SIDE, ["drop left lo: attn_out", "drop left lo: wqkv", "drop right lo: attn_out",
+                                                  "lo shift off by one: attn_out", "lo shift off by one: wqkv"]),
+    ("row128", "f16-f8-w"): (_ROW_PAIR, ["bf16 for fp16: mlp_out"]),
+    ("row320", "f16-f8-w"): (_ROW_PAIR, ["bf16 for fp16: mlp_out"]),
 }
-UNDETECTED = {(m, s, name) for (m, s), names in _UNDETECTED.items() for name in names}
+UNDETECTED = {(m, s, name) for (m, s), (_, names) in _UNDETECTED.items() for name in names}
 
 
 def _mutations(arith: am.Arith):
@@ -185,27 +197,108 @@ def _mutations(arith: am.Arith):
             out[f"bf16 for fp16: {fam}"] = arith.with_family(fam, Scheme(s.name + "b", torch.bfloat16, *pairs))
         if "e4m3" in (s.left_lo, s.right_lo):
             out[f"lo shift off by one: {fam}"] = arith.with_family(fam, Scheme(s.name + "s", s.hi, s.left_lo, s.right_lo, am.LO_SHIFT - 1))
-    out["window one key short"] = am.Arith(arith.schemes, arith.layer0_wqkv, window_delta=-1)
+    out["window one key short"] = dataclasses.replace(arith, window_delta=-1)
     return out
 
 
-@pytest.mark.parametrize("model,kernel_set", SENS_CASES)
+def test_the_undetected_list_is_the_named_eleven():
+    """On the GPU test's default models at most the 11 named mutations stay listed; the added shapes list a subset of the
+    same names."""
+
+    default = {u for u in UNDETECTED if u[0] in ("row", "panel512")}
+    assert len(default) <= 11, sorted(default)
+    names = {(s, n) for _, s, n in default}
+    assert all((s, n) in names for m, s, n in UNDETECTED), sorted(UNDETECTED - default)
+
+
+@pytest.mark.parametrize("model,kernel_set", SENS_CASES + SHAPE_SENS_CASES)
 def test_mutations_exceed_the_bound(model, kernel_set):
+    """Each mutation under the plain O(1) recipe and, for the sets the GPU test runs on it, under the MLP-isolating one: a
+    mutation is detected when either recipe's bound sees it."""
+
     import test_kernel_set_conformance as conf
 
     torch.set_num_threads(16)
-    weights = conf.weights_for(kernel_set, "o1")
-    state, dims, rows = conf._state(model, weights), conf._dims(model), conf._rows(conf.LENGTHS)
-    exact = am.model_entries(am.forward(state, dims, rows, "exact"))
+    dims, rows = conf._dims(model), conf._rows(conf.LENGTHS)
     arith = am.arith_for(kernel_set, conf.PATH_OF[model])
-    own = am.model_entries(am.forward(state, dims, rows, arith))
-    bnd = am.bounds(own, exact)
-    missed = set()
-    for name, mutant in _mutations(arith).items():
-        per = am.ratios(am.model_entries(am.forward(state, dims, rows, mutant)), own, bnd)
-        where = max(per, key=lambda n: per[n][0])
-        print(f"[sensitivity] {model:9s} {kernel_set:24s} {weights:8s} {name:32s} x{per[where][0]:8.2f} of the bound at {where}")
-        if am.first_over(per) is None:
-            missed.add((model, kernel_set, name))
+    mutants = _mutations(arith)
+    best = {name: 0.0 for name in mutants}
+    # the damped recipe only where the conformance test runs it (the panel models, DAMPED_SETS) -- except that the row
+    # sets 3 / 4 take it too: cheap, and it shows the recipe does not rescue their bf16-pair mutation
+    damped = kernel_set in conf.DAMPED_SETS and (model in conf.DAMPED_MODELS or conf.PATH_OF[model] == "row")
+    for weights in [conf.weights_for(kernel_set, "o1")] + ([conf.weights_for(kernel_set, "o1", damped=True)] if damped else []):
+        state = conf._state(model, weights)
+        exact = am.model_entries(am.forward(state, dims, rows, "exact"))
+        own = am.model_entries(am.forward(state, dims, rows, arith))
+        bnd = am.bounds(own, exact)
+        for name, mutant in mutants.items():
+            per = am.ratios(am.model_entries(am.forward(state, dims, rows, mutant)), own, bnd)
+            where = max(per, key=lambda n: per[n][0])
+            r = per[where][0]
+            note = "" if not r > 1.0 else (" (thin)" if r < THIN else "")
+            print(f"[sensitivity] {model:9s} {kernel_set:24s} {weights:14s} {name:32s} x{r:8.2f} of the bound at {where}{note}")
+            best[name] = max(best[name], r)
+    missed = {(model, kernel_set, name) for name, r in best.items() if not r > 1.0}
+    for name, r in best.items():
+        if 1.0 < r < THIN:
+            print(f"[sensitivity] {model:9s} {kernel_set:24s} thin: {name} is detected at x{r:.2f} only")
     expected = {m for m in UNDETECTED if m[:2] == (model, kernel_set)}
     assert missed == expected, f"undetected {sorted(missed)}, listed {sorted(expected)}"
+
+
+# 4. the layer mask of kernel sets 8 / 9 ------------------------------------------------------------------------------------------
+def test_layer_mask_selects_the_f16_scheme_outside_it():
+    a = am.arith_for("f16+mlp-f16-f8-w", "panel", mlp_layers=[0, 2])
+    for li in range(4):
+        for fam in am.FAMILIES:
+            want = "f16+2f8" if fam in am.MLP_FAMILIES and li in (0, 2) else "f16"
+            assert a.scheme(fam, li).name == want, (fam, li)
+    assert am.arith_for("f16+mlp-f16-f8", "panel").mlp_layers is None
+    with pytest.raises(ValueError):
+        am.arith_for("f16", "panel", mlp_layers=[0])
+
+
+def test_empty_and_full_masks_are_the_f16_and_whole_depth_models():
+    import test_kernel_set_masks as masks
+
+    torch.set_num_threads(16)
+    dims = _dims(H=256, I=512, nh=4, nl=3)
+    from open_provence_amd.synthetic import synth_state_dict
+
+    state = am.mlp_isolating_state_dict(synth_state_dict(dims, 3))
+    rows = _rows([1, 33, 130])
+    run = lambda a: am.model_entries(am.forward(state, dims, rows, a, path="panel"))  # noqa: E731
+    none, f16 = run(am.arith_for("f16+mlp-f16-f8-w", "panel", [])), run(am.arith_for("f16", "panel"))
+    full, whole = run(am.arith_for("f16+mlp-f16-f8-w", "panel", range(3))), run(am.arith_for("f16+mlp-f16-f8-w", "panel"))
+    for n in none:
+        assert torch.equal(none[n], f16[n]) and torch.equal(full[n], whole[n]), n
+    assert masks.neighbours(0b0101, 4) == [0b0100, 0b0111, 0b0001, 0b1101, 0b1010, 0b0010, 0b1111, 0b0000]
+
+
+@pytest.mark.parametrize("kernel_set", ["f16+mlp-f16-f8-w", "f16+mlp-f16-f8"])
+def test_neighbouring_masks_are_separated_at_the_first_differing_layer(kernel_set):
+    """For the masks the GPU test pins (tests/test_kernel_set_masks.py), on its model, rows and damped weights: the model of
+    every neighbouring mask (one bit flipped, shifted by one layer, bit order reversed, all, none) equals the pinned
+    mask's up to the first layer where the masks differ, and leaves it at the entry behind that layer by more than 100 x
+    the comparison's floor.  rms(model A - model B) there is printed next to rms(model A - exact): the yardstick for the GPU
+    test's "closer to its own mask's model" clause, which holds for any kernel within half of the first figure."""
+
+    import test_kernel_set_conformance as conf
+    import test_kernel_set_masks as masks
+
+    n_layers = conf.SHAPES[masks.MODEL][3]
+    weights = conf.weights_for(kernel_set, "o1", damped=True)
+    lengths = tuple(conf.LENGTHS)
+    exact = conf._model(masks.MODEL, weights, 128, lengths, "exact")
+    for mask in masks.MODEL_MASKS[kernel_set]:
+        own = conf._model(masks.MODEL, weights, 128, lengths, kernel_set, masks.layers_of(mask, n_layers))
+        for other in masks.neighbours(mask, n_layers):
+            theirs = conf._model(masks.MODEL, weights, 128, lengths, kernel_set, masks.layers_of(other, n_layers))
+            first = masks.first_differing_layer(mask, other)
+            for li in range(first + 1):
+                assert torch.equal(own[f"hidden_{li}"], theirs[f"hidden_{li}"]), (mask, other, li)
+            entry = f"hidden_{first + 1}"
+            apart, err = am.rms(own[entry] - theirs[entry]), am.rms(own[entry] - exact[entry])
+            print(f"[mask sensitivity] {kernel_set:18s} mask {mask:04b} vs {other:04b}: first differing layer {first}, at {entry} "
+                  f"rms(A - B) {apart:.3e}, rms(A - exact) {err:.3e}, ratio {apart / err:.2f}")
+            assert apart > 100 * am.FLOOR * am.rms(exact[entry]), (mask, other, apart)

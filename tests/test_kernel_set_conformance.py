@@ -10,7 +10,11 @@ set whose kernels it replaces in some families: one that silently ran its base s
 
 Weights: O(1) (``synth_state_dict``) and peaked (its q rows scaled up: the late-rescale branch of the attention runs).  The
 sets without a lo(W) term (am.BF16_WEIGHT_SETS) exist for bf16-valued checkpoints and run on bf16-valued versions of both:
-on fp32-valued weights their rounding of W would dominate their error and hide every other departure.
+on fp32-valued weights their rounding of W would dominate their error and hide every other departure.  The sets that carry
+a correction term in the MLP behind an fp16 weight plane (3, 4, 8 - 11) run a second time on the MLP-isolating recipe
+(``am.mlp_isolating_state_dict``: every attn.Wo x 2^-8): on the plain weights the single-pass fp16 attention side of sets
+8 - 11 hides a dropped or mis-scaled correction term of their MLP, which is all those sets add to "f16".  Both recipes stay:
+the attention-side mutations are only visible on the plain one.  The layer mask of sets 8 / 9: tests/test_kernel_set_masks.py.
 
 The CPU side (one model forward per (model, weights, window, rows, set)) is computed once per module.  The table of results
 is printed when the module ends, one line per comparison in the order they ran."""
@@ -40,8 +44,15 @@ MODELS = {
     "panel512": (512, 2048, 8, 3),
     "panel768": (768, 3072, 12, 2),
     "tiled": (384, 192, 6, 2),
+    "engte": (768, 1152, 12, 2),  # the published en-gte shape: nine 128-wide Wi tiles, 36 k-steps of the MLP output projection
+    "h1024": (1024, 512, 16, 2),  # four 256-wide tiles, 16 heads: the largest hidden op_create takes
+    "row128": (128, 512, 2, 3),  # the other row shape with fp16 / e4m3 packs; no wave-pair kernel
+    "row320": (256, 320, 4, 3),  # intermediate not 4 x hidden: 5 x 64, an odd count in the wave-pair kernel's MLP loop
 }
-PATH_OF = {"row": "row", "panel512": "panel", "panel768": "panel", "tiled": "tiled"}
+# ... and the 4-layer panel model of tests/test_kernel_set_masks.py (the layer mask of sets 8 / 9)
+SHAPES = {**MODELS, "panel512x4": (512, 2048, 8, 4)}
+PATH_OF = {"row": "row", "panel512": "panel", "panel768": "panel", "tiled": "tiled", "engte": "panel", "h1024": "panel",
+           "row128": "row", "row320": "row", "panel512x4": "panel"}
 
 # What each path supports, as an explicit expectation (op_api.hip set_available): every other set must be refused.
 ROW_SETS = ["bf16x3", "bf16-weights", "bf16", "f16-f8", "f16-f8-w", "f16"]
@@ -50,7 +61,15 @@ SUPPORTED = {
     "panel512": ALL_SETS,
     "panel768": ALL_SETS,
     "tiled": ["bf16x3"],
+    "engte": ALL_SETS,
+    "h1024": ALL_SETS,
+    "row128": ROW_SETS,
+    "row320": ROW_SETS,
 }
+# the MLP-isolating recipe (am.mlp_isolating_state_dict) runs on the sets whose weight hi plane is fp16 and that carry a
+# correction term in the MLP: 8 - 11, and 3 / 4, whose fp16 + e4m3 MLP launches sets 8 - 11 reuse (launch_panel_f8)
+DAMPED_SETS = ["f16-f8", "f16-f8-w", "f16+mlp-f16-f8-w", "f16+mlp-f16-f8", "f16-f8-w+attn-f16", "f16-f8+attn-f16"]
+DAMPED_MODELS = ["panel512", "panel768", "engte", "h1024"]
 # flag -> sets it leaves available on the row / panel path (the test hooks' header comments in open_provence_hip.h)
 SUPPORTED_WITH_FLAG = {
     ("row", "NO_SMALL_BLOCKS"): ROW_SETS,
@@ -100,7 +119,7 @@ TABLE: list[str] = []
 @pytest.fixture(scope="module", autouse=True)
 def _print_table():
     yield
-    print("\n[conformance] model     set                      flags              weights      window rows  | worst ratio to the bound: "
+    print("\n[conformance] model     set                      flags              weights        window rows  | worst ratio to the bound: "
           "over the entries that check a rounding scheme (hidden_0: the fp32 floor) | the kernel against exact")
     for line in TABLE:
         print("[conformance]", line)
@@ -109,7 +128,7 @@ def _print_table():
 def _dims(model: str, window: int = 128):
     from open_provence_amd.config import EncoderDims
 
-    H, I, nh, nl = MODELS[model]
+    H, I, nh, nl = SHAPES[model]
     return EncoderDims.from_base_model_config(
         dict(model_type="modernbert", vocab_size=512, hidden_size=H, intermediate_size=I, num_hidden_layers=nl,
              num_attention_heads=nh, local_attention=window, global_attn_every_n_layers=nl, global_rope_theta=160000.0,
@@ -122,10 +141,11 @@ def _rows(lengths, seed=7):
     return [([1] + rng.integers(3, 512, n - 1).tolist()) if n else [] for n in lengths]
 
 
-def weights_for(kernel_set: str, recipe: str) -> str:
-    """The weights a set is checked on: ``recipe`` ("o1" / "peaked"), bf16-valued for the sets without a lo(W) term."""
+def weights_for(kernel_set: str, recipe: str, damped: bool = False) -> str:
+    """The weights a set is checked on: ``recipe`` ("o1" / "peaked"), bf16-valued for the sets without a lo(W) term;
+    ``damped``: then the MLP-isolating recipe on top (every attn.Wo x 2^-8, on fp16's grid)."""
 
-    return f"{recipe}-bf16" if kernel_set in am.BF16_WEIGHT_SETS else recipe
+    return recipe + ("-bf16" if kernel_set in am.BF16_WEIGHT_SETS else "") + ("-damped" if damped else "")
 
 
 @functools.lru_cache(maxsize=None)
@@ -133,17 +153,22 @@ def _state(model: str, weights: str, window: int = 128):
     from open_provence_amd.synthetic import synth_state_dict
 
     dims = _dims(model, window)
-    recipe, _, bf16 = weights.partition("-")
+    recipe, *marks = weights.split("-")
+    assert recipe in ("o1", "peaked") and set(marks) <= {"bf16", "damped"}, weights
     state = synth_state_dict(dims, 21) if recipe == "o1" else am.peaked_state_dict(dims, 21)
-    return am.bf16_valued(state) if bf16 else state
+    if "bf16" in marks:
+        state = am.bf16_valued(state)
+    return am.mlp_isolating_state_dict(state) if "damped" in marks else state
 
 
 @functools.lru_cache(maxsize=None)
-def _model(model: str, weights: str, window: int, lengths: tuple, kernel_set: str):
-    """Entries of the model of `kernel_set` ("exact" included) on the rows of `lengths` -- once per module."""
+def _model(model: str, weights: str, window: int, lengths: tuple, kernel_set: str, mlp_layers: "tuple | None" = None):
+    """Entries of the model of `kernel_set` ("exact" included; `mlp_layers`: the layer mask of sets 8 / 9) on the rows of
+    `lengths` -- once per module."""
 
     torch.set_num_threads(16)
-    out = am.forward(_state(model, weights, window), _dims(model, window), _rows(lengths), kernel_set, path=PATH_OF[model])
+    arith = am.arith_for(kernel_set, PATH_OF[model], mlp_layers)
+    out = am.forward(_state(model, weights, window), _dims(model, window), _rows(lengths), arith, path=PATH_OF[model])
     return am.model_entries(out)
 
 
@@ -218,8 +243,8 @@ def _compare(label: str, got, own, exact, deepest: str, base=None):
         assert not worse, f"{label}: as close to the base set's model as to its own at {worse}: {[closer[n] for n in worse]}"
 
 
-def _check(model, kernel_set, flag_names, recipe, window, lengths=tuple(LENGTHS)):
-    weights = weights_for(kernel_set, recipe)
+def _check(model, kernel_set, flag_names, recipe, window, lengths=tuple(LENGTHS), damped=False):
+    weights = weights_for(kernel_set, recipe, damped)
     rows = _rows(lengths)
     own = _model(model, weights, window, lengths, kernel_set)
     exact = _model(model, weights, window, lengths, "exact")
@@ -232,9 +257,9 @@ def _check(model, kernel_set, flag_names, recipe, window, lengths=tuple(LENGTHS)
     finally:
         enc.close()
     rows_label = "L2048" if max(lengths) == 2048 else "list"
-    label = f"{model:9s} {kernel_set:24s} {'+'.join(flag_names) or '-':18s} {weights:12s} w{window:<5d} {rows_label:5s}"
+    label = f"{model:9s} {kernel_set:24s} {'+'.join(flag_names) or '-':18s} {weights:14s} w{window:<5d} {rows_label:5s}"
     assert after == kernel_set, f"{label}: the forward ran on {after}"
-    _compare(label, got, own, exact, f"hidden_{MODELS[model][3]}", base)
+    _compare(label, got, own, exact, f"hidden_{SHAPES[model][3]}", base)
 
 
 # -- which sets each path has -------------------------------------------------------------------------------------------------
@@ -265,6 +290,35 @@ DEFAULT_CASES = [(m, s, w) for m in MODELS for s in SUPPORTED[m] for w in (("o1"
 @pytest.mark.parametrize("model,kernel_set,recipe", DEFAULT_CASES)
 def test_kernel_set_matches_its_model(model, kernel_set, recipe):
     _check(model, kernel_set, [], recipe, 128)
+
+
+# -- the MLP-isolating recipe: the correction terms of the MLP of sets 8 - 11 (and of 3 / 4, whose launches they reuse) -------
+@pytest.mark.parametrize("model", DAMPED_MODELS)
+@pytest.mark.parametrize("weights", ["o1-damped", "o1-bf16-damped"])
+def test_damped_weights_keep_every_expected_set(model, weights):
+    """The damped output projection sits on fp16's grid, so no set with an fp16 weight plane is refused for it
+    (f16_unfit in op_api.hip): every set the model supports still pins."""
+
+    from open_provence_amd.engine import HipEncoder
+
+    enc = HipEncoder(_dims(model), device="cuda:0", flags=0)
+    try:
+        enc.load_state_dict(_state(model, weights), calibrate=False)
+        for name in SUPPORTED[model]:
+            enc.select_kernel_set(name)
+            assert enc.effective_policy()["kernel_set"] == name
+    finally:
+        enc.close()
+
+
+@pytest.mark.parametrize("model", DAMPED_MODELS)
+@pytest.mark.parametrize("kernel_set", DAMPED_SETS)
+def test_kernel_set_matches_its_model_on_mlp_isolating_weights(model, kernel_set):
+    """With every attn.Wo x 2^-8 the attention side's error shrinks 256-fold and the MLP's arithmetic dominates each entry:
+    a dropped lo term or a mis-scaled e4m3 plane in the Wi GEMM or the MLP output projection of sets 8 - 11 is 5 - 18 x
+    the bound here (tests/test_arith_model.py), and under it on the plain weights."""
+
+    _check(model, kernel_set, [], "o1", 128, damped=True)
 
 
 @pytest.mark.parametrize("model,kernel_set", [("row", "bf16x3"), ("row", "f16"), ("row", "f16-f8-w")])
@@ -315,4 +369,4 @@ def test_large_row_batch_sample():
     exact = am.model_entries(am.forward(_state("row", "o1"), dims, srows, "exact", path="row"))
     idx = torch.cat([torch.arange(i * length, (i + 1) * length) for i in sample])
     got = {k: (v[idx] if k != "rank" else v[sample]) for k, v in got_all.items()}
-    _compare(f"{'row':9s} {'f16':24s} {'-':18s} {'o1':12s} w128   300x128 (16 rows compared)", got, own, exact, "hidden_3")
+    _compare(f"{'row':9s} {'f16':24s} {'-':18s} {'o1':14s} w128   300x128 (16 rows compared)", got, own, exact, "hidden_3")
