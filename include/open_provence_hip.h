@@ -300,6 +300,55 @@ int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t
                              float* prune_logits_dev, float* rank_logits_dev, float* keep_prob_dev,
                              void* workspace_dev, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req);
 
+/* The padded boundary on the device.  Replaces: the reference forward taking `input_ids[B, L]` + `attention_mask[B, L]` as
+ * they come from the tokenizer (standalone.py:1666-1690) and returning `pruning_logits[B, L, 2]` (standalone.py:1695-1739);
+ * additive to ABI 10 (op_abi_version() is unchanged: detect the two calls by symbol).
+ *
+ * op_pack_padded: padded device tensors -> the inputs of op_forward_packed, without the batch visiting the host.
+ *   ids_dev   [n_rows][width] int32 or int64 (ids_dtype: OP_INT_I32 / OP_INT_I64), contiguous
+ *   mask_dev  [n_rows][width] uint8 (= bool), int32 or int64 (mask_dtype), contiguous; != 0 means "token".  NULL: every row
+ *             is full (mask_dtype is ignored)
+ *   ids_packed_dev  room for n_rows * width int32; receives ids[r][j] of the j < len[r] positions, rows end to end
+ *   cu_seqlens_dev / cu_seqlens_host  [n_rows + 1] prefix offsets of the row lengths, on the device and on the host
+ *   report    struct_bytes set by the caller; the call fills the rest (total_tokens and max_seqlen are what
+ *             op_workspace_bytes / op_forward_packed ask for)
+ * Two checks run on the device, because a batch that never visits the host cannot be checked there:
+ *   status bit 0  a row's mask is not ones-then-zeros (left padding, a hole): the packed path derives positions from token
+ *                 order.  (mask_row, mask_col) = the first zero entry, in row-major order, that has a non-zero entry behind
+ *                 it in its row;
+ *   status bit 1  an id outside 0 <= id < vocab_size at a position whose mask is non-zero (ids under padding are not
+ *                 looked at).  (id_row, id_col, id_value) = the first one in row-major order.  op_forward_packed itself
+ *                 only clamps such an id (a memory-safety net): this is the call that refuses it, as nn.Embedding does.
+ * Returns OP_OK when status == 0; otherwise OP_ERR_INVALID with the report filled and an op_last_error text that names
+ * row, column and id (cu_seqlens and ids_packed then hold the counts of non-zero entries: not a batch to run).
+ * The call enqueues its kernels on hip_stream, copies cu_seqlens and the report to the host and SYNCHRONISES THAT STREAM
+ * ONCE: the forward's grids and workspace need total_tokens and max_seqlen on the host (op_forward_packed reads cu_seqlens
+ * back the same way when it is given no host copy).  A stream that is being captured is therefore refused (OP_ERR_STATE).
+ * The small device status block and its pinned staging belong to the handle: like every call on a handle, serialised by
+ * the caller.  Refused with OP_ERR_INVALID before anything is enqueued (and before the handle is looked at): a NULL report,
+ * a wrong struct_bytes, an unknown ids_dtype / mask_dtype, a negative n_rows / width, n_rows * width >= 2^31, a NULL
+ * buffer.  n_rows == 0 or width == 0 launches nothing (cu_seqlens = 0).  Rows longer than max_position_embeddings are
+ * op_forward_packed's business.
+ *
+ * op_unpack_padded: packed_dev [total_tokens][channels] fp32 (channels = 2: prune_logits_dev, 1: keep_prob_dev) ->
+ * padded_dev [n_rows][width][channels]: EVERY element is written, the value at positions below the row's length and +0.0
+ * beyond it (the caller zeroes nothing).  Asynchronous on hip_stream.  width is not checked against the lengths: positions
+ * at or beyond width are simply not produced. */
+enum op_int_dtype { OP_INT_I32 = 0, OP_INT_I64 = 1, OP_INT_U8 = 2 };
+typedef struct op_padded_report {
+  uint32_t struct_bytes; /* sizeof(op_padded_report) */
+  int32_t total_tokens, max_seqlen;
+  int32_t status;             /* bit 0: mask not ones-then-zeros; bit 1: id outside the embedding table */
+  int32_t mask_row, mask_col; /* first offender of bit 0 (row-major); -1 when clear */
+  int32_t id_row, id_col;     /* first offender of bit 1 (row-major); -1 when clear */
+  int64_t id_value;
+} op_padded_report;
+int op_pack_padded(op_handle* h, const void* ids_dev, int ids_dtype, const void* mask_dev, int mask_dtype, int n_rows, int width,
+                   int32_t* ids_packed_dev, int32_t* cu_seqlens_dev, int32_t* cu_seqlens_host, op_padded_report* report,
+                   void* hip_stream);
+int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_seqlens_dev, int n_rows, int width, int channels,
+                     float* padded_dev, void* hip_stream);
+
 /* Replaces: the per-fragment `float(block_probs[start:end].mean())` of the reference's post-processing
  * (standalone.py:3075-3082), evaluated on the device on the keep-probabilities a forward left there:
  *   seg_dev [n_seg, 2] int32  token ranges [start, end) into keep_prob_dev (clamped to [0, n_values))

@@ -60,6 +60,8 @@ EXPORTED_SYMBOLS = (
     "op_workspace_bytes",
     "op_forward_packed",
     "op_forward_packed_hidden",
+    "op_pack_padded",
+    "op_unpack_padded",
     "op_segment_means",
     "op_debug_capture_hidden",
     "op_profile_enable",
@@ -135,6 +137,26 @@ class OpHiddenRequest(ctypes.Structure):
 
 OP_HIDDEN_F32, OP_HIDDEN_BF16 = 0, 1
 
+
+class OpPaddedReport(ctypes.Structure):
+    """``op_padded_report``: what ``op_pack_padded`` found in one padded batch."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("total_tokens", ctypes.c_int32),
+        ("max_seqlen", ctypes.c_int32),
+        ("status", ctypes.c_int32),
+        ("mask_row", ctypes.c_int32),
+        ("mask_col", ctypes.c_int32),
+        ("id_row", ctypes.c_int32),
+        ("id_col", ctypes.c_int32),
+        ("id_value", ctypes.c_int64),
+    ]
+
+
+OP_INT_I32, OP_INT_I64, OP_INT_U8 = 0, 1, 2
+OP_PADDED_BAD_MASK, OP_PADDED_BAD_ID = 1, 2  # op_padded_report.status bits
+
 OP_CAL_FULL_REPORT = 1
 OP_CAL_WHOLE_DEPTH = 2
 
@@ -201,6 +223,11 @@ def load_library() -> ctypes.CDLL:
             lib.op_select_mlp_correction_layers.argtypes = [vp, ctypes.c_uint64]
         lib.op_calibrate.restype = ci
         lib.op_calibrate.argtypes = [vp, ctypes.c_float, vp, vp, ci, ctypes.POINTER(OpCalibration)]
+    if hasattr(lib, "op_pack_padded"):  # (additive to ABI 10: an older library loaded for an A/B has neither)
+        lib.op_pack_padded.restype = ci
+        lib.op_pack_padded.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, ctypes.POINTER(OpPaddedReport), vp]
+        lib.op_unpack_padded.restype = ci
+        lib.op_unpack_padded.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
     lib.op_segment_means.restype = ci
     lib.op_segment_means.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     lib.op_debug_capture_hidden.restype = ci

@@ -27,9 +27,11 @@ _ROWGEMM = [CSRC / name for name in ("opk_rowgemm.hip.h", "opk_rowgemm_pack.hip.
                                      "opk_rowgemm_qkv_pairs.hip.h", "opk_rowgemm_chunks.hip.h")]
 _INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_attn.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
 
+_PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
+
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
-    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", INCLUDE]),
+    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, INCLUDE]),
     ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"], _INTERNAL),
     ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"], _INTERNAL),
     ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"], _INTERNAL),
@@ -40,6 +42,7 @@ UNITS = [
     ("op_launch_layer32", CSRC / "op_launch_layer32.hip", [], _INTERNAL),
     ("op_launch_attn", CSRC / "op_launch_attn.hip", [], _INTERNAL),
     ("op_launch_panel", CSRC / "op_launch_panel.hip", [], _INTERNAL),
+    ("op_launch_padded", CSRC / "op_launch_padded.hip", [], _INTERNAL + [_PADDED]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = sorted({h for u in UNITS for h in u[3]})

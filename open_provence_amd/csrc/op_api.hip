@@ -17,6 +17,7 @@
 #define OPK_PACK_KERNELS 1
 #include "op_internal.h"
 #include "opk_small.hip.h"
+#include "opk_padded.hip.h"
 #include "opk_tiled.hip.h"
 
 using namespace opk;
@@ -136,6 +137,9 @@ struct op_handle {
   std::vector<ProfileEvent> events;
   double prof_ms[PK_COUNT] = {0};
   int prof_launches[PK_COUNT] = {0};
+  uint32_t* pad_status = nullptr;    // op_pack_padded: the device status block (opk::PAD_ST_WORDS words), allocated on first use
+  int32_t* pad_host = nullptr;       // ... and its pinned host staging: cu_seqlens[n_rows + 1] + the status block
+  size_t pad_host_words = 0;
   std::string err;
 };
 
@@ -1238,6 +1242,7 @@ void op_destroy(op_handle* h) {
     (void)hipEventDestroy(ev.stop);
   }
   for (void* p : h->allocations) (void)hipFree(p);
+  if (h->pad_host) (void)hipHostFree(h->pad_host);
   delete h;
 }
 
@@ -2144,6 +2149,110 @@ int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t
     return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: out_dev is NULL with %d entries selected", n_sel);
   return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
                              workspace, workspace_bytes, hip_stream, n_sel > 0 ? &hid : nullptr);
+}
+
+int op_pack_padded(op_handle* h, const void* ids_dev, int ids_dtype, const void* mask_dev, int mask_dtype, int n_rows, int width,
+                   int32_t* ids_packed_dev, int32_t* cu_seqlens_dev, int32_t* cu_seqlens_host, op_padded_report* report,
+                   void* hip_stream) {
+  // (the arguments' own fields first: none of them needs the handle)
+  if (!report) return fail(h, OP_ERR_INVALID, "op_pack_padded: report is NULL");
+  if (report->struct_bytes != sizeof(op_padded_report))
+    return fail(h, OP_ERR_INVALID, "op_pack_padded: op_padded_report.struct_bytes is %u, expected %zu", report->struct_bytes,
+                sizeof(op_padded_report));
+  if (ids_dtype != OP_INT_I32 && ids_dtype != OP_INT_I64)
+    return fail(h, OP_ERR_INVALID, "op_pack_padded: ids_dtype %d is neither OP_INT_I32 nor OP_INT_I64", ids_dtype);
+  if (mask_dev && mask_dtype != OP_INT_I32 && mask_dtype != OP_INT_I64 && mask_dtype != OP_INT_U8)
+    return fail(h, OP_ERR_INVALID, "op_pack_padded: unknown mask_dtype %d", mask_dtype);
+  if (n_rows < 0) return fail(h, OP_ERR_INVALID, "op_pack_padded: negative n_rows %d", n_rows);
+  if (width < 0) return fail(h, OP_ERR_INVALID, "op_pack_padded: negative width %d", width);
+  const int64_t cells = (int64_t)n_rows * (int64_t)width;
+  if (cells > (int64_t)INT32_MAX)  // (the first offender of each check is a 32-bit linear index)
+    return fail(h, OP_ERR_INVALID, "op_pack_padded: n_rows * width = %lld exceeds 2^31 - 1", (long long)cells);
+  if (!cu_seqlens_dev) return fail(h, OP_ERR_INVALID, "op_pack_padded: cu_seqlens_dev is NULL");
+  if (!cu_seqlens_host) return fail(h, OP_ERR_INVALID, "op_pack_padded: cu_seqlens_host is NULL");
+  if (cells > 0 && !ids_dev) return fail(h, OP_ERR_INVALID, "op_pack_padded: ids_dev is NULL");
+  if (cells > 0 && !ids_packed_dev) return fail(h, OP_ERR_INVALID, "op_pack_padded: ids_packed_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_pack_padded: NULL handle");
+  report->total_tokens = report->max_seqlen = report->status = 0;
+  report->mask_row = report->mask_col = report->id_row = report->id_col = -1;
+  report->id_value = 0;
+
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  OP_HIP(h, hipStreamIsCapturing(stream, &capturing));
+  if (capturing != hipStreamCaptureStatusNone)
+    return fail(h, OP_ERR_STATE, "op_pack_padded: the stream is being captured (the call synchronises it to read the batch's size back)");
+  if (cells == 0) {  // nothing to launch: every row is empty
+    OP_HIP(h, hipMemsetAsync(cu_seqlens_dev, 0, ((size_t)n_rows + 1) * sizeof(int32_t), stream));
+    std::fill(cu_seqlens_host, cu_seqlens_host + n_rows + 1, 0);
+    return OP_OK;
+  }
+  if (!h->pad_status) OP_TRY(dev_alloc(h, &h->pad_status, (size_t)opk::PAD_ST_WORDS));
+  const size_t n_cu = (size_t)n_rows + 1, words = n_cu + opk::PAD_ST_WORDS;
+  if (h->pad_host_words < words) {
+    if (h->pad_host) (void)hipHostFree(h->pad_host);
+    h->pad_host = nullptr;
+    h->pad_host_words = 0;
+    void* p = nullptr;
+    const size_t grown = std::max<size_t>(words, 4096);
+    hipError_t e = hipHostMalloc(&p, grown * sizeof(int32_t), hipHostMallocDefault);
+    if (e != hipSuccess) return fail(h, OP_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", grown * sizeof(int32_t), hipGetErrorString(e));
+    h->pad_host = reinterpret_cast<int32_t*>(p);
+    h->pad_host_words = grown;
+  }
+  OP_HIP(h, hipMemsetAsync(h->pad_status, 0xff, 2 * sizeof(uint32_t), stream));  // the two atomicMin words = PAD_ST_NONE
+  if (!opl::launch_padded_pack(stream, ids_dev, ids_dtype, mask_dev, mask_dtype, n_rows, width, h->V, ids_packed_dev, cu_seqlens_dev,
+                               h->pad_status))
+    return fail(h, OP_ERR_UNSUPPORTED, "op_pack_padded: no kernel for ids_dtype %d / mask_dtype %d", ids_dtype, mask_dtype);
+  OP_HIP(h, hipGetLastError());
+  uint32_t* st_host = reinterpret_cast<uint32_t*>(h->pad_host + n_cu);
+  OP_HIP(h, hipMemcpyAsync(h->pad_host, cu_seqlens_dev, n_cu * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+  OP_HIP(h, hipMemcpyAsync(st_host, h->pad_status, opk::PAD_ST_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  OP_HIP(h, hipStreamSynchronize(stream));  // the one synchronisation: the forward's grids need T and the longest row
+  std::memcpy(cu_seqlens_host, h->pad_host, n_cu * sizeof(int32_t));
+  report->total_tokens = (int32_t)st_host[opk::PAD_ST_TOTAL];
+  report->max_seqlen = (int32_t)st_host[opk::PAD_ST_MAXLEN];
+  const uint32_t bad_mask = st_host[opk::PAD_ST_MASK], bad_id = st_host[opk::PAD_ST_ID];
+  if (bad_mask != opk::PAD_ST_NONE) {
+    report->status |= 1;
+    report->mask_row = (int32_t)(bad_mask / (uint32_t)width);
+    report->mask_col = (int32_t)(bad_mask % (uint32_t)width);
+  }
+  if (bad_id != opk::PAD_ST_NONE) {
+    report->status |= 2;
+    report->id_row = (int32_t)(bad_id / (uint32_t)width);
+    report->id_col = (int32_t)(bad_id % (uint32_t)width);
+    report->id_value = (int64_t)((uint64_t)st_host[opk::PAD_ST_IDVAL] | ((uint64_t)st_host[opk::PAD_ST_IDVAL + 1] << 32));
+  }
+  if (report->status == 0) return OP_OK;
+  char mask_text[160] = "", id_text[200] = "";
+  if (report->status & 1)
+    snprintf(mask_text, sizeof(mask_text), "the attention mask is not ones-then-zeros at row %d, column %d", report->mask_row, report->mask_col);
+  if (report->status & 2)
+    snprintf(id_text, sizeof(id_text), "token id %lld at row %d, column %d is outside the embedding table (vocab_size %d)",
+             (long long)report->id_value, report->id_row, report->id_col, h->V);
+  return fail(h, OP_ERR_INVALID, "op_pack_padded: %s%s%s", mask_text, report->status == 3 ? "; " : "", id_text);
+}
+
+int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_seqlens_dev, int n_rows, int width, int channels,
+                     float* padded_dev, void* hip_stream) {
+  if (channels != 1 && channels != 2) return fail(h, OP_ERR_INVALID, "op_unpack_padded: channels is %d, expected 1 or 2", channels);
+  if (n_rows < 0) return fail(h, OP_ERR_INVALID, "op_unpack_padded: negative n_rows %d", n_rows);
+  if (width < 0) return fail(h, OP_ERR_INVALID, "op_unpack_padded: negative width %d", width);
+  const int64_t cells = (int64_t)n_rows * (int64_t)width;
+  if (cells > (int64_t)INT32_MAX)
+    return fail(h, OP_ERR_INVALID, "op_unpack_padded: n_rows * width = %lld exceeds 2^31 - 1", (long long)cells);
+  if (cells > 0 && !packed_dev) return fail(h, OP_ERR_INVALID, "op_unpack_padded: packed_dev is NULL");
+  if (cells > 0 && !cu_seqlens_dev) return fail(h, OP_ERR_INVALID, "op_unpack_padded: cu_seqlens_dev is NULL");
+  if (cells > 0 && !padded_dev) return fail(h, OP_ERR_INVALID, "op_unpack_padded: padded_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_unpack_padded: NULL handle");
+  if (cells == 0) return OP_OK;
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  if (!opl::launch_padded_scatter(reinterpret_cast<hipStream_t>(hip_stream), packed_dev, cu_seqlens_dev, n_rows, width, channels, padded_dev))
+    return fail(h, OP_ERR_UNSUPPORTED, "op_unpack_padded: no kernel for %d channels", channels);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
 }
 
 }  // extern "C"

@@ -94,4 +94,13 @@ bool launch_panel_f8(hipStream_t st, const opk::PanelParams& p, int epi, bool wl
 // o16 (kernel sets 10 / 11): q, k, v^T as single-plane fp16 for launch_attn(.., f16_in_f8_out = true)
 bool launch_panel_f8_qkv(hipStream_t st, const opk::PanelParams& p, bool wlo, bool o16, dim3 grid);
 
+// The padded [B, L] boundary (opk_padded.hip.h; op_pack_padded / op_unpack_padded).  Integer types as enum op_int_dtype.
+constexpr int PAD_INT_I32 = 0, PAD_INT_I64 = 1, PAD_INT_U8 = 2;
+// row lengths + validation, scan and gather of one padded batch: cu[n_rows + 1], ids_packed[<= n_rows * width] and the
+// status block (opk::PAD_ST_*; the caller presets its two atomicMin words to opk::PAD_ST_NONE).  mask == nullptr: full rows.
+bool launch_padded_pack(hipStream_t st, const void* ids, int ids_dtype, const void* mask, int mask_dtype, int n_rows, int width,
+                        int vocab, int32_t* ids_packed, int32_t* cu, uint32_t* status);
+// packed [T][channels] fp32 -> padded [n_rows][width][channels], every element written; channels 1 or 2
+bool launch_padded_scatter(hipStream_t st, const float* packed, const int32_t* cu, int n_rows, int width, int channels, float* padded);
+
 }  // namespace opl

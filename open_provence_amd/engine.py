@@ -782,6 +782,102 @@ class HipEncoder:
                 f"vocab_size is {self.dims.vocab_size}"
             )
 
+    # -- the padded boundary on the device (op_pack_padded / op_unpack_padded) -----------------------------------------
+    def pack_padded_device(self, input_ids: torch.Tensor, attention_mask: "torch.Tensor | None"
+                           ) -> "tuple[torch.Tensor, torch.Tensor, np.ndarray, int]":
+        """``packing.pack_padded`` + :meth:`check_ids` for a batch that is already on this device: ``input_ids[B, L]`` (+
+        right-padded ``attention_mask[B, L]`` or None) -> ``(ids[int32, T], cu_seqlens[int32, B+1], cu_seqlens_host, max_len)``,
+        the first two on the device -- the arguments of :meth:`forward_packed`.  Lengths, both checks, the scan and the gather
+        run in HIP kernels on the current stream, which is synchronised once (the forward needs T and ``max_len`` on the host).
+        Raises what the host path raises: ``NotImplementedError`` for a mask that is not ones-then-zeros (it wins when both
+        faults are present, as on the host), ``IndexError`` for an id outside the embedding table at an unmasked position."""
+
+        if input_ids.ndim != 2:
+            raise ValueError("input_ids must be [B, L]")
+        n_rows, width = int(input_ids.shape[0]), int(input_ids.shape[1])
+        if attention_mask is not None and tuple(attention_mask.shape) != (n_rows, width):
+            raise ValueError("attention_mask shape must match input_ids")
+        if input_ids.device != self.device or (attention_mask is not None and attention_mask.device != self.device):
+            raise ValueError(f"input_ids / attention_mask must live on {self.device}")
+        if n_rows * width >= 2**31:
+            raise ValueError("batch has more than 2^31 positions")
+        int_types = {torch.int32: _lib.OP_INT_I32, torch.int64: _lib.OP_INT_I64, torch.uint8: _lib.OP_INT_U8}
+        ids_in = input_ids.detach()
+        if ids_in.dtype not in (torch.int32, torch.int64):
+            if ids_in.dtype.is_floating_point or ids_in.dtype in (torch.bool, torch.complex64, torch.complex128):
+                raise TypeError(f"input_ids must be an integer tensor, got {ids_in.dtype}")
+            ids_in = ids_in.to(torch.int64)
+        ids_in = ids_in.contiguous()
+        mask_in = None
+        if attention_mask is not None:
+            mask_in = attention_mask.detach()
+            if mask_in.dtype == torch.bool:
+                mask_in = mask_in.contiguous().view(torch.uint8)
+            elif mask_in.dtype not in int_types:  # other integer and float masks: reduced to bool on the device
+                mask_in = mask_in.ne(0).view(torch.uint8)
+            mask_in = mask_in.contiguous()
+        packed = torch.empty(n_rows * width, dtype=torch.int32, device=self.device)
+        cu = torch.empty(n_rows + 1, dtype=torch.int32, device=self.device)
+        cu_host = np.zeros(n_rows + 1, dtype=np.int32)
+        report = _lib.OpPaddedReport()
+        report.struct_bytes = ctypes.sizeof(_lib.OpPaddedReport)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_pack_padded(
+                self._handle, ctypes.c_void_p(ids_in.data_ptr()) if ids_in.numel() else None, int_types[ids_in.dtype],
+                ctypes.c_void_p(mask_in.data_ptr()) if mask_in is not None and mask_in.numel() else None,
+                int_types[mask_in.dtype] if mask_in is not None else 0, n_rows, width,
+                ctypes.c_void_p(packed.data_ptr()) if packed.numel() else None, ctypes.c_void_p(cu.data_ptr()),
+                cu_host.ctypes.data_as(ctypes.c_void_p), ctypes.byref(report), ctypes.c_void_p(stream),
+            )
+        status = int(report.status)
+        if code == _lib.OP_ERR_INVALID and status & _lib.OP_PADDED_BAD_MASK:
+            raise NotImplementedError(
+                "attention_mask must be right-padded (ones then zeros): the packed HIP path derives positions "
+                "from token order, exactly what the reference's process() produces (standalone.py:2832-2880)."
+                f"  First offender: row {int(report.mask_row)}, column {int(report.mask_col)}."
+            )
+        if code == _lib.OP_ERR_INVALID and status & _lib.OP_PADDED_BAD_ID:
+            raise IndexError(
+                f"token id out of range for the embedding table: id {int(report.id_value)} at row {int(report.id_row)}, "
+                f"column {int(report.id_col)}; vocab_size is {self.dims.vocab_size}"
+            )
+        _lib.check(self.lib, self._handle, code, "op_pack_padded")
+        return packed[: int(report.total_tokens)], cu, cu_host, int(report.max_seqlen)
+
+    def unpack_padded_device(self, values: torch.Tensor, cu_seqlens: torch.Tensor, n_rows: int, width: int) -> torch.Tensor:
+        """``packing.unpack_to_padded`` in one kernel: packed fp32 ``values[T, 2]`` (pruning logits) or ``values[T]`` / ``[T, 1]``
+        (keep-probabilities) -> ``[n_rows, width, 2]`` / ``[n_rows, width]`` / ``[n_rows, width, 1]`` with +0.0 at the positions
+        beyond each row's length.  Every element of the result is written by the kernel (no memset, no index tensors).
+        Asynchronous on the current stream."""
+
+        if values.dtype != torch.float32 or cu_seqlens.dtype != torch.int32:
+            raise TypeError("values must be fp32 and cu_seqlens int32")
+        if values.device != self.device or cu_seqlens.device != self.device:
+            raise ValueError(f"values / cu_seqlens must live on {self.device}")
+        channels = 1 if values.ndim == 1 else int(values.shape[1]) if values.ndim == 2 else 0
+        if channels not in (1, 2):
+            raise ValueError("values must be [T], [T, 1] or [T, 2]")
+        n_rows, width = int(n_rows), int(width)
+        if n_rows < 0 or width < 0 or n_rows * width >= 2**31 or int(cu_seqlens.numel()) != n_rows + 1:
+            raise ValueError("n_rows / width do not describe cu_seqlens")
+        if not values.is_contiguous() or not cu_seqlens.is_contiguous():
+            raise ValueError("values and cu_seqlens must be contiguous")
+        shape = (n_rows, width) + tuple(values.shape[1:])
+        if values.shape[0] == 0:  # (nothing to read: an empty batch, or empty rows only)
+            return torch.zeros(shape, dtype=torch.float32, device=self.device)
+        out = torch.empty(shape, dtype=torch.float32, device=self.device)
+        if out.numel() == 0:
+            return out
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_unpack_padded(
+                self._handle, ctypes.c_void_p(values.data_ptr()), ctypes.c_void_p(cu_seqlens.data_ptr()), n_rows, width, channels,
+                ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream),
+            )
+        _lib.check(self.lib, self._handle, code, "op_unpack_padded")
+        return out
+
     def forward_rows(self, rows: Sequence[Sequence[int]]) -> tuple[torch.Tensor, torch.Tensor, np.ndarray]:
         """Convenience: host id rows -> one H2D copy -> forward.  Returns (prune[T,2], rank[B,nl], cu_host)."""
 

@@ -512,12 +512,20 @@ class OpenProvenceModel:
             raise ValueError("input_ids must be provided")
         if labels is not None:
             raise NotImplementedError("training losses are outside the MI355X inference path")
-        ids_np, cu_np, max_len = pack_padded(input_ids, attention_mask)
-        self.encoder.check_ids(ids_np)
-        width = int(input_ids.shape[1])
         dev = self._runtime_device
-        ids = torch.from_numpy(ids_np).to(dev)
-        cu = torch.from_numpy(cu_np).to(dev)
+        # A batch that already lives on the model's GPU is packed, checked and (below) unpacked there by HIP kernels
+        # (op_pack_padded / op_unpack_padded: same results, same errors); CPU tensors, and tensors of another GPU, go through
+        # the host as before.
+        on_device = (dev.type == "cuda" and isinstance(input_ids, torch.Tensor) and input_ids.device == dev
+                     and (attention_mask is None or (isinstance(attention_mask, torch.Tensor) and attention_mask.device == dev)))
+        if on_device:
+            ids, cu, cu_np, max_len = self.encoder.pack_padded_device(input_ids, attention_mask)
+        else:
+            ids_np, cu_np, max_len = pack_padded(input_ids, attention_mask)
+            self.encoder.check_ids(ids_np)
+            ids = torch.from_numpy(ids_np).to(dev)
+            cu = torch.from_numpy(cu_np).to(dev)
+        width = int(input_ids.shape[1])
         # (the fp16 + e4m3 kernel sets are range-guarded: a non-finite result is repeated on the (hi, lo) bf16 sets)
         hidden_states = None
         if output_hidden_states:
@@ -528,7 +536,10 @@ class OpenProvenceModel:
             hidden_states = tuple(hidden.reshape(hidden.shape[0], int(input_ids.shape[0]), width, hidden.shape[-1]).unbind(0))
         else:
             prune, rank = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len)
-        pruning_logits = unpack_to_padded(prune, cu_np, width)
+        if on_device:
+            pruning_logits = self.encoder.unpack_padded_device(prune, cu, int(input_ids.shape[0]), width)
+        else:
+            pruning_logits = unpack_to_padded(prune, cu_np, width)
         if return_dict is not None and not return_dict:
             return (rank, pruning_logits)
         return OpenProvenceOutput(

@@ -13,11 +13,12 @@ CSRC = ROOT / "open_provence_amd" / "csrc"
 
 
 def main() -> None:
-    """usage: kernel_resources.py <unit: api|row0|row1|row2|attn|panel> [name filter]"""
+    """usage: kernel_resources.py <unit: api|row0|row1|row2|row3|attn|panel|padded> [name filter]"""
 
     unit = sys.argv[1] if len(sys.argv) > 1 else "attn"
     pattern = sys.argv[2] if len(sys.argv) > 2 else ""
     src, defines = {"api": ("op_api.hip", []), "attn": ("op_launch_attn.hip", []), "panel": ("op_launch_panel.hip", []),
+                    "padded": ("op_launch_padded.hip", []),
                     "row0": ("op_launch_row.hip", ["-DOPL_ROW_PART=0"]), "row1": ("op_launch_row.hip", ["-DOPL_ROW_PART=1"]),
                     "row2": ("op_launch_row.hip", ["-DOPL_ROW_PART=2"]), "row3": ("op_launch_row.hip", ["-DOPL_ROW_PART=3"])}[unit]
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-c", *defines,
