@@ -218,6 +218,7 @@ class OpenProvenceModel:
         kernel_set: str | None = None,
         calibrate: "bool | float | None" = None,
         calibration_rows: "Sequence[Sequence[int]] | None" = None,
+        forward_token_budget: int | None = None,
     ) -> None:
         # kernel_set / calibrate / calibration_rows: how the arithmetic is chosen from the loaded weights
         # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615)
@@ -256,6 +257,61 @@ class OpenProvenceModel:
         self._update_tokenizer_runtime()
         self._update_runtime_defaults()
         self.default_threshold = self._resolve_default_threshold(config)
+        self.forward_token_budget = forward_token_budget  # (None: OPEN_PROVENCE_FORWARD_TOKENS, else the device's default)
+
+    # -- how many tokens process() puts into one forward (pipeline.plan_forward_chunks) ----------------------------------
+    # One round of the chip is n_cus x ROW_BM rows: the whole-layer kernels run one 128-row block per CU, and a launch takes
+    # one block period however few blocks it has -- so a forward costs about the same up to that many tokens, and the budget is
+    # counted in such rounds (round_token_budget).  FORWARD_BUDGET_ROUNDS is the default (0 would be the fixed batch_size
+    # stride): one round -- never slower than the stride in any measured workload, 20 - 27 % less inference_seconds where a granule
+    # holds more than batch_size rows, and the only R that is not sometimes worse than a smaller one
+    # (profiles/process_token_budget.txt).
+    FORWARD_BUDGET_ROUNDS = 1
+    FORWARD_ROUND_ROWS_PER_CU = 128
+
+    @property
+    def forward_token_budget(self) -> int:
+        """Token budget of one forward of ``process()`` / ``get_raw_predictions_batch`` on the native path: chunks of
+        ``batch_size`` rows are coalesced while their padded tokens fit (``pipeline.plan_forward_chunks``); 0 = the fixed
+        ``batch_size`` stride of the reference.  A row's outputs do not depend on its companions, so results do not change."""
+
+        value = self.__dict__.get("_forward_token_budget")
+        if value is None:
+            value = self.__dict__["_forward_token_budget"] = self._default_forward_token_budget()
+        return value
+
+    @forward_token_budget.setter
+    def forward_token_budget(self, value: int | None) -> None:
+        if value is None:  # OPEN_PROVENCE_FORWARD_TOKENS, else the device's default
+            self.__dict__["_forward_token_budget"] = self._default_forward_token_budget()
+            return
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+            raise ValueError(f"forward_token_budget must be a non-negative integer, got {value!r}")
+        if value < 0:
+            raise ValueError(f"forward_token_budget must be >= 0 (0 = the fixed batch_size stride), got {value!r}")
+        self.__dict__["_forward_token_budget"] = int(value)
+
+    def round_token_budget(self, rounds: int = 1) -> int:
+        """``rounds`` rounds of the model's device in tokens (``n_cus`` x 128 each); 0 without a device."""
+
+        dev = getattr(self, "_runtime_device", None)
+        if isinstance(dev, torch.device) and dev.type == "cuda" and torch.cuda.is_available():
+            n_cus = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+            return int(rounds) * n_cus * self.FORWARD_ROUND_ROWS_PER_CU
+        return 0
+
+    def _default_forward_token_budget(self) -> int:
+        text = os.environ.get("OPEN_PROVENCE_FORWARD_TOKENS", "").strip()
+        if text:
+            try:
+                value = int(text)
+            except ValueError:
+                raise ValueError(f"OPEN_PROVENCE_FORWARD_TOKENS must be a non-negative integer, got {text!r}") from None
+            if value < 0:
+                raise ValueError(f"OPEN_PROVENCE_FORWARD_TOKENS must be >= 0, got {text!r}")
+            return value
+        # (no device -- a model whose forward was replaced, which keeps the fixed stride anyway -- gives 0)
+        return self.round_token_budget(self.FORWARD_BUDGET_ROUNDS) if self.FORWARD_BUDGET_ROUNDS else 0
 
     @staticmethod
     def _normalize_device(device: str | torch.device | None) -> torch.device | None:
@@ -464,6 +520,7 @@ class OpenProvenceModel:
             kernel_set=kwargs.pop("kernel_set", None),
             calibrate=kwargs.pop("calibrate", None),
             calibration_rows=kwargs.pop("calibration_rows", None),
+            forward_token_budget=kwargs.pop("forward_token_budget", None),
         )
         if max_length is not None:
             model.max_length = int(max_length)
@@ -581,6 +638,7 @@ class OpenProvenceModel:
             "manual": (self._manual_special_tokens_required, self._manual_cls_token_id, self._manual_sep_token_id),
             "vocab_size": int(dims.vocab_size) if dims is not None else None,
             "num_labels": int(getattr(dims, "num_labels", 0) or getattr(self, "num_labels", 1) or 1),
+            "forward_token_budget": int(self.forward_token_budget),  # replicas plan their forwards as the owner would
         }
 
     @classmethod
@@ -604,6 +662,7 @@ class OpenProvenceModel:
         model._manual_special_tokens_required, model._manual_cls_token_id, model._manual_sep_token_id = spec["manual"]
         model._remote_forward = remote_forward
         model._dist = None
+        model.forward_token_budget = int(spec.get("forward_token_budget", 0))
         return model
 
     # -- data parallelism over (query, block) rows -----------------------------------
@@ -626,7 +685,11 @@ class OpenProvenceModel:
           the plain single-GPU pipeline, and ONE ``gather_object`` at the end moves the per-context results to ``dst``:
           the host stages -- most of the time of a call with short contexts -- scale with the ranks too.
         * ``"rows"``: every rank runs the whole host pipeline and only the forward batches are divided (as described
-          above).  ``get_raw_predictions_batch`` always shards rows."""
+          above).  ``get_raw_predictions_batch`` always shards rows.
+
+        Every rank must hold the same ``forward_token_budget``: the ranks derive the chunks of a row-sharded call from it and
+        would mismatch their collectives otherwise.  ``round_token_budget()`` is ``n_cus`` x 128 of each rank's own device:
+        on a node of unlike GPUs set one explicit number on every rank."""
 
         import torch.distributed as dist
 
@@ -747,6 +810,7 @@ class OpenProvenceModel:
 
         remote = self.__dict__.get("_remote_forward")
         if remote is not None:  # host-stage replica (frontend.py, mode="host"): the GPU owner's process runs the forward
+            self._count_forward(len(rows), sum(len(r) for r in rows))
             return remote.submit(rows, segments)
         info = self._dist_info()
         shard = None
@@ -768,6 +832,15 @@ class OpenProvenceModel:
         handle = self._enqueue_local(rows, segments)
         handle["shard"] = shard
         return handle
+
+    def _count_forward(self, n_rows: int, n_tokens: int) -> None:
+        """One forward this process enqueued (or, a host-stage replica, submitted): ``performance_trace.runtime["forwards"]``."""
+
+        stats = self.__dict__.get("_forward_stats")
+        if stats is not None:
+            stats["launches"] += 1
+            stats["rows"] += int(n_rows)
+            stats["tokens"] += int(n_tokens)
 
     @staticmethod
     def _pack_launch(rows: list[list[int]], segments: list[list[tuple[int, int]]] | None):
@@ -830,6 +903,7 @@ class OpenProvenceModel:
             np.copyto(pool["seg_np"][: 2 * n_seg], seg_flat)
             seg_dev = pool["seg"][: 2 * n_seg].to(dev, non_blocking=True).view(n_seg, 2)
         _, rank_dev = self.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev)
+        self._count_forward(n_rows, total)
         if seg_counts is not None:
             means_dev = self.encoder.segment_means(keep_dev, seg_dev)
             pool["keep"][:n_seg].copy_(means_dev, non_blocking=True)
@@ -958,12 +1032,14 @@ class OpenProvenceModel:
             keep_dev = torch.empty(int(cu_np[-1]), dtype=torch.float32, device=dev)
             ids_dev, cu_dev = torch.from_numpy(ids_np).to(dev), torch.from_numpy(cu_np).to(dev)
             _, rank = self.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev)
+            self._count_forward(len(rows), int(cu_np[-1]))
             keep = keep_dev.cpu().numpy()
             rank_cpu = rank.cpu()
             if self.encoder.f8_active() and not (np.isfinite(keep).all() and bool(torch.isfinite(rank_cpu).all())):
                 # range guard of the fp16 + e4m3 kernel sets: repeat on the (hi, lo) bf16 sets, stay there
                 if self.encoder.fall_back_from_f8("get_raw_predictions"):
                     _, rank = self.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev)
+                    self._count_forward(len(rows), int(cu_np[-1]))
                     keep, rank_cpu = keep_dev.cpu().numpy(), rank.cpu()
             return rank_cpu, [keep[cu_np[i] : cu_np[i + 1]] for i in range(len(rows))]
 
@@ -1047,19 +1123,35 @@ class OpenProvenceModel:
         else:
             queries = [str(query)] * len(contexts_batch)
         results: list[RawPrediction] = []
-        for start in range(0, len(contexts_batch), batch_size):
-            chunk = contexts_batch[start : start + batch_size]
-            chunk_queries = queries[start : start + batch_size]
-            rows = self._encode_texts([q + sep + "".join(c) for q, c in zip(chunk_queries, chunk)], truncate=True)
+        n_blocks = len(contexts_batch)
+        spans = [(start, min(start + batch_size, n_blocks)) for start in range(0, n_blocks, batch_size)]
+        all_rows = widths = None
+        if n_blocks > batch_size and self._forward_is_native() and self.forward_token_budget > 0:
+            # native forward: chunks of batch_size rows coalesced within the token budget (pipeline.plan_forward_chunks); a
+            # row's tokens do not depend on its batch (no padding), and each row keeps the padded width of ITS batch_size chunk
+            all_rows = self._encode_texts([q + sep + "".join(c) for q, c in zip(queries, contexts_batch)], truncate=True)
+            lengths = [len(r) for r in all_rows]
+            widths = [max(lengths[a:b], default=0) for a, b in spans]
+            spans = pl.plan_forward_chunks(lengths, batch_size, self.forward_token_budget)
+        for start, stop in spans:
+            chunk = contexts_batch[start:stop]
+            chunk_queries = queries[start:stop]
+            if all_rows is not None:
+                rows = all_rows[start:stop]
+            else:
+                rows = self._encode_texts([q + sep + "".join(c) for q, c in zip(chunk_queries, chunk)], truncate=True)
             rank, keeps = self._predict_rows(rows, None)
             # the reference returns every row's probabilities at the padded batch width (standalone.py:1820-1823: softmax
             # over the padded logits tensor); positions past the row's tokens carry softmax([0, 0])[1] = 0.5 here (the
             # forward boundary zero-fills masked positions; the reference's values there are whatever the model makes of
             # pad tokens, and no range ever addresses them)
-            width = max((len(r) for r in rows), default=0)
+            # (the padded width of a row is that of ITS batch_size chunk, whatever forward it travelled in)
+            row_widths = ([widths[at // batch_size] for at in range(start, stop)] if widths is not None
+                          else [max((len(r) for r in rows), default=0)] * len(rows))
             for i, ctxs in enumerate(chunk):
                 if len(ctxs) == 0:
                     continue
+                width = row_widths[i]
                 probs = np.asarray(keeps[i], dtype=np.float32)
                 if len(probs) < width:
                     probs = np.concatenate([probs, np.full(width - len(probs), 0.5, dtype=np.float32)])
@@ -1410,16 +1502,33 @@ class OpenProvenceModel:
 
         elapsed = 0.0
         pipelined = pending is not None and self._can_pipeline()
-        for start in range(0, len(inference_jobs), batch_size):
-            chunk = inference_jobs[start : start + batch_size]
+        n_jobs = len(inference_jobs)
+        spans = [(start, min(start + batch_size, n_jobs)) for start in range(0, n_jobs, batch_size)]
+        prepared = None
+        # Native forward: a forward costs the same up to about one round of the chip, so the chunks of batch_size rows are
+        # coalesced within the model's token budget (pipeline.plan_forward_chunks; rows are independent, results do not
+        # change).  The plan needs every row's length: the rows of the granule are built first.  A replaced forward keeps
+        # the reference's contract: at most batch_size rows per call.
+        if n_jobs > batch_size and self._forward_is_native() and self.forward_token_budget > 0:
+            prepared = [
+                self._prepare_block_inputs(query_token_ids[job["query_idx"]],
+                                           states[(job["query_idx"], job["context_idx"])].blocks[job["block_idx"]])
+                for job in inference_jobs
+            ]
+            spans = pl.plan_forward_chunks([len(p[0]) for p in prepared], batch_size, self.forward_token_budget)
+        for start, stop in spans:
+            chunk = inference_jobs[start:stop]
             if not chunk:
                 continue
             rows: list[list[int]] = []
             type_rows: list[list[int]] = []
             ranges_per_job: list[list[tuple[int, int]]] = []
-            for job in chunk:
-                block = states[(job["query_idx"], job["context_idx"])].blocks[job["block_idx"]]
-                ids, _mask, type_ids, ranges = self._prepare_block_inputs(query_token_ids[job["query_idx"]], block)
+            for at, job in enumerate(chunk, start):
+                if prepared is not None:
+                    ids, _mask, type_ids, ranges = prepared[at]
+                else:
+                    block = states[(job["query_idx"], job["context_idx"])].blocks[job["block_idx"]]
+                    ids, _mask, type_ids, ranges = self._prepare_block_inputs(query_token_ids[job["query_idx"]], block)
                 rows.append(ids)
                 type_rows.append(type_ids)
                 ranges_per_job.append(ranges)
@@ -1634,6 +1743,7 @@ class OpenProvenceModel:
                 preprocess_batch_size=preprocess_batch_size, torch_dataloader_kwargs=torch_dataloader_kwargs,
             )
         finally:
+            self.__dict__.pop("_forward_stats", None)  # (the call's counter: later get_raw_predictions* calls count nowhere)
             if gc_was_enabled:
                 gc.enable()
 
@@ -1700,13 +1810,15 @@ class OpenProvenceModel:
                                "local function as sentence_splitter / debug_messages?): running it in this process")
             return None
         front = self.__dict__.get("_host_front_end")
-        if front is None or front.world != workers or not front._open:
+        if (front is None or front.world != workers or not front._open
+                or front.__dict__.get("forward_token_budget") != self.forward_token_budget):  # (replicas plan with the budget they were built with)
             if front is not None:
                 front.close()
             if self.__dict__.get("_front_end_unavailable"):
                 return None
             try:
                 front = self.__dict__["_host_front_end"] = HostFrontEnd(self, workers=workers, import_main=not implicit)
+                front.forward_token_budget = self.forward_token_budget
             except Exception as exc:  # the tokenizer cannot be sent to worker processes, or a worker failed to start
                 self.__dict__["_front_end_unavailable"] = True
                 self.__dict__["_host_front_end"] = None
@@ -1759,6 +1871,7 @@ class OpenProvenceModel:
         batch_size = max(1, batch_size)
         threshold = self._resolve_process_threshold(threshold)
         start_total = perf_counter()
+        forward_stats = self.__dict__["_forward_stats"] = {"launches": 0, "rows": 0, "tokens": 0}
         splitter = self._resolve_sentence_splitter(sentence_splitter, language)
 
         if isinstance(debug_messages, bool):
@@ -2015,6 +2128,10 @@ class OpenProvenceModel:
             runtime["kernel_set"] = self.encoder.effective_policy()["kernel_set"]
             runtime["calibration"] = self.encoder.calibration
             runtime["fallback_from_f8"] = int(getattr(self.encoder, "fallbacks", 0))
+        if self._forward_is_native():
+            # the forwards this process enqueued (the owner of a host front-end: its replicas' merged batches) or, a
+            # host-stage replica, submitted.  A dict on purpose: as_dict() / "timing" keep numbers only
+            runtime["forwards"] = dict(forward_stats, token_budget=int(self.forward_token_budget))
         transport = (getattr(self, "_dist", None) or {}).get("transport")
         if transport is not None and hasattr(transport, "conns"):  # the owner of a host-mode front-end
             runtime["host_replicas"] = len(transport.conns)

@@ -280,6 +280,37 @@ def assign_jobs(contexts: Sequence[Sequence[Any]], world: int) -> list[list[int]
     return owner
 
 
+FORWARD_ROW_ALIGN = 32  # sequences of a packed forward start at multiples of this many rows (ROW_ALIGN of the kernels)
+
+
+def plan_forward_chunks(lengths: Sequence[int], batch_size: int, token_budget: int) -> list[tuple[int, int]]:
+    """Contiguous, order-preserving ``(start, stop)`` chunks of the rows of one granule, one forward each.
+
+    A row costs its padded length ``ceil(len / 32) * 32``.  An open chunk takes the next row while it holds fewer than
+    ``batch_size`` rows, or while its cost plus the row's cost stays within ``token_budget``; otherwise it closes.  So a
+    chunk never holds fewer rows than the fixed ``batch_size`` stride gives it (only the last one may), a chunk grown past
+    ``batch_size`` rows costs at most the budget, and ``token_budget <= 0`` IS the fixed stride.  The answer depends on
+    the three arguments alone -- not on the device, free memory or the rank -- so every rank of a process group and every
+    host-stage replica derives the same chunks from the same rows."""
+
+    batch_size = max(1, int(batch_size))
+    budget = int(token_budget)
+    n = len(lengths)
+    if budget <= 0:
+        return [(start, min(start + batch_size, n)) for start in range(0, n, batch_size)]
+    chunks: list[tuple[int, int]] = []
+    start = cost = 0
+    for i, length in enumerate(lengths):
+        row = -(-max(0, int(length)) // FORWARD_ROW_ALIGN) * FORWARD_ROW_ALIGN
+        if i - start >= batch_size and cost + row > budget:
+            chunks.append((start, i))
+            start, cost = i, 0
+        cost += row
+    if n > start:
+        chunks.append((start, n))
+    return chunks
+
+
 def normalize_sentences(raw_sentences: Sequence[str], context_text: str, strip_sentences: bool) -> list[str]:
     out: list[str] = []
     for entry in raw_sentences:

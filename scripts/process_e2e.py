@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """GPU-box probe: end-to-end ``process()`` (host pipeline + HIP forward) on a synthetic 1-query x N-context
 request with the char tokenizer of the tests; prints the reference-style timing breakdown and, with
---profile, the top of a cProfile run.  Usage: scripts/process_e2e.py [--contexts 256] [--chars 470] [--profile]"""
+--profile, the top of a cProfile run.  Usage: scripts/process_e2e.py [--contexts 256] [--chars 470] [--profile]
+
+--forward-tokens 0,r1,r2,r4 compares token budgets of the forwards (OpenProvenceModel.forward_token_budget; "rN" = N rounds
+of the chip, n_cus x 128 tokens; 0 = the fixed batch_size stride): the settings take turns (--passes times: a warm-up call,
+then --reps timed calls each) and every setting gets one JSON line with the median and the spread of its calls."""
 import argparse
 import cProfile
 import io
@@ -86,6 +90,11 @@ def main():
     ap.add_argument("--stock-tokenizer", action="store_true",
                     help="wordpiece: the plain transformers PreTrainedTokenizerFast object (what a checkpoint's tokenizer files load as; "
                     "it pickles, so process() can start host replicas by itself) instead of the test helper's local 4.x-style subclass")
+    ap.add_argument("--forward-tokens", default=None,
+                    help="token budget of one forward: a number (0 = the fixed batch_size stride), rN (N rounds of n_cus x 128 tokens) or "
+                    "'default'; a comma-separated list compares the settings in turns (in-process or with the replicas process() starts)")
+    ap.add_argument("--passes", type=int, default=2, help="--forward-tokens with several settings: how often the settings take turns")
+    ap.add_argument("--dump-result", default=None, help="write the result of the last call of every setting (without timings) as JSON here")
     ap.add_argument("--chars-are-words", action="store_true", help="wordpiece: size the contexts in words (~tokens) instead of characters")
     args = ap.parse_args()
 
@@ -93,6 +102,19 @@ def main():
     if args.stock_tokenizer:
         os.environ["E2E_STOCK_TOKENIZER"] = "1"
     question, contexts = make_request(args.contexts, args.chars)
+    budgets = [b.strip() for b in args.forward_tokens.split(",")] if args.forward_tokens else []
+
+    def budget_value(text):
+        if text == "default":
+            return None
+        if text.startswith("r"):
+            return int(text[1:]) * int(torch.cuda.get_device_properties(0).multi_processor_count) * 128
+        return int(text)
+
+    if len(budgets) == 1:  # (front-end workers and replicas take the budget of the model they are built from)
+        value = budget_value(budgets[0])
+        if value is not None:
+            os.environ["OPEN_PROVENCE_FORWARD_TOKENS"] = str(value)
     front = None
     if args.front_end > 0:
         from open_provence_amd.frontend import ProcessFrontEnd
@@ -111,6 +133,11 @@ def main():
         return target.process(question, contexts, threshold=0.1, batch_size=args.batch_size, sentence_splitter=period_splitter,
                               show_progress=False, preprocess_batch_size=args.preprocess_batch, preprocess_workers=args.workers)
 
+    if len(budgets) > 1:
+        if front is not None:
+            raise SystemExit("--forward-tokens with several settings: in-process, or the replicas process() starts by itself")
+        compare_budgets(args, target, call, [(b, budget_value(b)) for b in budgets])
+        return
     call()
     torch.cuda.synchronize()
     best = None
@@ -137,6 +164,45 @@ def main():
         buf = io.StringIO()
         pstats.Stats(pr, stream=buf).sort_stats("cumulative").print_stats(35)
         print(buf.getvalue()[:6000])
+    if front is not None:
+        front.close()
+
+
+def compare_budgets(args, model, call, settings):
+    """The same call under every budget in turns; one JSON line per setting."""
+
+    runs = {label: [] for label, _ in settings}
+    last = {}
+    for _ in range(max(1, args.passes)):
+        for label, value in settings:
+            model.forward_token_budget = value
+            call()  # warm-up (with replicas: they are restarted with the new budget here)
+            torch.cuda.synchronize()
+            for _ in range(args.reps):
+                t0 = time.perf_counter()
+                out = call()
+                torch.cuda.synchronize()
+                runs[label].append((time.perf_counter() - t0, out))
+            last[label] = out
+    keep = lambda out: {k: v for k, v in out.items() if k not in ("timing", "performance_trace")}
+    first = keep(last[settings[0][0]])
+    for label, value in settings:
+        walls = np.array([dt for dt, _ in runs[label]])
+        inference = np.array([out["timing"]["inference_seconds"] for _, out in runs[label]])
+        total = np.array([out["timing"]["total_seconds"] for _, out in runs[label]])
+        forwards = [getattr(out["performance_trace"], "runtime", {}).get("forwards", {}) for _, out in runs[label]]
+        stat = lambda a: {"median": round(float(np.median(a)), 5), "min": round(float(a.min()), 5), "max": round(float(a.max()), 5)}
+        print(json.dumps({"forward_tokens": label, "token_budget": forwards[-1].get("token_budget"), "contexts": args.contexts,
+                          "batch_size": args.batch_size, "tokenizer": args.tokenizer, "calls": len(walls),
+                          "host_replicas": runs[label][-1][1]["timing"].get("host_replicas", 0),
+                          "inference_seconds": stat(inference), "total_seconds": stat(total), "wall_seconds": stat(walls),
+                          "contexts_per_s": round(args.contexts / float(np.median(walls)), 1),
+                          "launches": sorted({f.get("launches") for f in forwards}, key=lambda v: -1 if v is None else v),
+                          "equals_first_setting": keep(last[label]) == first}), flush=True)
+    if args.dump_result:
+        with open(args.dump_result, "w", encoding="utf-8") as handle:
+            json.dump({label: keep(out) for label, out in last.items()}, handle)
+    front = model.__dict__.get("_host_front_end")
     if front is not None:
         front.close()
 
