@@ -349,6 +349,53 @@ int op_pack_padded(op_handle* h, const void* ids_dev, int ids_dtype, const void*
 int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_seqlens_dev, int n_rows, int width, int channels,
                      float* padded_dev, void* hip_stream);
 
+/* The running audit of a calibrated kernel set (HipEncoder's audit policy "running").  Replaces: nothing
+ * in the reference, which picks its dtype once at load (standalone.py:1631-1642) and never looks again.  Additive to ABI 10
+ * (op_abi_version() is unchanged: detect the five calls by symbol).  The handle owns a bitmap of vocab_size bits -- the token
+ * ids the audited rows have held -- and the longest audited row.  Both belong to ONE arithmetic: they start empty at op_create
+ * and are emptied by op_coverage_reset, by op_load_weight of the embedding table, by op_calibrate, and whenever the handle runs
+ * another kernel set (or another layer mask of sets 8 / 9) than the one they were collected under -- a new arithmetic has seen
+ * nothing.  Emptying enqueues nothing: the memory is cleared on the stream of the next scan or commit, which is also where the
+ * kernel set is looked at, so op_select_kernel_set to another set AND BACK between two such calls (the audit's own detour
+ * through the reference set) keeps the coverage.  Rows are rows of a packed batch (ids_dev [total_tokens], cu_seqlens_dev
+ * [n_seqs + 1]); rows_dev [n_rows] int32 lists some of them.  On the device a listed row outside 0 <= row < n_seqs is skipped
+ * and row bounds are held inside [0, total_tokens), whatever cu_seqlens_dev holds.  Every call checks its arguments before it
+ * enqueues (OP_ERR_INVALID: a NULL report or buffer, a wrong struct_bytes, a negative count) and before it looks at the
+ * handle.  Like every call on a handle, serialised by the caller.
+ *
+ * op_coverage_scan: read-only.  row_novel_dev[s] = the number of positions of row s whose id has no bit in the bitmap
+ *   (duplicates count once per position; an id outside 0 <= id < vocab_size counts as novel and is never used as an index).
+ *   The report receives the sum of those counts, the longest row of the batch with its index (the first of equals; -1 for
+ *   an empty batch) and the handle's longest audited row.  The call copies the report to the host and SYNCHRONISES
+ *   hip_stream ONCE, as op_pack_padded does; a stream that is being captured is refused (OP_ERR_STATE).
+ * op_coverage_commit: sets the bit of every id of the listed rows and raises the longest audited row.  Asynchronous.
+ * op_coverage_reset: empties both.
+ * op_gather_rows: lays the listed rows end to end in sub_ids_dev (room for their tokens) and writes their prefix offsets to
+ *   sub_cu_dev [n_rows + 1] -- a packed batch for op_forward_packed.  Asynchronous.
+ * op_audit_compare: err_dev[0] = max |difference| between the pruning logits ([token][2]) of the listed rows' tokens in
+ *   prune_dev and the same tokens in sub_prune_dev (laid out by sub_cu_dev, as op_gather_rows leaves them), and between the
+ *   rows' ranking logits rank_dev[rows[i]][num_labels] and sub_rank_dev[i][num_labels]; +inf when a value on either side is
+ *   not finite, a listed row is not a row of the batch, or a row's two lengths differ.  The call initialises the cell on
+ *   hip_stream (the caller zeroes nothing); fp32 max does not depend on the order, so the result is exact.  n_rows == 0
+ *   leaves +0.0.  Asynchronous. */
+typedef struct op_coverage_report {
+  uint32_t struct_bytes;      /* sizeof(op_coverage_report) */
+  int32_t novel_tokens;       /* sum of row_novel_dev */
+  int32_t longest_row_tokens; /* the batch's longest row ... */
+  int32_t longest_row;        /* ... and its index */
+  int32_t max_audited_tokens; /* the handle's longest audited row */
+} op_coverage_report;
+int op_coverage_scan(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev, int n_seqs, int total_tokens,
+                     int32_t* row_novel_dev, op_coverage_report* report, void* hip_stream);
+int op_coverage_commit(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev, int n_seqs, int total_tokens,
+                       const int32_t* rows_dev, int n_rows, void* hip_stream);
+int op_coverage_reset(op_handle* h);
+int op_gather_rows(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev, int n_seqs, int total_tokens,
+                   const int32_t* rows_dev, int n_rows, int32_t* sub_ids_dev, int32_t* sub_cu_dev, void* hip_stream);
+int op_audit_compare(op_handle* h, const float* prune_dev, const float* rank_dev, const int32_t* cu_seqlens_dev, int n_seqs,
+                     int total_tokens, const int32_t* rows_dev, int n_rows, const float* sub_prune_dev, const float* sub_rank_dev,
+                     const int32_t* sub_cu_dev, float* err_dev, void* hip_stream);
+
 /* Replaces: the per-fragment `float(block_probs[start:end].mean())` of the reference's post-processing
  * (standalone.py:3075-3082), evaluated on the device on the keep-probabilities a forward left there:
  *   seg_dev [n_seg, 2] int32  token ranges [start, end) into keep_prob_dev (clamped to [0, n_values))

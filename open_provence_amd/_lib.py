@@ -62,6 +62,11 @@ EXPORTED_SYMBOLS = (
     "op_forward_packed_hidden",
     "op_pack_padded",
     "op_unpack_padded",
+    "op_coverage_scan",
+    "op_coverage_commit",
+    "op_coverage_reset",
+    "op_gather_rows",
+    "op_audit_compare",
     "op_segment_means",
     "op_debug_capture_hidden",
     "op_profile_enable",
@@ -157,6 +162,19 @@ class OpPaddedReport(ctypes.Structure):
 OP_INT_I32, OP_INT_I64, OP_INT_U8 = 0, 1, 2
 OP_PADDED_BAD_MASK, OP_PADDED_BAD_ID = 1, 2  # op_padded_report.status bits
 
+
+class OpCoverageReport(ctypes.Structure):
+    """``op_coverage_report``: what ``op_coverage_scan`` found in one packed batch."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("novel_tokens", ctypes.c_int32),
+        ("longest_row_tokens", ctypes.c_int32),
+        ("longest_row", ctypes.c_int32),
+        ("max_audited_tokens", ctypes.c_int32),
+    ]
+
+
 OP_CAL_FULL_REPORT = 1
 OP_CAL_WHOLE_DEPTH = 2
 
@@ -228,6 +246,17 @@ def load_library() -> ctypes.CDLL:
         lib.op_pack_padded.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, ctypes.POINTER(OpPaddedReport), vp]
         lib.op_unpack_padded.restype = ci
         lib.op_unpack_padded.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
+    if hasattr(lib, "op_coverage_scan"):  # (the running audit's five calls, additive to ABI 10 like the two above)
+        lib.op_coverage_scan.restype = ci
+        lib.op_coverage_scan.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.POINTER(OpCoverageReport), vp]
+        lib.op_coverage_commit.restype = ci
+        lib.op_coverage_commit.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp]
+        lib.op_coverage_reset.restype = ci
+        lib.op_coverage_reset.argtypes = [vp]
+        lib.op_gather_rows.restype = ci
+        lib.op_gather_rows.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, vp]
+        lib.op_audit_compare.restype = ci
+        lib.op_audit_compare.argtypes = [vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]
     lib.op_segment_means.restype = ci
     lib.op_segment_means.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     lib.op_debug_capture_hidden.restype = ci

@@ -28,6 +28,7 @@ _ROWGEMM = [CSRC / name for name in ("opk_rowgemm.hip.h", "opk_rowgemm_pack.hip.
 _INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_attn.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
 
 _PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
+_AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
 
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
@@ -43,6 +44,7 @@ UNITS = [
     ("op_launch_attn", CSRC / "op_launch_attn.hip", [], _INTERNAL),
     ("op_launch_panel", CSRC / "op_launch_panel.hip", [], _INTERNAL),
     ("op_launch_padded", CSRC / "op_launch_padded.hip", [], _INTERNAL + [_PADDED]),
+    ("op_launch_audit", CSRC / "op_launch_audit.hip", [], _INTERNAL + [_AUDIT]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = sorted({h for u in UNITS for h in u[3]})

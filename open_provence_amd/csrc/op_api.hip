@@ -140,6 +140,13 @@ struct op_handle {
   uint32_t* pad_status = nullptr;    // op_pack_padded: the device status block (opk::PAD_ST_WORDS words), allocated on first use
   int32_t* pad_host = nullptr;       // ... and its pinned host staging: cu_seqlens[n_rows + 1] + the status block
   size_t pad_host_words = 0;
+  // the running audit's coverage (op_coverage_scan / op_coverage_commit): a bitmap of vocab_size bits + opl::COV_WORDS state words
+  uint32_t* cov_bits = nullptr;
+  uint32_t* cov_state = nullptr;
+  uint32_t* cov_host = nullptr;      // pinned staging of the state block, allocated on first use
+  bool cov_clear = true;             // clear bitmap and state on the stream of the next scan / commit (nothing audited yet)
+  int cov_set = -2;                  // the arithmetic the coverage was collected under: kernel set (public numbering) ...
+  uint64_t cov_mlp_layers = 0;       // ... and the layer mask of sets 8 / 9; another one at the next scan / commit clears too
   std::string err;
 };
 
@@ -1222,6 +1229,8 @@ int op_create(const op_config* cfg, op_handle** out) {
     h->missing.push_back(pre + "mlp.Wi.weight");
     h->missing.push_back(pre + "mlp.Wo.weight");
   }
+  OP_CREATE_TRY(dev_alloc(h, &h->cov_bits, ((size_t)h->V + 31) / 32));
+  OP_CREATE_TRY(dev_alloc(h, &h->cov_state, (size_t)opl::COV_WORDS));
   for (int t = 0; t < 2; ++t) {
     std::vector<float> cs, sn;
     build_rope_host(t == 1 ? cfg->global_rope_theta : cfg->local_rope_theta, h->max_pos, cs, sn);
@@ -1243,6 +1252,7 @@ void op_destroy(op_handle* h) {
   }
   for (void* p : h->allocations) (void)hipFree(p);
   if (h->pad_host) (void)hipHostFree(h->pad_host);
+  if (h->cov_host) (void)hipHostFree(h->cov_host);
   delete h;
 }
 
@@ -1279,6 +1289,7 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
 
   if (name == "model.embeddings.tok_embeddings.weight") {
     dst_f32 = h->emb; expect(h->V, H);
+    h->cov_clear = true;  // (the audited ids were audited against the old table)
   } else if (name == "model.embeddings.norm.weight") {
     dst_f32 = h->emb_norm; expect(H, 1);
   } else if (name == "model.final_norm.weight") {
@@ -1684,7 +1695,7 @@ int op_select_kernel_set(op_handle* h, int kernel_set) {
   h->forced_set = kernel_set == OP_KS_AUTO ? -1 : kernel_set;
   h->forced_mlp_layers = ~0ull;
   h->resolved = false;
-  return resolve_policy(h);
+  return resolve_policy(h);  // (the coverage follows the arithmetic: coverage_prepare)
 }
 
 int op_mlp_correction_layers(op_handle* h, uint64_t* layer_mask) {
@@ -1737,6 +1748,7 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   }
   const bool full_report = report && (report->flags & OP_CAL_FULL_REPORT) != 0;
   OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  h->cov_clear = true;  // whatever set comes out, it has seen no real row
 
   // the default selection and its (hi, lo) bf16 realisation = the reference of the comparison
   const bool f8_off_before = h->f8_off;
@@ -2251,6 +2263,137 @@ int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_se
   OP_HIP(h, hipSetDevice(h->cfg.device_id));
   if (!opl::launch_padded_scatter(reinterpret_cast<hipStream_t>(hip_stream), packed_dev, cu_seqlens_dev, n_rows, width, channels, padded_dev))
     return fail(h, OP_ERR_UNSUPPORTED, "op_unpack_padded: no kernel for %d channels", channels);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
+// The coverage belongs to one arithmetic: the kernel set (and the layer mask of sets 8 / 9) it was collected under.  It is
+// emptied lazily, on the stream of the call that next looks at it -- after op_coverage_reset / op_calibrate / op_load_weight
+// of the embedding table, and whenever the handle runs another arithmetic than the one the coverage belongs to.  So
+// op_select_kernel_set enqueues nothing (the default audit mode never pays for a feature it does not use), and an audit's
+// detour through the reference set and back finds the coverage as it left it.
+static int coverage_prepare(op_handle* h, hipStream_t stream) {
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  const int set = h->resolved ? public_set(h) : -2;
+  const uint64_t mlp = (h->resolved && h->mlp_f8) ? h->mlp_layers : 0ull;
+  if (h->cov_clear || set != h->cov_set || mlp != h->cov_mlp_layers) {
+    OP_HIP(h, hipMemsetAsync(h->cov_bits, 0, (((size_t)h->V + 31) / 32) * sizeof(uint32_t), stream));
+    OP_HIP(h, hipMemsetAsync(h->cov_state, 0, opl::COV_WORDS * sizeof(uint32_t), stream));
+    h->cov_clear = false;
+    h->cov_set = set;
+    h->cov_mlp_layers = mlp;
+  }
+  return OP_OK;
+}
+
+int op_coverage_scan(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev, int n_seqs, int total_tokens,
+                     int32_t* row_novel_dev, op_coverage_report* report, void* hip_stream) {
+  // (the arguments' own fields first: none of them needs the handle)
+  if (!report) return fail(h, OP_ERR_INVALID, "op_coverage_scan: report is NULL");
+  if (report->struct_bytes != sizeof(op_coverage_report))
+    return fail(h, OP_ERR_INVALID, "op_coverage_scan: op_coverage_report.struct_bytes is %u, expected %zu", report->struct_bytes,
+                sizeof(op_coverage_report));
+  if (n_seqs < 0) return fail(h, OP_ERR_INVALID, "op_coverage_scan: negative n_seqs %d", n_seqs);
+  if (total_tokens < 0) return fail(h, OP_ERR_INVALID, "op_coverage_scan: negative total_tokens %d", total_tokens);
+  if (n_seqs > 0 && !cu_seqlens_dev) return fail(h, OP_ERR_INVALID, "op_coverage_scan: cu_seqlens_dev is NULL");
+  if (n_seqs > 0 && !row_novel_dev) return fail(h, OP_ERR_INVALID, "op_coverage_scan: row_novel_dev is NULL");
+  if (n_seqs > 0 && total_tokens > 0 && !ids_dev) return fail(h, OP_ERR_INVALID, "op_coverage_scan: ids_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_coverage_scan: NULL handle");
+  report->novel_tokens = report->longest_row_tokens = report->max_audited_tokens = 0;
+  report->longest_row = -1;
+
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  OP_HIP(h, hipStreamIsCapturing(stream, &capturing));
+  if (capturing != hipStreamCaptureStatusNone)
+    return fail(h, OP_ERR_STATE, "op_coverage_scan: the stream is being captured (the call synchronises it to read the report back)");
+  if (!h->cov_host) {
+    void* p = nullptr;
+    hipError_t e = hipHostMalloc(&p, opl::COV_WORDS * sizeof(uint32_t), hipHostMallocDefault);
+    if (e != hipSuccess) return fail(h, OP_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", opl::COV_WORDS * sizeof(uint32_t), hipGetErrorString(e));
+    h->cov_host = reinterpret_cast<uint32_t*>(p);
+  }
+  OP_TRY(coverage_prepare(h, stream));
+  OP_HIP(h, hipMemsetAsync(h->cov_state + opl::COV_NOVEL, 0, (opl::COV_WORDS - opl::COV_NOVEL) * sizeof(uint32_t), stream));
+  if (n_seqs > 0) {
+    opl::launch_coverage_scan(stream, ids_dev, cu_seqlens_dev, n_seqs, total_tokens, h->V, h->cov_bits, row_novel_dev, h->cov_state);
+    OP_HIP(h, hipGetLastError());
+  }
+  OP_HIP(h, hipMemcpyAsync(h->cov_host, h->cov_state, opl::COV_WORDS * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  OP_HIP(h, hipStreamSynchronize(stream));  // the one synchronisation: the caller decides on the host whether to audit
+  report->max_audited_tokens = (int32_t)h->cov_host[opl::COV_MAXLEN];
+  report->novel_tokens = (int32_t)h->cov_host[opl::COV_NOVEL];
+  if (n_seqs > 0) {
+    report->longest_row_tokens = (int32_t)h->cov_host[opl::COV_LONGEST + 1];
+    report->longest_row = (int32_t)~h->cov_host[opl::COV_LONGEST];
+  }
+  return OP_OK;
+}
+
+// the checks commit, gather and compare share: a packed batch and a list of its rows
+static int check_row_list(op_handle* h, const char* who, const void* cu_seqlens_dev, int n_seqs, int total_tokens, const void* rows_dev,
+                          int n_rows) {
+  if (n_seqs < 0) return fail(h, OP_ERR_INVALID, "%s: negative n_seqs %d", who, n_seqs);
+  if (total_tokens < 0) return fail(h, OP_ERR_INVALID, "%s: negative total_tokens %d", who, total_tokens);
+  if (n_rows < 0) return fail(h, OP_ERR_INVALID, "%s: negative n_rows %d", who, n_rows);
+  if (n_rows > 0 && !cu_seqlens_dev) return fail(h, OP_ERR_INVALID, "%s: cu_seqlens_dev is NULL", who);
+  if (n_rows > 0 && !rows_dev) return fail(h, OP_ERR_INVALID, "%s: rows_dev is NULL", who);
+  return OP_OK;
+}
+
+int op_coverage_commit(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev, int n_seqs, int total_tokens,
+                       const int32_t* rows_dev, int n_rows, void* hip_stream) {
+  OP_TRY(check_row_list(h, "op_coverage_commit", cu_seqlens_dev, n_seqs, total_tokens, rows_dev, n_rows));
+  if (n_rows > 0 && total_tokens > 0 && !ids_dev) return fail(h, OP_ERR_INVALID, "op_coverage_commit: ids_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_coverage_commit: NULL handle");
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  OP_TRY(coverage_prepare(h, stream));
+  if (n_rows == 0) return OP_OK;
+  opl::launch_coverage_commit(stream, ids_dev, cu_seqlens_dev, n_seqs, total_tokens, rows_dev, n_rows, h->V, h->cov_bits, h->cov_state);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
+int op_coverage_reset(op_handle* h) {
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_coverage_reset: NULL handle");
+  h->cov_clear = true;
+  return OP_OK;
+}
+
+int op_gather_rows(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev, int n_seqs, int total_tokens,
+                   const int32_t* rows_dev, int n_rows, int32_t* sub_ids_dev, int32_t* sub_cu_dev, void* hip_stream) {
+  OP_TRY(check_row_list(h, "op_gather_rows", cu_seqlens_dev, n_seqs, total_tokens, rows_dev, n_rows));
+  if (!sub_cu_dev) return fail(h, OP_ERR_INVALID, "op_gather_rows: sub_cu_dev is NULL");
+  if (n_rows > 0 && total_tokens > 0 && !ids_dev) return fail(h, OP_ERR_INVALID, "op_gather_rows: ids_dev is NULL");
+  if (n_rows > 0 && total_tokens > 0 && !sub_ids_dev) return fail(h, OP_ERR_INVALID, "op_gather_rows: sub_ids_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_gather_rows: NULL handle");
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  if (n_rows == 0) {
+    OP_HIP(h, hipMemsetAsync(sub_cu_dev, 0, sizeof(int32_t), stream));
+    return OP_OK;
+  }
+  opl::launch_gather_rows(stream, ids_dev, cu_seqlens_dev, n_seqs, total_tokens, rows_dev, n_rows, sub_ids_dev, sub_cu_dev);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
+int op_audit_compare(op_handle* h, const float* prune_dev, const float* rank_dev, const int32_t* cu_seqlens_dev, int n_seqs,
+                     int total_tokens, const int32_t* rows_dev, int n_rows, const float* sub_prune_dev, const float* sub_rank_dev,
+                     const int32_t* sub_cu_dev, float* err_dev, void* hip_stream) {
+  OP_TRY(check_row_list(h, "op_audit_compare", cu_seqlens_dev, n_seqs, total_tokens, rows_dev, n_rows));
+  if (!err_dev) return fail(h, OP_ERR_INVALID, "op_audit_compare: err_dev is NULL");
+  if (n_rows > 0 && total_tokens > 0 && (!prune_dev || !sub_prune_dev)) return fail(h, OP_ERR_INVALID, "op_audit_compare: prune_dev / sub_prune_dev is NULL");
+  if (n_rows > 0 && (!rank_dev || !sub_rank_dev)) return fail(h, OP_ERR_INVALID, "op_audit_compare: rank_dev / sub_rank_dev is NULL");
+  if (n_rows > 0 && !sub_cu_dev) return fail(h, OP_ERR_INVALID, "op_audit_compare: sub_cu_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_audit_compare: NULL handle");
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  OP_HIP(h, hipMemsetAsync(err_dev, 0, sizeof(float), stream));  // +0.0: the kernel's atomicMax starts from it
+  if (n_rows == 0) return OP_OK;
+  opl::launch_audit_compare(stream, prune_dev, rank_dev, cu_seqlens_dev, n_seqs, total_tokens, rows_dev, n_rows, sub_prune_dev, sub_rank_dev,
+                            sub_cu_dev, h->nl, err_dev);
   OP_HIP(h, hipGetLastError());
   return OP_OK;
 }

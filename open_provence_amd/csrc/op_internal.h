@@ -103,4 +103,23 @@ bool launch_padded_pack(hipStream_t st, const void* ids, int ids_dtype, const vo
 // packed [T][channels] fp32 -> padded [n_rows][width][channels], every element written; channels 1 or 2
 bool launch_padded_scatter(hipStream_t st, const float* packed, const int32_t* cu, int n_rows, int width, int channels, float* padded);
 
+// The running audit of a calibrated kernel set (opk_audit.hip.h; op_coverage_scan / op_coverage_commit / op_gather_rows /
+// op_audit_compare).  The handle's coverage state block, uint32 words (= opk::COV_ST_*): the longest audited row, then what one
+// scan leaves -- the sum of the rows' novel positions and a uint64 (length << 32 | ~row) of the first longest row.
+constexpr int COV_MAXLEN = 0, COV_NOVEL = 1, COV_LONGEST = 2, COV_WORDS = 4;
+// row_novel[n_seqs]; the caller clears state[COV_NOVEL .. COV_WORDS) first
+void launch_coverage_scan(hipStream_t st, const int32_t* ids, const int32_t* cu, int n_seqs, int total, int vocab, const uint32_t* bits,
+                          int32_t* row_novel, uint32_t* state);
+// commit, gather and compare: a listed row outside [0, n_seqs) is skipped (compare: counts as +inf), row bounds are held inside
+// [0, total)
+void launch_coverage_commit(hipStream_t st, const int32_t* ids, const int32_t* cu, int n_seqs, int total, const int32_t* rows, int n_rows,
+                            int vocab, uint32_t* bits, uint32_t* state);
+// the listed rows end to end in sub_ids, their prefix offsets in sub_cu[n_rows + 1]
+void launch_gather_rows(hipStream_t st, const int32_t* ids, const int32_t* cu, int n_seqs, int total, const int32_t* rows, int n_rows,
+                        int32_t* sub_ids, int32_t* sub_cu);
+// err[0] (cleared by the caller) = max |difference|, +inf when a value is not finite
+void launch_audit_compare(hipStream_t st, const float* prune, const float* rank, const int32_t* cu, int n_seqs, int total,
+                          const int32_t* rows, int n_rows, const float* sub_prune, const float* sub_rank, const int32_t* sub_cu,
+                          int n_labels, float* err);
+
 }  // namespace opl

@@ -112,6 +112,62 @@ def resolve_calibration_tolerance(calibrate: "bool | float | None") -> float:
     return DEFAULT_CALIBRATION_TOLERANCE
 
 
+AUDIT_MODES = ("off", "first", "running")
+# Tokens one running audit may re-run on the reference set.  A forward of up to 16 k tokens sits at the 0.68 - 0.72 ms launch
+# floor on xsmall (profiles/r06_small_request.txt), so half of that is priced like the smallest forward -- ON THE CHOSEN SET: what
+# the reference set costs at this size has not been measured.
+DEFAULT_AUDIT_TOKENS = 8192
+MIN_AUDIT_TOKENS = 64  # batches below this are not audited (first-batch audit and running audit alike)
+
+
+def resolve_audit_mode(audit: "str | bool | None") -> str:
+    """``"off" | "first" | "running"``; ``False`` / ``True`` = ``"off"`` / ``"first"``; ``None`` = ``OPEN_PROVENCE_AUDIT``
+    (``0 / off / false / no`` -> ``"off"``, ``running`` -> ``"running"``, anything else or unset -> ``"first"``)."""
+
+    if isinstance(audit, (bool, np.bool_)):
+        return "first" if audit else "off"
+    if audit is None:
+        env = os.environ.get("OPEN_PROVENCE_AUDIT", "1").strip().lower()
+        return "off" if env in ("0", "off", "false", "no") else "running" if env == "running" else "first"
+    mode = str(audit).strip().lower()
+    if mode not in AUDIT_MODES:
+        raise ValueError(f"audit must be one of {AUDIT_MODES}, got {audit!r}")
+    return mode
+
+
+def coverage_counts(ids: np.ndarray, cu_seqlens: np.ndarray, covered: np.ndarray) -> np.ndarray:
+    """Per row of a packed batch, the positions whose token id is not in ``covered`` (bool ``[vocab]``): what
+    ``op_coverage_scan`` writes to ``row_novel_dev``.  Duplicates count once per position; an id outside the table is novel."""
+
+    ids = np.asarray(ids).astype(np.int64, copy=False)
+    inside = (ids >= 0) & (ids < covered.shape[0])
+    novel = np.ones(ids.shape[0], dtype=bool)
+    novel[inside] = ~covered[ids[inside]]
+    csum = np.concatenate(([0], np.cumsum(novel, dtype=np.int64)))
+    cu = np.asarray(cu_seqlens, dtype=np.int64)
+    return (csum[cu[1:]] - csum[cu[:-1]]).astype(np.int32)
+
+
+def select_audit_rows(row_novel: "Sequence[int]", lengths: "Sequence[int]", budget: int, longest: "int | None" = None) -> list[int]:
+    """The rows one running audit re-runs: ``longest`` first (the index of the batch's longest row, given when the length
+    trigger fired), then by (novel positions descending, length descending, index ascending) until the next row would take
+    the sub-batch past ``budget`` tokens.  At least one row is always taken, whatever its length; no rows give ``[]``."""
+
+    n = len(row_novel)
+    if n == 0:
+        return []
+    order = sorted(range(n), key=lambda i: (-int(row_novel[i]), -int(lengths[i]), i))
+    if longest is not None:
+        order = [int(longest)] + [i for i in order if i != int(longest)]
+    picked, tokens = [], 0
+    for i in order:
+        if picked and tokens + int(lengths[i]) > int(budget):
+            break
+        picked.append(i)
+        tokens += int(lengths[i])
+    return picked
+
+
 def require_gpu(device: torch.device | str | int | None = None) -> torch.device:
     """Resolve a HIP device or fail loudly (the product has no CPU path)."""
 
@@ -142,7 +198,19 @@ class HipEncoder:
         chunk_rows: int | None = None,
         prune_pre_final_norm: bool = False,
         flags: int | None = None,
+        audit: "str | bool | None" = None,
+        audit_every: int = 0,
+        audit_tokens: int = DEFAULT_AUDIT_TOKENS,
     ) -> None:
+        """``audit`` / ``audit_every`` / ``audit_tokens``: how a kernel set chosen by :meth:`calibrate` is re-checked on real
+        batches -- ``"first"`` (default; ``None`` reads ``OPEN_PROVENCE_AUDIT``): once, on the first real batch
+        (:meth:`_audit_first_batch`); ``"running"``: also later, see :meth:`_maybe_audit`; ``"off"``: never."""
+
+        self.audit_mode = resolve_audit_mode(audit)
+        self.audit_every = int(audit_every)
+        self.audit_tokens = int(audit_tokens)
+        if self.audit_every < 0 or self.audit_tokens < 1:
+            raise ValueError("audit_every must be >= 0 and audit_tokens >= 1")
         precision_code, terms = parse_precision(precision)
         self.lib = _lib.load_library()
         self.device = require_gpu(device)
@@ -243,6 +311,7 @@ class HipEncoder:
         _lib.check(self.lib, self._handle, self.lib.op_select_kernel_set(self._handle, int(_lib.OP_KS_AUTO)), "op_select_kernel_set(auto)")
         self.__dict__["_f8_active"] = None
         self.__dict__["_audit_pending"] = False
+        self._reset_coverage(running=False)
         self.calibration = None
         pinned = kernel_set or os.environ.get("OPEN_PROVENCE_KERNEL_SET")
         if pinned:
@@ -256,18 +325,24 @@ class HipEncoder:
         """Pin the kernel set by its :meth:`effective_policy` name (``None`` / ``"auto"``: the default selection).  A set with
         fewer product terms than the checkpoint carries is an approximation: :meth:`calibrate` is what measures one."""
 
+        self._select_kernel_set(name)
+        self.__dict__["_audit_pending"] = False  # (a pinned set is the caller's decision: nothing to audit)
+        self._reset_coverage(running=False)
+
+    def _select_kernel_set(self, name: "str | None") -> None:
+        """``op_select_kernel_set`` alone: the audits' detour through the reference set leaves the audit state where it is."""
+
         number = _lib.OP_KS_AUTO if name in (None, "auto") else _lib.KERNEL_SET_IDS.get(str(name))
         if number is None:
             raise ValueError(f"unknown kernel set {name!r}; expected one of {sorted(_lib.KERNEL_SET_IDS)} or 'auto'")
         _lib.check(self.lib, self._handle, self.lib.op_select_kernel_set(self._handle, int(number)), f"op_select_kernel_set({name})")
         self.__dict__["_f8_active"] = None
-        self.__dict__["_audit_pending"] = False  # (a pinned set is the caller's decision: nothing to audit)
 
     def _repin_calibrated(self, chosen: str) -> None:
         """Pin the calibrated set again after a detour through another one (the audits run the reference set in between):
         ``op_select_kernel_set`` means the whole depth, so the layer mask of sets 8 / 9 is pinned again behind it."""
 
-        self.select_kernel_set(chosen)
+        self._select_kernel_set(chosen)
         layers = (self.calibration or {}).get("mlp_correction_layers")
         if layers is not None and chosen in ("f16+mlp-f16-f8-w", "f16+mlp-f16-f8") and chosen == (self.calibration or {}).get("chosen_set"):
             mask = sum(1 << int(li) for li in layers)
@@ -326,9 +401,13 @@ class HipEncoder:
             self.calibration["mlp_correction_layers"] = [li for li in range(self.dims.num_layers) if (mask >> li) & 1]
             self.calibration["mlp_correction_err"] = float(report.mlp_layers_err)
         # a set chosen on SYNTHETIC token ids is audited on the first real batch (_audit_first_batch); the caller's own rows
-        # are real inputs already.  OPEN_PROVENCE_AUDIT=0 switches the audit off.
-        self.__dict__["_audit_pending"] = (rows is None and self.calibration["chosen_set"] != self.calibration["default_set"]
-                                           and os.environ.get("OPEN_PROVENCE_AUDIT", "1").strip().lower() not in ("0", "off", "false", "no"))
+        # are real inputs already.  audit="off" / OPEN_PROVENCE_AUDIT=0 switches the audit off; audit="running" keeps auditing.
+        mode = getattr(self, "audit_mode", None) or resolve_audit_mode(None)
+        cheaper = self.calibration["chosen_set"] != self.calibration["default_set"]
+        self.__dict__["_audit_pending"] = rows is None and cheaper and mode != "off"
+        self._reset_coverage(running=(mode == "running" and cheaper and self.calibration["reference_set"] in _lib.KERNEL_SET_IDS
+                                      and self.calibration["reference_set"] != self.calibration["chosen_set"]
+                                      and hasattr(self.lib, "op_coverage_scan")))
         return self.calibration
 
     def effective_policy(self) -> dict:
@@ -383,6 +462,7 @@ class HipEncoder:
                 self.calibration["chosen_set"] = self.effective_policy()["kernel_set"]
                 self.calibration["fallback"] = "fp16 range guard"
             self.__dict__["_audit_pending"] = False
+            self._reset_coverage(running=False)
 
             self.fallbacks = int(getattr(self, "fallbacks", 0)) + 1  # reported by process() (timing / performance_trace)
 
@@ -396,18 +476,18 @@ class HipEncoder:
             )
         return bool(changed.value)
 
-    def forward_packed_checked(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None):
+    def forward_packed_checked(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None, ids_host=None):
         """``forward_packed`` + the range guard: on kernel sets 3 / 4 the outputs are tested for NaN / Inf (one device
         reduction, one synchronisation) and a non-finite batch is repeated on the (hi, lo) bf16 sets.  On those sets
         nothing is tested: whatever comes out is what the reference's arithmetic gives.  With a ``hidden`` request the
         result is ``(prune, rank, hidden_states)``, the states of the forward whose logits are returned."""
 
-        out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden)
+        out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden, ids_host=ids_host)
         if self.f8_active():
             prune, rank = out[0], out[1]
             ok = torch.isfinite(rank).all() & torch.isfinite(prune).all()
             if not bool(ok.item()) and self.fall_back_from_f8("forward"):
-                out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden)
+                out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden, ids_host=ids_host)
         return out
 
     # -- forward ---------------------------------------------------------------------------------
@@ -454,15 +534,18 @@ class HipEncoder:
         max_seqlen: int,
         keep_prob: torch.Tensor | None = None,
         hidden: "HiddenRequest | None" = None,
+        ids_host: "np.ndarray | None" = None,
     ) -> tuple[torch.Tensor, ...]:
         """``ids[T]`` / ``cu_seqlens[B+1]`` int32 on this device -> (prune_logits[T, 2], rank_logits[B, nl]) fp32.
         ``keep_prob`` (optional, fp32 ``[T]`` on this device) additionally receives
         ``softmax(prune_logits, -1)[:, 1]``, evaluated in the head kernel.  ``hidden`` (a :class:`HiddenRequest`): the
         result is ``(prune, rank, hidden_states)``, the selected entries written by the same kernels in one device buffer
         (packed ``[n_sel, T, H]`` or padded ``[n_sel, B, pad_width, H]``, zeros at padding); the logits are bit-identical
-        to those of the same forward without the request.
+        to those of the same forward without the request.  ``ids_host`` (optional): the host copy of ``ids`` the caller
+        already holds (what it handed to :meth:`check_ids`); the running audit decides coverage on it without touching the
+        device (:meth:`_maybe_audit`).
 
-        Asynchronous on the current torch stream of ``self.device``."""
+        Asynchronous on the current torch stream of ``self.device`` (a forward that is audited synchronises it once)."""
 
         total, n_seqs = self._check_packed_inputs(ids, cu_seqlens, keep_prob)
         cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
@@ -486,7 +569,7 @@ class HipEncoder:
                                  prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None,
                                  ws, stream, req[1] if req is not None else None)
             self._maybe_audit(ids, cu_seqlens, cu_host, n_seqs, total, int(max_seqlen), prune, rank, keep_prob, ws, stream,
-                              req[1] if req is not None else None)
+                              req[1] if req is not None else None, ids_host=ids_host, running=True)
         return (prune, rank) if req is None else (prune, rank, req[0])
 
     def _hidden_request(self, hidden: "HiddenRequest", n_seqs: int, total: int, max_seqlen: int):
@@ -537,7 +620,7 @@ class HipEncoder:
             return None
         ids_np, cu_np, max_len = pack_rows(rows)
         total, n_seqs = int(cu_np[-1]), len(cu_np) - 1
-        if total < 64:
+        if total < MIN_AUDIT_TOKENS:
             return None
         self.check_ids(ids_np)
         ids = torch.from_numpy(ids_np).to(self.device)
@@ -549,10 +632,8 @@ class HipEncoder:
             return None
         outs = {}
         outs[chosen] = self.forward_packed(ids, cu, cu_np, max_len)  # (what is pinned now: the calibrated set, its layer mask included)
-        _lib.check(self.lib, self._handle, self.lib.op_select_kernel_set(self._handle, int(_lib.KERNEL_SET_IDS[reference])), "op_select_kernel_set")
-        outs[reference] = self.forward_packed(ids, cu, cu_np, max_len)
-        self._repin_calibrated(chosen)
-        self.__dict__["_f8_active"] = None
+        with self._reference_detour(chosen, reference):
+            outs[reference] = self.forward_packed(ids, cu, cu_np, max_len)
         err = float(torch.maximum((outs[chosen][0] - outs[reference][0]).abs().max(), (outs[chosen][1] - outs[reference][1]).abs().max()).item())
         bound = float(cal.get("tolerance", DEFAULT_CALIBRATION_TOLERANCE)) * float(getattr(self, "audit_factor", 3.0))
         passed = err == err and err <= bound
@@ -575,53 +656,221 @@ class HipEncoder:
                           RuntimeWarning, stacklevel=3)
         return after
 
-    def _maybe_audit(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req=None) -> None:
-        """The first-real-batch audit of a synthetically calibrated kernel set, from EITHER forward entry point
-        (``forward_packed`` / ``forward_packed_on``).  Skipped -- and left pending -- for batches under 64 tokens, while hidden
-        states are captured (the debug hook; a per-call request is audited like any batch), and while the stream is being
-        captured into a hipGraph (the audit synchronises and switches the handle's kernel set in the middle of the forward)."""
+    # -- the running audit's state: which ids audited rows have held, on the host and (op_coverage_*) on the device ---------
+    def _reset_coverage(self, running: bool) -> None:
+        """Forget what was audited, on the host and in the handle (a new arithmetic has seen nothing), and switch the running
+        audit on or off."""
 
-        if not self.__dict__.get("_audit_pending") or total < 64 or self._capture is not None:
+        self.__dict__["_running_on"] = bool(running)
+        self.__dict__["_cov_mirror"] = None  # bool [vocab], allocated by the first audit
+        self.__dict__["_cov_max_len"] = 0
+        self.__dict__["_since_audit"] = 0
+        if hasattr(self.lib, "op_coverage_reset") and getattr(self, "_handle", None):
+            self.lib.op_coverage_reset(self._handle)
+
+    @contextmanager
+    def _reference_detour(self, chosen: str, reference: str) -> Iterator[None]:
+        """Run what is inside on the calibration's ``reference`` kernel set, then pin ``chosen`` again -- whatever happens in
+        between.  Per-kernel profiling is suspended (the audit's launches are not the caller's workload).  The running
+        audit's coverage stays as it is on both sides: the handle's belongs to the arithmetic it was collected under and is
+        looked at again only once ``chosen`` is back."""
+
+        profiling = bool(self.__dict__.get("_profiling"))
+        if profiling:
+            self.lib.op_profile_enable(self._handle, 0)
+        self._select_kernel_set(reference)
+        try:
+            yield
+        finally:
+            self._repin_calibrated(chosen)
+            if profiling:
+                self.lib.op_profile_enable(self._handle, 1)
+
+    def _commit_coverage(self, ids: torch.Tensor, cu: torch.Tensor, rows_dev: torch.Tensor, n_rows: int) -> None:
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        code = self.lib.op_coverage_commit(self._handle, ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(cu.data_ptr()),
+                                           int(cu.numel()) - 1, int(ids.numel()), ctypes.c_void_p(rows_dev.data_ptr()), int(n_rows),
+                                           ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_coverage_commit")
+
+    def _commit_audited(self, sub_ids_host: np.ndarray, sub_lengths: np.ndarray, sub_ids: torch.Tensor, sub_cu: torch.Tensor) -> None:
+        """An audit passed: its rows' ids join the coverage and the longest audited length rises, in the host mirror and in
+        the handle's bitmap, both from the sub-batch's ids."""
+
+        mirror = self.__dict__.get("_cov_mirror")
+        if mirror is None:
+            mirror = self.__dict__["_cov_mirror"] = np.zeros(self.dims.vocab_size, dtype=bool)
+        mirror[np.asarray(sub_ids_host, dtype=np.int64)] = True
+        if len(sub_lengths):
+            self.__dict__["_cov_max_len"] = max(int(self.__dict__.get("_cov_max_len") or 0), int(np.max(sub_lengths)))
+        n_rows = int(sub_cu.numel()) - 1
+        self._commit_coverage(sub_ids, sub_cu, torch.arange(n_rows, dtype=torch.int32, device=self.device), n_rows)
+
+    def _record_audit(self, trigger: str, rows: "Sequence[int]", tokens: int, err: float, bound: float, passed: bool) -> None:
+        audits = (self.calibration or {}).setdefault("audits", {"count": 0, "by_trigger": {}, "last": None})
+        audits["count"] += 1
+        audits["by_trigger"][trigger] = audits["by_trigger"].get(trigger, 0) + 1
+        audits["last"] = {"rows": [int(r) for r in rows], "tokens": int(tokens), "max_abs_err": float(err), "bound": float(bound),
+                          "passed": bool(passed), "trigger": trigger}
+        self.__dict__["_since_audit"] = 0
+
+    def coverage_scan_device(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int, total: int) -> "tuple[torch.Tensor, dict]":
+        """``op_coverage_scan`` on the current stream (synchronised once): ``(row_novel[int32, n_seqs] on the device, {"novel",
+        "longest", "longest_row", "max_audited"})`` -- the coverage decision for a batch whose ids are not on the host."""
+
+        row_novel = torch.empty(max(n_seqs, 1), dtype=torch.int32, device=self.device)
+        report = _lib.OpCoverageReport()
+        report.struct_bytes = ctypes.sizeof(_lib.OpCoverageReport)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_coverage_scan(self._handle, ctypes.c_void_p(ids.data_ptr()) if total else None, ctypes.c_void_p(cu_seqlens.data_ptr()),
+                                             int(n_seqs), int(total), ctypes.c_void_p(row_novel.data_ptr()), ctypes.byref(report),
+                                             ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_coverage_scan")
+        return row_novel[:n_seqs], {"novel": int(report.novel_tokens), "longest": int(report.longest_row_tokens),
+                                    "longest_row": int(report.longest_row), "max_audited": int(report.max_audited_tokens)}
+
+    def _maybe_audit(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req=None,
+                     ids_host=None, running=False) -> None:
+        """The audits of a calibrated kernel set, from EITHER forward entry point (``forward_packed`` / ``forward_packed_on``).
+
+        The first-real-batch audit of a synthetically calibrated set (modes ``"first"`` and ``"running"``) is skipped -- and left
+        pending -- for batches under 64 tokens, while hidden states are captured (the debug hook; a per-call request is
+        audited like any batch), and while the stream is being captured into a hipGraph (the audit synchronises and switches
+        the handle's kernel set in the middle of the forward).
+
+        The RUNNING audit (mode ``"running"``, a calibrated set that is not the default one) re-checks later forwards when a
+        trigger fires: ``audit_every`` forwards have passed since the last audit (0 = never), or the batch holds positions
+        whose token id was in no audited row so far, or a row longer than any audited row (``"coverage"``).  Coverage is
+        decided where the ids are: on ``ids_host`` in numpy against a host mirror of the handle's bitmap -- a forward that
+        does not audit then synchronises nothing -- or, without it, by ``op_coverage_scan`` (one small kernel and one
+        synchronisation per forward).  An audit re-runs up to ``audit_tokens`` tokens of the batch (:func:`select_audit_rows`)
+        on the reference set and compares on the device (:meth:`_running_audit`).  It is skipped -- the forward counts
+        towards ``audit_every`` all the same -- for batches under 64 tokens, under a debug hidden capture, on a capturing
+        stream, from ``forward_packed_on`` (the pipelined path), and on an encoder with ``audit_collective`` set: a process
+        group keeps its collective first-batch audit, and a collective running audit is future work."""
+
+        pending = bool(self.__dict__.get("_audit_pending"))
+        running = bool(running and self.__dict__.get("_running_on"))
+        if not pending and not running:
+            return
+        if running:
+            self.__dict__["_since_audit"] = int(self.__dict__.get("_since_audit") or 0) + 1
+        if total < MIN_AUDIT_TOKENS or self._capture is not None:
             return
         if getattr(self, "audit_collective", False):  # under a process group the ranks audit TOGETHER (sharding.collective_audit)
             return
         if torch.cuda.is_current_stream_capturing():
             return
-        self._audit_first_batch(ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req)
+        if pending:
+            verdict = self._audit_first_batch(ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req)
+            if running and verdict is not None:
+                # in running mode the first batch is the first running audit too: every row of it was just audited
+                first = (self.calibration or {}).get("audit", {})
+                self._record_audit("coverage", range(n_seqs), total, first.get("max_abs_err", float("nan")), first.get("bound", 0.0), verdict)
+                if verdict:
+                    self._commit_audited(ids_host if ids_host is not None else ids.cpu().numpy(), np.diff(cu_host), ids, cu_seqlens)
+            return
+        lengths = np.diff(cu_host)
+        longest = int(lengths.argmax())
+        if ids_host is not None:
+            mirror = self.__dict__.get("_cov_mirror")
+            if mirror is None:
+                mirror = self.__dict__["_cov_mirror"] = np.zeros(self.dims.vocab_size, dtype=bool)
+            too_long = int(lengths[longest]) > int(self.__dict__.get("_cov_max_len") or 0)
+            row_novel = None
+            if too_long or not mirror[ids_host].all():
+                row_novel = coverage_counts(ids_host, cu_host, mirror)
+        else:
+            novel_dev, report = self.coverage_scan_device(ids, cu_seqlens, n_seqs, total)
+            too_long = report["longest"] > report["max_audited"]
+            row_novel = novel_dev.cpu().numpy() if (too_long or report["novel"] > 0) else None
+        trigger = "coverage" if row_novel is not None else None
+        if trigger is None and self.audit_every > 0 and self.__dict__["_since_audit"] >= self.audit_every:
+            trigger, row_novel = "every_n", np.zeros(n_seqs, dtype=np.int32)
+        if trigger is None:
+            return
+        rows = select_audit_rows(row_novel, lengths, self.audit_tokens, longest=longest if too_long else None)
+        self._running_audit(trigger, rows, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream,
+                            hidden_req, ids_host)
+
+    def _running_audit(self, trigger, rows, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream,
+                       hidden_req, ids_host) -> None:
+        """One running audit: ``rows`` of the batch gathered into a sub-batch on the device (``op_gather_rows``), run on the
+        calibration's reference set, compared on the device with the logits the chosen set just wrote for those rows
+        (``op_audit_compare``; per-row outputs do not depend on the batch's composition, so the comparison is exact), one
+        float read back.  Within ``audit_factor`` x the calibration tolerance: the rows' ids join the coverage.  Beyond it,
+        or non-finite: what a failed first-batch audit does -- :meth:`revert_to_default`, one ``RuntimeWarning``, and THIS
+        batch recomputed there (with the caller's hidden-state request) before it is returned."""
+
+        cal = self.calibration or {}
+        chosen, reference = cal.get("chosen_set"), cal.get("reference_set")
+        lengths = np.diff(cu_host)
+        sub_lengths = lengths[rows].astype(np.int32)
+        sub_cu_host = np.concatenate(([0], np.cumsum(sub_lengths))).astype(np.int32)
+        n_sub, sub_total, sub_max = len(rows), int(sub_cu_host[-1]), int(sub_lengths.max())
+        rows_dev = torch.tensor(rows, dtype=torch.int32, device=self.device)
+        sub_ids = torch.empty(sub_total, dtype=torch.int32, device=self.device)
+        sub_cu = torch.empty(n_sub + 1, dtype=torch.int32, device=self.device)
+        vp = ctypes.c_void_p
+        code = self.lib.op_gather_rows(self._handle, vp(ids.data_ptr()), vp(cu_seqlens.data_ptr()), n_seqs, total, vp(rows_dev.data_ptr()),
+                                       n_sub, vp(sub_ids.data_ptr()), vp(sub_cu.data_ptr()), vp(stream))
+        _lib.check(self.lib, self._handle, code, "op_gather_rows")
+        p_ref = torch.empty((sub_total, 2), dtype=torch.float32, device=self.device)
+        r_ref = torch.empty((n_sub, self.dims.num_labels), dtype=torch.float32, device=self.device)
+        if int(self.lib.op_workspace_bytes(self._handle, n_sub, sub_total, sub_max)) + 256 > ws.numel():
+            ws = torch.empty(int(self.lib.op_workspace_bytes(self._handle, n_sub, sub_total, sub_max)) + 256, dtype=torch.uint8, device=self.device)
+        err_dev = torch.empty(1, dtype=torch.float32, device=self.device)
+        with self._reference_detour(chosen, reference):
+            self._forward_native(sub_ids.data_ptr(), sub_cu.data_ptr(), sub_cu_host, n_sub, sub_total, sub_max,
+                                 p_ref.data_ptr(), r_ref.data_ptr(), None, ws, stream)
+        code = self.lib.op_audit_compare(self._handle, vp(prune.data_ptr()), vp(rank.data_ptr()), vp(cu_seqlens.data_ptr()), n_seqs, total,
+                                         vp(rows_dev.data_ptr()), n_sub, vp(p_ref.data_ptr()), vp(r_ref.data_ptr()), vp(sub_cu.data_ptr()),
+                                         vp(err_dev.data_ptr()), vp(stream))
+        _lib.check(self.lib, self._handle, code, "op_audit_compare")
+        err = float(err_dev.item())  # (synchronises: the one float an audit reads back)
+        bound = float(cal.get("tolerance", DEFAULT_CALIBRATION_TOLERANCE)) * float(getattr(self, "audit_factor", 3.0))
+        passed = err <= bound  # (+inf -- a non-finite logit on either side -- fails)
+        self._record_audit(trigger, rows, sub_total, err, bound, passed)
+        if passed:
+            if ids_host is not None:
+                sub_ids_host = np.concatenate([ids_host[cu_host[r]: cu_host[r + 1]] for r in rows])
+            else:
+                sub_ids_host = sub_ids.cpu().numpy()
+            self._commit_audited(sub_ids_host, sub_lengths, sub_ids, sub_cu)
+            return
+        self.revert_to_default(f"running audit ({trigger}): {err:.2e} from the {reference!r} kernels on rows {list(rows)[:8]} "
+                               f"of a batch, bound {bound:.1e}")
+        self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, max_seqlen,
+                             prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None, ws, stream,
+                             hidden_req)
 
     def _audit_first_batch(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream,
-                           hidden_req=None) -> None:
+                           hidden_req=None) -> "bool | None":
         """The calibration ran on synthetic token ids; the FIRST real batch a calibrated model sees is its audit: the same
         batch once more through the reference kernel set of the calibration, max |logit difference| against what the chosen
         set just returned.  Within ``audit_factor`` (3) x the calibration tolerance -- 3e-4, still 3 x inside the path's bar;
         the forward fuzz puts the worst row of other inputs at <= 2.7 x a calibration batch's maximum -- the choice stands
         (one synchronisation, two extra forwards, once per load).  Beyond it, or non-finite: the model goes back to the
         default selection of ``op_weights_ready`` for good, warns, and THIS batch is recomputed there before it is returned
-        (with the caller's hidden-state request, ``hidden_req``: the reference forward of the audit itself writes none)."""
+        (with the caller's hidden-state request, ``hidden_req``: the reference forward of the audit itself writes none).
+        Returns the verdict (None: there was nothing to audit)."""
 
         self.__dict__["_audit_pending"] = False
         cal = self.calibration or {}
         chosen, reference = cal.get("chosen_set"), cal.get("reference_set")
         if not chosen or chosen == cal.get("default_set") or reference not in _lib.KERNEL_SET_IDS:
-            return
+            return None
         p_ref, r_ref = torch.empty_like(prune), torch.empty_like(rank)
-        profiling = bool(self.__dict__.get("_profiling"))
-        if profiling:  # the audit's launches are not the caller's workload: keep them out of a per-kernel profile
-            self.lib.op_profile_enable(self._handle, 0)
-        self.select_kernel_set(reference)
-        try:
+        with self._reference_detour(chosen, reference):
             self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, max_seqlen,
                                  p_ref.data_ptr(), r_ref.data_ptr(), None, ws, stream)
-        finally:
-            self._repin_calibrated(chosen)
-            if profiling:
-                self.lib.op_profile_enable(self._handle, 1)
         err = float(torch.maximum((prune - p_ref).abs().max(), (rank - r_ref).abs().max()).item())  # (synchronises)
         bound = float(cal.get("tolerance", DEFAULT_CALIBRATION_TOLERANCE)) * float(getattr(self, "audit_factor", 3.0))
         passed = err == err and err <= bound  # (NaN fails)
         cal["audit"] = {"tokens": int(total), "rows": int(n_seqs), "max_abs_err": err, "bound": bound, "passed": bool(passed)}
         if passed:
-            return
+            return True
         import warnings
 
         self.select_kernel_set("auto")
@@ -635,6 +884,7 @@ class HipEncoder:
         self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, max_seqlen,
                              prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None, ws, stream,
                              hidden_req)
+        return False
 
     def _check_packed_inputs(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, keep_prob: torch.Tensor | None) -> tuple[int, int]:
         """Shared argument checks of forward_packed / forward_packed_on -> (total_tokens, n_seqs)."""
@@ -885,7 +1135,7 @@ class HipEncoder:
         self.check_ids(ids_np)
         ids = torch.from_numpy(ids_np).to(self.device, non_blocking=False)
         cu = torch.from_numpy(cu_np).to(self.device, non_blocking=False)
-        prune, rank = self.forward_packed(ids, cu, cu_np, max_len)
+        prune, rank = self.forward_packed(ids, cu, cu_np, max_len, ids_host=ids_np)
         return prune, rank, cu_np
 
     # -- test / measurement hooks ------------------------------------------------------------------

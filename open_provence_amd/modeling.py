@@ -219,9 +219,13 @@ class OpenProvenceModel:
         calibrate: "bool | float | None" = None,
         calibration_rows: "Sequence[Sequence[int]] | None" = None,
         forward_token_budget: int | None = None,
+        audit: "str | bool | None" = None,
+        audit_every: int = 0,
+        audit_tokens: int | None = None,
     ) -> None:
         # kernel_set / calibrate / calibration_rows: how the arithmetic is chosen from the loaded weights
-        # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615)
+        # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615);
+        # audit / audit_every / audit_tokens: how a calibrated choice is re-checked on real batches (HipEncoder._maybe_audit)
         self._kernel_set_request = kernel_set
         self._calibrate_request = calibrate
         self._calibration_rows = calibration_rows
@@ -247,6 +251,7 @@ class OpenProvenceModel:
         self.encoder = HipEncoder(
             self.dims, device=self._runtime_device, precision=self.precision, chunk_rows=chunk_rows,
             prune_pre_final_norm=self.pruning_hidden_state == "pre_final_norm",
+            audit=audit, audit_every=audit_every, **({} if audit_tokens is None else {"audit_tokens": audit_tokens}),
         )
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -521,6 +526,9 @@ class OpenProvenceModel:
             calibrate=kwargs.pop("calibrate", None),
             calibration_rows=kwargs.pop("calibration_rows", None),
             forward_token_budget=kwargs.pop("forward_token_budget", None),
+            audit=kwargs.pop("audit", None),
+            audit_every=kwargs.pop("audit_every", 0),
+            audit_tokens=kwargs.pop("audit_tokens", None),
         )
         if max_length is not None:
             model.max_length = int(max_length)
@@ -575,6 +583,7 @@ class OpenProvenceModel:
         # the host as before.
         on_device = (dev.type == "cuda" and isinstance(input_ids, torch.Tensor) and input_ids.device == dev
                      and (attention_mask is None or (isinstance(attention_mask, torch.Tensor) and attention_mask.device == dev)))
+        ids_np = None  # (a device-resident batch has no host copy: the running audit scans it on the device)
         if on_device:
             ids, cu, cu_np, max_len = self.encoder.pack_padded_device(input_ids, attention_mask)
         else:
@@ -587,12 +596,12 @@ class OpenProvenceModel:
         hidden_states = None
         if output_hidden_states:
             prune, rank, hidden = self.encoder.forward_packed_checked(
-                ids, cu, cu_np, max_len, hidden=HiddenRequest(dtype=torch.float32, pad_width=width)
+                ids, cu, cu_np, max_len, hidden=HiddenRequest(dtype=torch.float32, pad_width=width), ids_host=ids_np
             )
             # ([N + 1, B, L, H]; with L = 0 the request is packed and empty: the same shape, no data)
             hidden_states = tuple(hidden.reshape(hidden.shape[0], int(input_ids.shape[0]), width, hidden.shape[-1]).unbind(0))
         else:
-            prune, rank = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len)
+            prune, rank = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len, ids_host=ids_np)
         if on_device:
             pruning_logits = self.encoder.unpack_padded_device(prune, cu, int(input_ids.shape[0]), width)
         else:
@@ -902,7 +911,7 @@ class OpenProvenceModel:
         if seg_counts is not None:
             np.copyto(pool["seg_np"][: 2 * n_seg], seg_flat)
             seg_dev = pool["seg"][: 2 * n_seg].to(dev, non_blocking=True).view(n_seg, 2)
-        _, rank_dev = self.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev)
+        _, rank_dev = self.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev, ids_host=ids_np)
         self._count_forward(n_rows, total)
         if seg_counts is not None:
             means_dev = self.encoder.segment_means(keep_dev, seg_dev)

@@ -222,6 +222,45 @@ def trained_like_state_dict(dims: EncoderDims, seed: int, *, row_sigma: float = 
         out[name] = t.contiguous()
     return out
 
+OUTLIER_TOKEN, OUTLIER_CHANNEL, OUTLIER_SEED = 450, 5, 3
+# Found by a search on the float64 model of the kernel sets (tests/arith_model.py, "f16" against "bf16x3"; hidden 256, 4 heads,
+# 3 layers, vocab 500) over 1 .. 1024: at 64 the benign rows of outlier_token_rows differ by 5.1e-5 (within the 1e-4
+# calibration tolerance), a 70-token row holding the token by 2.6e-3 (9 x the 3e-4 audit bound) with max |hidden| = 44, far inside
+# fp16's range; 32 leaves the row at the bound's edge, 256 takes the benign rows past the tolerance.
+# tests/test_running_audit_host.py asserts all three on the CPU.
+OUTLIER_SCALE = 64.0
+
+
+def outlier_token_state_dict(dims: EncoderDims, seed: int = OUTLIER_SEED, *, token: int = OUTLIER_TOKEN, channel: int = OUTLIER_CHANNEL,
+                             scale: float = OUTLIER_SCALE) -> dict[str, torch.Tensor]:
+    """:func:`refinit_state_dict` with ONE token that single-pass fp16 operands get wrong while every other token stays
+    benign -- the input a calibration on other ids never sees (the running audit's fixture).  The embedding of ``token`` is
+    one-hot in ``channel``, which is zero in every other embedding row, and the columns ``channel`` of layer 0's ``Wqkv`` and
+    ``Wi`` are scaled by ``scale``: after the embedding LayerNorm the token carries sqrt(H) in that channel, layer 0 turns
+    it into q / k / v and MLP inputs ``scale`` times the usual size, and their fp16 rounding error grows with them."""
+
+    out = {k: v.clone() for k, v in refinit_state_dict(dims, seed).items()}
+    emb = out["ranking_model.model.embeddings.tok_embeddings.weight"]
+    emb[:, channel] = 0.0
+    emb[token] = 0.0
+    emb[token, channel] = 1.0
+    for name in ("attn.Wqkv.weight", "mlp.Wi.weight"):
+        out[f"ranking_model.model.layers.0.{name}"][:, channel] *= scale
+    return out
+
+
+def outlier_token_rows(seed: int = OUTLIER_SEED, *, token: int = OUTLIER_TOKEN) -> tuple[list[list[int]], list[int]]:
+    """``(benign, outlier)`` for :func:`outlier_token_state_dict` (vocab 500): six benign rows of 3, 17, 40, 63, 64 and 130
+    tokens with ids in [4, 400), and one 70-token row of such ids that holds ``token`` once, in the middle."""
+
+    def draw(tag: int, count: int) -> list[int]:
+        return [4 + int(u * 396) for u in _unit_stream(seed, 9100 + tag, count)]
+
+    benign = [draw(i, n) for i, n in enumerate((3, 17, 40, 63, 64, 130))]
+    outlier = draw(99, 70)
+    outlier[33] = int(token)
+    return benign, outlier
+
 
 def zipf_token_rows(dims: EncoderDims, n_rows: int, seq_len: int, seed: int, *, alpha: float = 1.1) -> list[list[int]]:
     """Rows shaped like :func:`synth_pair_batch`'s ([CLS] query [SEP] context [SEP]) whose token ids follow a Zipf law over a

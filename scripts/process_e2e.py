@@ -56,7 +56,7 @@ def build_e2e_model():
 
     from open_provence_amd.config import OpenProvenceConfig
     from open_provence_amd.modeling import OpenProvenceModel
-    from open_provence_amd.synthetic import named_dims, synth_state_dict
+    from open_provence_amd.synthetic import named_dims, refinit_state_dict, synth_state_dict
 
     dims = named_dims("xsmall")
     cfg = OpenProvenceConfig(base_model_config=dims.to_base_model_config(), tokenizer_name_or_path="x",
@@ -67,7 +67,10 @@ def build_e2e_model():
         tok = build_wordpiece_tokenizer(True, legacy_methods=os.environ.get("E2E_STOCK_TOKENIZER") != "1")
     else:
         tok = CharTokenizer()
-    model = OpenProvenceModel(cfg, device="cuda", tokenizer=tok, state_dict=synth_state_dict(dims, 7))
+    # E2E_WEIGHTS=refinit: reference-initialised weights, which calibrate to kernel set "f16" -- the case the audits of a
+    # calibrated set (--audit) exist for; the O(1) default keeps the default set, where no audit ever runs
+    make_state = refinit_state_dict if os.environ.get("E2E_WEIGHTS", "synth") == "refinit" else synth_state_dict
+    model = OpenProvenceModel(cfg, device="cuda", tokenizer=tok, state_dict=make_state(dims, 7))
     model.tokenizer.model_max_length = 512
     return model
 
@@ -96,7 +99,14 @@ def main():
     ap.add_argument("--passes", type=int, default=2, help="--forward-tokens with several settings: how often the settings take turns")
     ap.add_argument("--dump-result", default=None, help="write the result of the last call of every setting (without timings) as JSON here")
     ap.add_argument("--chars-are-words", action="store_true", help="wordpiece: size the contexts in words (~tokens) instead of characters")
+    ap.add_argument("--weights", default="synth", choices=["synth", "refinit"],
+                    help="synth: O(1) worst-case weights (the default kernel set stays); refinit: reference initialisation (calibrates to 'f16')")
+    ap.add_argument("--audit", default=None, choices=["off", "first", "running"],
+                    help="audit policy of the calibrated kernel set (HipEncoder(audit=...), here through OPEN_PROVENCE_AUDIT)")
     args = ap.parse_args()
+    os.environ["E2E_WEIGHTS"] = args.weights
+    if args.audit is not None:
+        os.environ["OPEN_PROVENCE_AUDIT"] = {"off": "0", "first": "1", "running": "running"}[args.audit]
 
     os.environ["E2E_TOKENIZER"] = args.tokenizer
     if args.stock_tokenizer:
@@ -138,9 +148,15 @@ def main():
             raise SystemExit("--forward-tokens with several settings: in-process, or the replicas process() starts by itself")
         compare_budgets(args, target, call, [(b, budget_value(b)) for b in budgets])
         return
+    def audits_so_far():
+        encoder = getattr(target, "encoder", None)
+        return int(((getattr(encoder, "calibration", None) or {}).get("audits") or {}).get("count", 0))
+
     call()
     torch.cuda.synchronize()
+    audits_warm = audits_so_far()
     best = None
+    inference_all = []
     for _ in range(args.reps):
         r0 = resource.getrusage(resource.RUSAGE_SELF)
         t0 = time.perf_counter()
@@ -151,10 +167,15 @@ def main():
         usage = {"user_s": round(r1.ru_utime - r0.ru_utime, 4), "sys_s": round(r1.ru_stime - r0.ru_stime, 4),
                  "minor_faults": r1.ru_minflt - r0.ru_minflt, "vol_ctx_switches": r1.ru_nvcsw - r0.ru_nvcsw,
                  "invol_ctx_switches": r1.ru_nivcsw - r0.ru_nivcsw}
+        inference_all.append(round(float(out["timing"]["inference_seconds"]), 5))
         if best is None or dt < best[0]:
             best = (dt, out["timing"], usage)
     dt, timing, usage = best
-    print(json.dumps({"contexts": args.contexts, "chars": args.chars, "tokenizer": args.tokenizer, "workers": args.workers, "front_end_processes": args.front_end, "host_replicas": args.host_front_end, "wall_s": dt, "contexts_per_s": args.contexts / dt, "rusage": usage, "owner_trace": getattr(front, "last_trace", None),
+    encoder = getattr(target, "encoder", None)
+    audit_info = {} if encoder is None else {"weights": args.weights, "audit": encoder.audit_mode, "kernel_set": encoder.effective_policy()["kernel_set"],
+                                             "audits_in_warm_up": audits_warm, "audits_in_timed_calls": audits_so_far() - audits_warm,
+                                             "inference_seconds_per_call": inference_all}
+    print(json.dumps({**audit_info, "contexts": args.contexts, "chars": args.chars, "tokenizer": args.tokenizer, "workers": args.workers, "front_end_processes": args.front_end, "host_replicas": args.host_front_end, "wall_s": dt, "contexts_per_s": args.contexts / dt, "rusage": usage, "owner_trace": getattr(front, "last_trace", None),
                       "timing": {k: round(float(v), 5) for k, v in timing.items()}}))
     if args.profile:
         pr = cProfile.Profile()
