@@ -261,6 +261,23 @@ def attention(q, k, v, vis, arith: Arith, layer: int, tile: int):
     return contract(p, v, spv) / l
 
 
+def rank_logits(state: Mapping[str, torch.Tensor], dims, last_rows: Sequence[torch.Tensor], pool=None) -> torch.Tensor:
+    """The ranking head on the final_norm output of every row ([len, H] each): [B, num_labels]; an empty row's logits are
+    defined as zeros.  ``pool``: mutation hook, rows [len, H] -> the pooled vector [H] (None = the model's pooling)."""
+
+    pre = "ranking_model." if any(k.startswith("ranking_model.") for k in state) else ""
+    W = lambda n: state[pre + n].to(torch.float64)  # noqa: E731
+    if pool is None:
+        pool = (lambda r: r.mean(dim=0)) if dims.classifier_pooling == "mean" else (lambda r: r[0])
+    rank = torch.zeros(len(last_rows), dims.num_labels, dtype=torch.float64)
+    for b, rows in enumerate(last_rows):
+        if rows.shape[0] == 0:
+            continue
+        pooled = _layer_norm(_gelu(pool(rows.to(torch.float64)) @ W("head.dense.weight").T), W("head.norm.weight"), float(dims.norm_eps))
+        rank[b] = pooled @ W("classifier.weight").T + W("classifier.bias")
+    return rank
+
+
 @dataclass
 class ModelOutput:
     hidden: list[torch.Tensor]  # N + 1 entries, padded [B, Lmax, H] float64 (zeros beyond each row)
@@ -269,14 +286,24 @@ class ModelOutput:
     lengths: list[int]
 
 
-def forward(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int]], arith: "Arith | str" = "exact", *,
-            path: str = "row", prune_pre_final_norm: bool = False) -> ModelOutput:
-    """The forward on ragged ``rows`` of token ids (no padding enters any row's arithmetic).  Hidden entry 0 is the
-    embedding LayerNorm output, entry i the output of layer i - 1, entry N the final_norm output -- or, under
-    ``prune_pre_final_norm``, the un-normalised last layer (the pruning head's input either way, as op_hidden_request)."""
+@dataclass
+class Backbone:
+    """The encoder without its heads, packed: what :func:`heads` turns into a :class:`ModelOutput` under any pooling, label count
+    and side of final_norm (none of which enters a layer)."""
+
+    states: list[torch.Tensor]  # N entries [T, H]: the embedding LayerNorm output, then the outputs of layers 0 .. N - 2
+    x: torch.Tensor  # [T, H]: the output of the last layer, before final_norm
+    lengths: list[int]
+
+
+def backbone(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int]], arith: "Arith | str" = "exact", *,
+             path: str = "row", rope_is_global: "Sequence[bool] | None" = None) -> Backbone:
+    """The layers of :func:`forward` (its arguments)."""
 
     if isinstance(arith, str):
         arith = arith_for(arith, path)
+    if rope_is_global is not None and len(rope_is_global) != dims.num_layers:
+        raise ValueError("rope_is_global needs one flag per layer")
     pre = "ranking_model." if any(k.startswith("ranking_model.") for k in state) else ""
     W = lambda n: state[pre + n].to(torch.float64)  # noqa: E731
     H, nh = dims.hidden_size, dims.num_heads
@@ -307,7 +334,7 @@ def forward(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int
             if a == e:
                 continue
             n = e - a
-            c, s = (t[:n] for t in rope[glob])
+            c, s = (t[:n] for t in rope[glob if rope_is_global is None else bool(rope_is_global[i])])
             q, k, v = (qkv[a:e, j].transpose(0, 1) for j in range(3))  # [nh, n, hd]
             q = (q * c + _rot(q) * s) * qscale
             k = k * c + _rot(k) * s
@@ -318,20 +345,25 @@ def forward(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int
         x = x + contract(_gelu(g_in) * gate, W(p + "mlp.Wo.weight").T, arith.scheme("mlp_out", i))
         if i != dims.num_layers - 1:
             states.append(x)
-    last = _layer_norm(x, W("model.final_norm.weight"), eps)
-    states.append(x if prune_pre_final_norm else last)
+    return Backbone(states, x, lengths)
+
+
+def heads(state: Mapping[str, torch.Tensor], dims, body: Backbone, *, prune_pre_final_norm: bool = False) -> ModelOutput:
+    """final_norm, the pruning head and the ranking head of :func:`forward` on a backbone's last layer."""
+
+    pre = "ranking_model." if any(k.startswith("ranking_model.") for k in state) else ""
+    lengths, x = body.lengths, body.x
+    B, Lmax = len(lengths), max(lengths, default=0)
+    offs = [0]
+    for n in lengths:
+        offs.append(offs[-1] + n)
+    last = _layer_norm(x, state[pre + "model.final_norm.weight"].to(torch.float64), float(dims.norm_eps))
+    states = body.states + [x if prune_pre_final_norm else last]
 
     pw = state["pruning_head.classifier.weight"].to(torch.float64)
     pb = state["pruning_head.classifier.bias"].to(torch.float64)
     prune_packed = (x if prune_pre_final_norm else last) @ pw.T + pb
-    rank = torch.zeros(B, dims.num_labels, dtype=torch.float64)
-    for b in range(B):
-        a, e = offs[b], offs[b + 1]
-        if a == e:
-            continue  # an empty row's ranking logits are defined as zeros
-        pooled = last[a:e].mean(dim=0) if dims.classifier_pooling == "mean" else last[a]
-        pooled = _layer_norm(_gelu(pooled @ W("head.dense.weight").T), W("head.norm.weight"), eps)
-        rank[b] = pooled @ W("classifier.weight").T + W("classifier.bias")
+    rank = rank_logits(state, dims, [last[offs[b] : offs[b + 1]] for b in range(B)])
 
     def pad(t):
         out = torch.zeros(B, Lmax, t.shape[-1], dtype=torch.float64)
@@ -340,6 +372,19 @@ def forward(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int
         return out
 
     return ModelOutput([pad(t) for t in states], pad(prune_packed), rank, lengths)
+
+
+def forward(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int]], arith: "Arith | str" = "exact", *,
+            path: str = "row", prune_pre_final_norm: bool = False,
+            rope_is_global: "Sequence[bool] | None" = None) -> ModelOutput:
+    """The forward on ragged ``rows`` of token ids (no padding enters any row's arithmetic).  Hidden entry 0 is the
+    embedding LayerNorm output, entry i the output of layer i - 1, entry N the final_norm output -- or, under
+    ``prune_pre_final_norm``, the un-normalised last layer (the pruning head's input either way, as op_hidden_request).
+    ``rope_is_global``: mutation hook, per layer which RoPE table its q / k take (None = the layer's own type; the mask and
+    the key tiles always follow the layer's own type)."""
+
+    body = backbone(state, dims, rows, arith, path=path, rope_is_global=rope_is_global)
+    return heads(state, dims, body, prune_pre_final_norm=prune_pre_final_norm)
 
 
 # -- the statistic the conformance tests bound ------------------------------------------------------------------------------
@@ -364,6 +409,24 @@ def entries(hidden: Sequence[torch.Tensor], prune: torch.Tensor, rank: torch.Ten
 
 def model_entries(out: ModelOutput) -> dict[str, torch.Tensor]:
     return entries(out.hidden, out.prune, out.rank, out.lengths)
+
+
+def expand_entries(content: Mapping[str, torch.Tensor], lengths: Sequence[int], index: Sequence[int]) -> dict[str, torch.Tensor]:
+    """The entries of the batch whose row b is a copy of content row ``index[b]``: ``content`` holds the entries of the
+    content rows (of ``lengths``) run as one batch; no row's arithmetic depends on its neighbours, so the batch's entries
+    are the contents' token blocks (and, for the non-empty rows, ranking logits) gathered in batch order."""
+
+    lens = torch.tensor(list(lengths), dtype=torch.long)
+    idx = torch.tensor(list(index), dtype=torch.long)
+    start = torch.cumsum(lens, 0) - lens
+    n = lens[idx]
+    # token t of the batch: offset within its row + the start of that row's content
+    row_of = torch.repeat_interleave(torch.arange(len(idx)), n)
+    within = torch.arange(int(n.sum())) - (torch.cumsum(n, 0) - n)[row_of]
+    tok = start[idx][row_of] + within
+    rank_slot = torch.cumsum((lens > 0).long(), 0) - 1  # content row -> its line of the "rank" entry (empty rows are left out)
+    rank_idx = rank_slot[idx[n > 0]]
+    return {name: t[rank_idx] if name == "rank" else t[tok] for name, t in content.items()}
 
 
 def rms(t: torch.Tensor) -> float:

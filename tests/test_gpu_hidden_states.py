@@ -251,8 +251,9 @@ def test_chunked_and_ragged_batches(kernel_set):
     whole.close()
     chunked.close()
     assert sum(lengths) == 2048
-    # chunks change the launch shapes (small blocks, pair kernel), not the rows' arithmetic beyond fp32 noise
-    assert float((ha - hb).abs().max()) < 1e-3 and float((pa - pb).abs().max()) < 1e-3
+    # chunks change the launch shapes (small blocks, pair kernel), not one bit of a row's arithmetic: measured on these three sets
+    # here and on the 2 600-row batch of tests/test_kernel_set_geometry.py, which also holds the rows to the model's bound
+    assert torch.equal(ha, hb) and torch.equal(pa, pb) and torch.equal(ra, rb)
     for s in range(len(lengths)):
         assert torch.equal(ha[:, s, : lengths[s]], hp[:, cu[s] : cu[s + 1]])
         assert bool((ha[:, s, lengths[s]:] == 0).all()) and bool((hb[:, s, lengths[s]:] == 0).all())

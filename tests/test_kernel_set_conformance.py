@@ -50,9 +50,10 @@ MODELS = {
     "row320": (256, 320, 4, 3),  # intermediate not 4 x hidden: 5 x 64, an odd count in the wave-pair kernel's MLP loop
 }
 # ... and the 4-layer panel model of tests/test_kernel_set_masks.py (the layer mask of sets 8 / 9)
-SHAPES = {**MODELS, "panel512x4": (512, 2048, 8, 4)}
+# ... and the 3-layer tiled model of tests/test_kernel_set_geometry.py (its layer patterns have three letters)
+SHAPES = {**MODELS, "panel512x4": (512, 2048, 8, 4), "tiled3": (384, 192, 6, 3)}
 PATH_OF = {"row": "row", "panel512": "panel", "panel768": "panel", "tiled": "tiled", "engte": "panel", "h1024": "panel",
-           "row128": "row", "row320": "row", "panel512x4": "panel"}
+           "row128": "row", "row320": "row", "panel512x4": "panel", "tiled3": "tiled"}
 
 # What each path supports, as an explicit expectation (op_api.hip set_available): every other set must be refused.
 ROW_SETS = ["bf16x3", "bf16-weights", "bf16", "f16-f8", "f16-f8-w", "f16"]
@@ -125,15 +126,23 @@ def _print_table():
         print("[conformance]", line)
 
 
-def _dims(model: str, window: int = 128):
+def _dims(model: str, window: int = 128, *, layer_types: "str | None" = None, pooling: "str | None" = None,
+          labels: "int | None" = None):
+    """``layer_types``: one letter per layer, "G" (full attention) / "L" (sliding window), None = one global layer, then
+    sliding-window layers; ``pooling``: "cls" (None) / "mean"; ``labels``: ranking labels (None = 1)."""
+
     from open_provence_amd.config import EncoderDims
 
     H, I, nh, nl = SHAPES[model]
-    return EncoderDims.from_base_model_config(
-        dict(model_type="modernbert", vocab_size=512, hidden_size=H, intermediate_size=I, num_hidden_layers=nl,
-             num_attention_heads=nh, local_attention=window, global_attn_every_n_layers=nl, global_rope_theta=160000.0,
-             local_rope_theta=10000.0, max_position_embeddings=2048, pad_token_id=0, cls_token_id=1, sep_token_id=2),
-        num_labels=1)
+    cfg = dict(model_type="modernbert", vocab_size=512, hidden_size=H, intermediate_size=I, num_hidden_layers=nl,
+               num_attention_heads=nh, local_attention=window, global_attn_every_n_layers=nl, global_rope_theta=160000.0,
+               local_rope_theta=10000.0, max_position_embeddings=2048, pad_token_id=0, cls_token_id=1, sep_token_id=2)
+    if layer_types is not None:
+        assert len(layer_types) == nl and set(layer_types) <= {"G", "L"}, layer_types
+        cfg["layer_types"] = ["full_attention" if t == "G" else "sliding_attention" for t in layer_types]
+    if pooling is not None:
+        cfg["classifier_pooling"] = pooling
+    return EncoderDims.from_base_model_config(cfg, num_labels=1 if labels is None else labels)
 
 
 def _rows(lengths, seed=7):
@@ -149,10 +158,10 @@ def weights_for(kernel_set: str, recipe: str, damped: bool = False) -> str:
 
 
 @functools.lru_cache(maxsize=None)
-def _state(model: str, weights: str, window: int = 128):
+def _state(model: str, weights: str, window: int = 128, labels: "int | None" = None):
     from open_provence_amd.synthetic import synth_state_dict
 
-    dims = _dims(model, window)
+    dims = _dims(model, window, labels=labels)  # (of a model's dims only the shapes enter its weights)
     recipe, *marks = weights.split("-")
     assert recipe in ("o1", "peaked") and set(marks) <= {"bf16", "damped"}, weights
     state = synth_state_dict(dims, 21) if recipe == "o1" else am.peaked_state_dict(dims, 21)
@@ -172,12 +181,17 @@ def _model(model: str, weights: str, window: int, lengths: tuple, kernel_set: st
     return am.model_entries(out)
 
 
-def _encoder(model: str, weights: str, window: int, kernel_set: str, flags: int):
+def _encoder(model: str, weights: str, window: int, kernel_set: str, flags: int, *, chunk_rows: "int | None" = None,
+             prune_pre_final_norm: bool = False, dims=None):
+    """``dims``: the model's dims with another layer pattern or head (``_dims(model, window, ...)``); None = ``_dims(model, window)``."""
+
     from open_provence_amd.engine import HipEncoder
 
-    enc = HipEncoder(_dims(model, window), device="cuda:0", flags=flags)
+    dims = _dims(model, window) if dims is None else dims
+    enc = HipEncoder(dims, device="cuda:0", flags=flags, chunk_rows=chunk_rows, prune_pre_final_norm=prune_pre_final_norm)
     try:
-        enc.load_state_dict(_state(model, weights, window), calibrate=False, kernel_set=kernel_set)
+        enc.load_state_dict(_state(model, weights, window, None if dims.num_labels == 1 else dims.num_labels), calibrate=False,
+                            kernel_set=kernel_set)
         assert enc.effective_policy()["kernel_set"] == kernel_set
     except BaseException:
         enc.close()
