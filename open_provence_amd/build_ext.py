@@ -32,7 +32,7 @@ _AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gat
 
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
-    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, INCLUDE]),
+    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_sets.h", CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, INCLUDE]),
     ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"], _INTERNAL),
     ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"], _INTERNAL),
     ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"], _INTERNAL),

@@ -16,12 +16,14 @@
 
 #define OPK_PACK_KERNELS 1
 #include "op_internal.h"
+#include "op_sets.h"
 #include "opk_small.hip.h"
 #include "opk_padded.hip.h"
 #include "opk_tiled.hip.h"
 
 using namespace opk;
 using opl::Policy;
+using namespace ops;
 
 namespace {
 
@@ -62,26 +64,7 @@ const char* kProfileNames[PK_COUNT] = {"rowmap",        "embed_ln",      "layer_
 struct LayerWeights {
   float* attn_norm = nullptr;  // absent on layer 0
   float* mlp_norm = nullptr;
-  u16 *wqkv_hi = nullptr, *wqkv_lo = nullptr;
-  u16 *wo_hi = nullptr, *wo_lo = nullptr;
-  u16 *wi_hi = nullptr, *wi_lo = nullptr;
-  u16 *wo2_hi = nullptr, *wo2_lo = nullptr;
-  // row-stationary layouts (hidden <= 256): chunk-major, fragment-ordered, hi/lo planes interleaved per k-step
-  u16 *wqkv_pk = nullptr, *wi_pk = nullptr;
-  u16* wo2_pk = nullptr;  // k-streamed layouts (output features permuted): MLP output projection ...
-  u16* wo_ks = nullptr;   // ... and attention output projection (fused kernels)
-  // hi planes in the fragment order of the 32x32x16 whole-layer kernel (opk_layer32.hip.h), hidden = 256 only
-  u16 *wo_p32 = nullptr, *wi_p32 = nullptr, *wo2_p32 = nullptr, *wqkv_p32 = nullptr;
-  // the wave-pair whole-layer kernel (opk_layer16p.hip.h), hidden = 256: one plane in its fragment order, [0] bf16 / [1] fp16 values
-  u16 *wo_pp[2] = {nullptr, nullptr}, *wi_pp[2] = {nullptr, nullptr}, *wo2_pp[2] = {nullptr, nullptr}, *wqkv_pp[2] = {nullptr, nullptr};
-  // "f16 + fp8" kernel set (opk_common.hip.h): chunks of [fp16 plane | e4m3 plane] (Wqkv, Wi), fp16 k-streamed slabs
-  // (attention Wo, MLP Wo) and the e4m3 K = 128 slabs of the attention Wo
-  u16 *wqkv_f8 = nullptr, *wi_f8 = nullptr, *wo_f16 = nullptr, *wo_f8 = nullptr, *wo2_f16 = nullptr;
-  // the same kernel sets on the panel path: per weight fp16 slabs + e4m3 slabs (w, then lo(w)) (pack_panel_f8_kernel)
-  u16 *wqkv_p16 = nullptr, *wqkv_p8 = nullptr, *wo_p16 = nullptr, *wo_p8 = nullptr, *wi_p16 = nullptr, *wi_p8 = nullptr,
-      *wo2_p16 = nullptr, *wo2_p8 = nullptr;
-  // kernel set "f16" (single-pass fp16 operands): the layouts of wqkv_pk / wi_pk / wo2_pk / wo_ks with fp16 values in the hi plane
-  u16 *wqkv_h16 = nullptr, *wi_h16 = nullptr, *wo2_h16 = nullptr, *wo_h16 = nullptr;
+  u16* pack[W_COUNT][PF_COUNT] = {};  // the GEMM weights in every format the handle builds (op_sets.h), nullptr: no such pack
 };
 
 struct ProfileEvent {
@@ -96,9 +79,9 @@ struct op_handle {
   int H = 0, I = 0, N = 0, nh = 0, V = 0, nl = 0, max_pos = 0;
   Policy req = opl::kPolicies[0];  // requested term masks (op_config.precision / terms)
   Policy eff = opl::kPolicies[0];  // evaluated term masks: req minus weight-lo terms that are identically zero
-  int pi = 0;                      // curated kernel set that runs `eff` (index into opl::kPolicies)
-  bool emulate = false;            // eff is not curated: kernel set 0 with the unused lo operands cleared
-  bool resolved = false;           // eff / pi / emulate are valid (set by op_weights_ready)
+  int set = -1;                    // the kernel set that runs (op_kernel_set numbering); -1: `eff` is no set's, all-terms kernels with the unused lo operands cleared
+  const KernelSet* ks = &kClearedOperands;  // its row of kKernelSets
+  bool resolved = false;           // eff / set / ks / mlp_layers are valid (set by op_weights_ready)
   float* f16_fit_dev = nullptr;    // [2] lost / total weight energy of the tensor being packed for the "f16 + fp8" sets
   int* any_lo_dev = nullptr;       // [OP_FAM_COUNT] device flags: some weight of the family has a non-zero lo element
                                    // [OP_FAM_COUNT]: some GEMM weight is not exactly an fp16 value (no "f16 + fp8" set)
@@ -106,14 +89,9 @@ struct op_handle {
   bool f8_off = false;             // op_set_compact_operands(h, 0): keep the (hi, lo) bf16 sets although the packs exist
   bool h16_packs = false;          // the fp16 single-plane weight packs of kernel set "f16" exist
   int forced_set = -1;             // op_select_kernel_set / op_calibrate: run this kernel set (op_kernel_set numbering), -1 = the default selection
-  int default_set = 0;             // the kernel set the default selection gives for this checkpoint (valid once resolved)
   bool f16_unfit = false;          // some weight TENSOR sits on fp16's subnormal grid: no kernel set with an fp16 weight plane
-  bool wi_f8 = false;              // panel path, OP_FLAG_PANEL_F8_WI: the Wi GEMM (and its LayerNorm) in the fp16 + e4m3 format
-  bool mlp_f8 = false;             // panel path, kernel sets 8 / 9: pi = PI_F16 for the attention side, the whole MLP in the fp16 + e4m3 format
-  bool mlp_wlo = false;            // ... with the weights' lo part (set 8)
   uint64_t mlp_layers = ~0ull;     // sets 8 / 9: the layers whose MLP runs in that format (bit li); the others run the "f16" set's MLP
   uint64_t forced_mlp_layers = ~0ull;  // ... as pinned with forced_set (op_calibrate's per-layer search, op_select_mlp_correction_layers)
-  bool attn_f16 = false;           // panel path, kernel sets 10 / 11: pi = PI_F16_F8_W / PI_F16_F8 with the attention on set 7's fp16 kernels
   bool row_path = false;    // hidden <= 256: row-stationary GEMMs with fused LayerNorm
   bool panel_path = false;  // hidden % 256 == 0, intermediate % 128 == 0: k-streamed panel GEMMs, fragment-packed operands
   int n_cus = 256;          // compute units of the device (hipDeviceProp multiProcessorCount)
@@ -355,8 +333,12 @@ struct ChunkPass {
   unsigned row_blocks;
   hipStream_t st;
   Policy E, V;  // evaluated policy, instantiated kernel set (V has every term of E)
+  int pi;       // ... its opl::kPolicies index
   bool clr_q, clr_k, clr_v, clr_o, clr_h, clr_ln_attn, clr_ln_mlp, zero_p_lo, split;
-  bool o_f8, f16, attn16, range_flagged, embed_in_qkv0;
+  // the operand formats of the handle's kernel set (h->ks, op_sets.h), decided once here
+  bool o_f8, f16, attn16, wi8, wlo8, range_flagged, embed_in_qkv0;
+  bool mlp8[OP_MAX_LAYERS];  // sets 8 / 9, per layer: the MLP in the fp16 + e4m3 format
+  PackFmt fmt_base, fmt_f8, fmt_side, fmt_wi;  // weight packs: layer-0 q / k / v, the fp16 + e4m3 GEMMs, attention side, Wi
   size_t plane_bytes;  // one row-major plane (tiled path)
   int q_tiles;
   bool small_blocks;
@@ -384,27 +366,42 @@ struct ChunkPass {
     st = L.stream;
     // Evaluated policy E, instantiated kernel set V (V has every term of E).  Where V multiplies by a lo operand that
     // E does not have, that operand is cleared: weights at load time (op_load_weight), activations in the launch sequence.
+    const KernelSet& ks = *h->ks;
     E = h->eff;
-    V = opl::kPolicies[h->pi];
+    pi = ks.pi;
+    V = opl::kPolicies[pi];
+    o_f8 = ks.side == FMT_F8;   // o = fp16 pieces (ws.o_hi) + e4m3 pieces (ws.o_lo); panel path: every GEMM in that format
+    f16 = ks.side == FMT_F16;   // kernel set "f16": set 2's layouts, fp16 values, the fp16 weight packs
+    // kernel sets 10 / 11 (panel path): q / k / v^T as single-plane fp16, attention on set 7's kernels with o in sets 3 / 4's
+    // format; they neither write nor read a lo plane of q / k / v^T
+    attn16 = o_f8 && ks.attn == FMT_F16;
     auto extra = [](int v, int e, int bit) { return (v & bit) != 0 && (e & bit) == 0; };
-    clr_q = extra(V.qk, E.qk, 1);
-    clr_k = extra(V.qk, E.qk, 2);
-    clr_v = extra(V.pv, E.pv, 2);
+    clr_q = !attn16 && extra(V.qk, E.qk, 1);
+    clr_k = !attn16 && extra(V.qk, E.qk, 2);
+    clr_v = !attn16 && extra(V.pv, E.pv, 2);
     clr_o = extra(V.attn_out, E.attn_out, 1);
     clr_h = extra(V.mlp_out, E.mlp_out, 1);
     clr_ln_attn = extra(V.wqkv, E.wqkv, 1);
     clr_ln_mlp = extra(V.wi, E.wi, 1);
-    zero_p_lo = extra(V.pv, E.pv, 1);
+    zero_p_lo = !attn16 && extra(V.pv, E.pv, 1);
     // tiled path: two kernel sets only (single pass / all terms)
     split = (E.wqkv | E.qk | E.pv | E.attn_out | E.wi | E.mlp_out) != 0;
-    o_f8 = (h->pi == opl::PI_F16_F8 || h->pi == opl::PI_F16_F8_W) && !h->emulate;  // o = fp16 pieces (ws.o_hi) + e4m3 pieces (ws.o_lo)
-    f16 = h->pi == opl::PI_F16 && !h->emulate;  // kernel set "f16": set 2's layouts, fp16 values, the fp16 weight packs
-    // kernel sets 10 / 11 (panel path): q / k / v^T as single-plane fp16, attention on set 7's kernels with o in sets 3 / 4's format
-    attn16 = o_f8 && h->attn_f16 && h->panel_path;
+    // OP_FLAG_PANEL_F8_WI (sets 5 / 6): the format in the Wi GEMM alone -- its LayerNorm writes fp16 + e4m3 pieces, its epilogue
+    // writes h as the (hi, lo) bf16 pieces the MLP output projection's kernel reads
+    wi8 = !o_f8 && ks.wi == FMT_F8 && ks.mlp != FMT_F8;
+    wlo8 = ks.wlo;
+    // kernel sets 8 / 9: the attention side on the "f16" kernels, the MLP -- LayerNorm(mlp_norm), Wi + GeGLU with h as fp16 +
+    // e4m3 pieces, MLP output projection -- on the fp16 + e4m3 kernels of sets 4 / 3, layer by layer: op_calibrate keeps it
+    // only in the layers the tolerance needs it in (mlp_layers)
+    for (int li = 0; li < h->N; ++li) mlp8[li] = mlp_by_layer(ks) && (li >= 64 || ((h->mlp_layers >> li) & 1ull) != 0);
     // Panel path, fp16 + e4m3 kernels (sets 3 / 4 / 8 - 11): they convert under MODE.FP16_OVFL = 1 (an h beyond fp16's range is
     // clamped) and their fp16 MFMAs take a NaN operand for a finite number, so an out-of-range activation cannot travel to the
     // outputs as Inf / NaN by itself: the kernels raise ws.range_flag and the head kernels write NaN logits.
-    range_flagged = h->panel_path && !h->emulate && (o_f8 || (f16 && h->mlp_f8));
+    range_flagged = h->panel_path && (o_f8 || ks.mlp == FMT_F8);
+    fmt_base = f16 ? PF_PK16 : PF_PK;
+    fmt_f8 = h->row_path ? PF_ROW_F8A : PF_PANEL16;
+    fmt_side = o_f8 ? fmt_f8 : fmt_base;
+    fmt_wi = (o_f8 || wi8) ? fmt_f8 : fmt_base;
     // Row path without hidden-state capture: the layer-0 q / k / v kernel gathers and normalises the embeddings itself
     // (RowGemmParams::emb_table) -- no embedding launch, the residual rows are written once and not read back.
     embed_in_qkv0 = h->row_path && !h->capture && !(h->cfg.flags & OP_FLAG_NO_HEAD_FUSION);
@@ -416,12 +413,16 @@ struct ChunkPass {
     row_grid = (unsigned)(r_pad / (small_blocks ? 64 : ROW_BM));
     // Kernel sets whose GEMM weights are single-plane run a whole layer (attention output projection, MLP, next q/k/v
     // projection) as ONE kernel with h kept on chip; the all-terms set keeps the two fused kernels per layer.
-    layer_fused = h->row_path && !h->emulate && opl::has_row_layer_fused(h->pi) && !(h->cfg.flags & OP_FLAG_NO_LAYER_FUSION);
+    layer_fused = h->row_path && h->set >= 0 && opl::has_row_layer_fused(pi) && !(h->cfg.flags & OP_FLAG_NO_LAYER_FUSION);
     head_in_last_layer = layer_fused && h->cfg.pooling != OP_POOL_MEAN && !h->capture && !(h->cfg.flags & OP_FLAG_NO_HEAD_FUSION);
-    pair_layers = layer_fused && H == 256 && I % 64 == 0 && (f16 || h->pi == 2) && !h->capture &&
+    // (!split: the single-pass sets "f16" / "bf16")
+    pair_layers = layer_fused && H == 256 && I % 64 == 0 && !split && !h->capture &&
                   !(h->cfg.flags & (OP_FLAG_NO_LAYER_PAIRS | OP_FLAG_LAYER_8X16 | OP_FLAG_LAYER_M32)) &&
-                  h->layers[0].wo_pp[f16 ? 1 : 0] != nullptr;
+                  weight(0, W_ATTN_OUT, f16 ? PF_PAIR16 : PF_PAIR) != nullptr;
   }
+
+  // the pack of a GEMM weight of layer `li` in the format the constructor decided
+  u16* weight(int li, Weight w, PackFmt f) const { return h->layers[li].pack[w][f]; }
 
   // row map, the range flag, padding rows of the attention output, embeddings
   int prologue() {
@@ -521,7 +522,7 @@ struct ChunkPass {
       const unsigned item_span = 8u * opk::ATT_ITEM_GROUP;
       const dim3 grid((ap.xcd_group ? ((unsigned)ap.n_items + item_span - 1) / item_span * item_span : (unsigned)ap.n_items) *
                       (unsigned)h->nh);
-      if (!opl::launch_attn(st, ap, is_global ? plan.waves_g : 4, is_global ? 2 : 1, h->pi, zero_p_lo && !attn16, grid, attn16))
+      if (!opl::launch_attn(st, ap, is_global ? plan.waves_g : 4, is_global ? 2 : 1, pi, zero_p_lo, grid, attn16))
         return fail(h, OP_ERR_UNSUPPORTED, "internal: no attention kernel for this configuration");
     } else {
       const dim3 grid((unsigned)q_tiles, (unsigned)h->nh, (unsigned)ns);
@@ -565,7 +566,6 @@ struct ChunkPass {
 
   // parameters of a q/k/v projection of layer `li` (row-stationary kernels)
   RowGemmParams qkv_params(int li) {
-    const LayerWeights& lw = h->layers[li];
     const bool is_global = h->cfg.layer_is_global[li] != 0;
     RowGemmParams rp;
     memset(&rp, 0, sizeof(rp));
@@ -577,8 +577,8 @@ struct ChunkPass {
     rp.rope_sin = h->rope_sin[is_global ? 1 : 0];
     rp.max_pos = h->max_pos;
     rp.x_in = ws.x;
-    rp.ln_w = lw.attn_norm;
-    rp.wp = f16 ? lw.wqkv_h16 : lw.wqkv_pk;
+    rp.ln_w = h->layers[li].attn_norm;
+    rp.wp = weight(li, W_QKV, fmt_base);
     rp.n_chunks = 3 * H / ROW_CHUNK;
     rp.n_swapped = 2 * H / ROW_CHUNK;
     rp.o0_hi = ws.q_hi;
@@ -605,7 +605,7 @@ struct ChunkPass {
         rp.x_io = ws.x;
       }
       OP_TRY(L.begin(PK_ROW_QKV));
-      if (!opl::launch_row_qkv0(st, rp, H / 32, small_blocks, h->pi, row_grid)) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
+      if (!opl::launch_row_qkv0(st, rp, H / 32, small_blocks, pi, row_grid)) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
       OP_TRY(L.end());
       OP_TRY(clear_qkv());
       if (embed_in_qkv0) OP_TRY(hidden(0));  // (the embedding rows were written by the launch above)
@@ -615,66 +615,41 @@ struct ChunkPass {
     if (layer_fused) {
       // x += o Wo^T ; x += GeGLU(LN(x) Wi^T) Wo^T ; q, k, v^T of the NEXT layer -- one kernel, h stays on chip
       const bool with_qkv = li + 1 < h->N;
-      if ((h->cfg.flags & OP_FLAG_LAYER_M32) && lw.wo_p32 && opl::has_layer32(h->pi) && I % 64 == 0) {
-        // hidden = 256, on request: the same launch on the 32x32x16 MFMA shape (opk_layer32.hip.h) -- 6 % fewer
-        // cycles, but that shape draws more power per flop and the chip clocks lower under it
-        Layer32Params lp;
-        memset(&lp, 0, sizeof(lp));
-        const LayerWeights& nx = h->layers[with_qkv ? li + 1 : li];
-        lp.o_fp = ws.o_hi;
-        lp.x_io = ws.x;
-        lp.ln_mlp = lw.mlp_norm;
-        lp.ln_next = with_qkv ? nx.attn_norm : nullptr;
-        lp.eps = h->cfg.norm_eps;
-        lp.wo_p = lw.wo_p32;
-        lp.wi_p = lw.wi_p32;
-        lp.wo2_p = lw.wo2_p32;
-        lp.wqkv_p = nx.wqkv_p32;
-        lp.n_pairs = I / 32;
-        lp.q_fp = ws.q_hi;
-        lp.k_fp = ws.k_hi;
-        lp.vt_fp = ws.vt_hi;
-        lp.r_pad = r_pad;
-        lp.row_pos = ws.row_pos;
-        const int gl = h->cfg.layer_is_global[with_qkv ? li + 1 : li] ? 1 : 0;
-        lp.rope_cos = h->rope_cos[gl];
-        lp.rope_sin = h->rope_sin[gl];
-        lp.max_pos = h->max_pos;
-        OP_TRY(L.begin(PK_FUSED_LAYER));
-        if (!opl::launch_layer32(st, lp, h->pi, with_qkv, (unsigned)(r_pad / ROW_BM))) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
-        OP_TRY(L.end());
-        return OP_OK;
-      }
-      // Single-pass kernel sets ("f16" / "bf16"), hidden = 256: the wave-pair kernel (opk_layer16p.hip.h), at every batch size --
+      // The two other forms of this launch, hidden = 256.  OP_FLAG_LAYER_M32, on request: the 32x32x16 MFMA shape
+      // (opk_layer32.hip.h) -- 6 % fewer cycles, but that shape draws more power per flop and the chip clocks lower under it
+      // (DESIGN.md section 4).
+      // Single-pass kernel sets ("f16" / "bf16"): the wave-pair kernel (opk_layer16p.hip.h), at every batch size --
       // below one 128-row block per CU too, where the other launches switch to 64-row blocks (small_blocks): 4 - 8 % faster
       // forwards from 512 to 32 k tokens than the 8 x 16 kernel's 64-row form (profiles/r06_small_request.txt).  The last layer keeps the 8 x 16 kernel (it ends with final_norm + the pruning head).  Between two
       // wave-pair launches the residual stream is TILED (coalesced 1 KiB loads / stores): the first one reads rows, the last
       // one writes rows.  Hidden-state capture reads rows after every layer: it keeps the 8 x 16 kernel.  A per-call
       // hidden-state request does not change the kernel: its entry li + 1 is stored from this launch's epilogue (layer16p_hout_kernel).
-      if (pair_layers && with_qkv) {
+      const bool m32 = (h->cfg.flags & OP_FLAG_LAYER_M32) && weight(li, W_ATTN_OUT, PF_L32) && opl::has_layer32(pi) && I % 64 == 0;
+      if (m32 || (pair_layers && with_qkv)) {
+        const PackFmt pf = m32 ? PF_L32 : (f16 ? PF_PAIR16 : PF_PAIR);
+        const int nx = with_qkv ? li + 1 : li;
         Layer32Params lp;
         memset(&lp, 0, sizeof(lp));
-        const LayerWeights& nx = h->layers[li + 1];
         lp.o_fp = ws.o_hi;
         lp.x_io = ws.x;
         lp.ln_mlp = lw.mlp_norm;
-        lp.ln_next = nx.attn_norm;
+        lp.ln_next = with_qkv ? h->layers[nx].attn_norm : nullptr;
         lp.eps = h->cfg.norm_eps;
-        lp.wo_p = lw.wo_pp[f16 ? 1 : 0];
-        lp.wi_p = lw.wi_pp[f16 ? 1 : 0];
-        lp.wo2_p = lw.wo2_pp[f16 ? 1 : 0];
-        lp.wqkv_p = nx.wqkv_pp[f16 ? 1 : 0];
+        lp.wo_p = weight(li, W_ATTN_OUT, pf);
+        lp.wi_p = weight(li, W_WI, pf);
+        lp.wo2_p = weight(li, W_MLP_OUT, pf);
+        lp.wqkv_p = weight(nx, W_QKV, pf);
         lp.n_pairs = I / 32;
         lp.q_fp = ws.q_hi;
         lp.k_fp = ws.k_hi;
         lp.vt_fp = ws.vt_hi;
         lp.r_pad = r_pad;
         lp.row_pos = ws.row_pos;
-        const int gl = h->cfg.layer_is_global[li + 1] ? 1 : 0;
+        const int gl = h->cfg.layer_is_global[nx] ? 1 : 0;
         lp.rope_cos = h->rope_cos[gl];
         lp.rope_sin = h->rope_sin[gl];
         lp.max_pos = h->max_pos;
-        lp.hid_out = hidden_entry(li + 1);
+        if (!m32) lp.hid_out = hidden_entry(li + 1);
         if (lp.hid_out) {
           lp.row_tok = ws.row_tok;
           lp.row_seq = ws.row_seq;
@@ -684,28 +659,26 @@ struct ChunkPass {
           hidden_stored = li + 1;
         }
         OP_TRY(L.begin(PK_FUSED_LAYER));
-        if (!opl::launch_layer16p(st, lp, f16, true, /*xin_t=*/li > 0, /*xout_t=*/li + 2 < h->N, (unsigned)(r_pad / ROW_BM),
-                                  lp.hid_out != nullptr))
+        const unsigned grid = (unsigned)(r_pad / ROW_BM);
+        if (!(m32 ? opl::launch_layer32(st, lp, pi, with_qkv, grid)
+                  : opl::launch_layer16p(st, lp, f16, true, /*xin_t=*/li > 0, /*xout_t=*/li + 2 < h->N, grid, lp.hid_out != nullptr)))
           return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
         OP_TRY(L.end());
         return OP_OK;
       }
       RowGemmParams rl = qkv_params(with_qkv ? li + 1 : li);
       rl.a1_fp = ws.o_hi;
-      rl.w1p = f16 ? lw.wo_h16 : lw.wo_ks;
+      rl.wp = weight(with_qkv ? li + 1 : li, W_QKV, fmt_side);  // (sets 3 / 4: layer 0's own projection ran on fmt_base)
+      rl.w1p = weight(li, W_ATTN_OUT, fmt_side);
       rl.k1_steps = H / 32;
       rl.x_io = ws.x;
       rl.ln_w_mlp = lw.mlp_norm;
-      rl.wi_pk = f16 ? lw.wi_h16 : lw.wi_pk;
-      rl.wo2_ks = f16 ? lw.wo2_h16 : lw.wo2_pk;
+      rl.wi_pk = weight(li, W_WI, fmt_side);
+      rl.wo2_ks = weight(li, W_MLP_OUT, fmt_side);
       rl.n_pairs = I / 32;
-      if (o_f8) {  // the "f16 + fp8" packs of the same weights
+      if (o_f8) {  // the e4m3 pieces of o and of the attention Wo
         rl.a1_lo8 = ws.o_lo;
-        rl.w1p = lw.wo_f16;
-        rl.w1p8 = lw.wo_f8;
-        rl.wi_pk = lw.wi_f8;
-        rl.wo2_ks = lw.wo2_f16;
-        rl.wp = h->layers[with_qkv ? li + 1 : li].wqkv_f8;
+        rl.w1p8 = weight(li, W_ATTN_OUT, PF_ROW_F8B);
       }
       if (!with_qkv && head_in_last_layer) {
         // the last layer's rows go straight through final_norm + the pruning head (no write-back of x, no
@@ -728,8 +701,8 @@ struct ChunkPass {
         }
       }
       OP_TRY(L.begin(PK_FUSED_LAYER));
-      if (!opl::launch_row_layer_fused(st, rl, H / 32, h->pi, with_qkv, (unsigned)(r_pad / ROW_BM),
-                                       (h->cfg.flags & OP_FLAG_LAYER_8X16) != 0 || (opl::kPolicies[h->pi].wi & 1) == 0,
+      if (!opl::launch_row_layer_fused(st, rl, H / 32, pi, with_qkv, (unsigned)(r_pad / ROW_BM),
+                                       (h->cfg.flags & OP_FLAG_LAYER_8X16) != 0 || (V.wi & 1) == 0,
                                        rl.hid_out != nullptr))
         return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
       OP_TRY(L.end());
@@ -743,17 +716,17 @@ struct ChunkPass {
     rp.hidden = H;
     rp.r_pad = r_pad;
     rp.ln_w = lw.mlp_norm;
-    rp.wp = lw.wi_pk;
+    rp.wp = weight(li, W_WI, PF_PK);
     rp.n_chunks = 2 * I / ROW_CHUNK;
     rp.o0_hi = ws.h_hi;  // fragment-packed h (h_hi + h_lo are one buffer)
     rp.ld_out = I;
     rp.a1_fp = ws.o_hi;
-    rp.w1p = lw.wo_ks;
+    rp.w1p = weight(li, W_ATTN_OUT, PF_PK);
     rp.k1_steps = H / 32;
     rp.x_io = ws.x;
     rp.zero_a_lo = clr_ln_mlp ? 1 : 0;
     OP_TRY(L.begin(PK_FUSED_ATTN_OUT_WI));
-    if (!opl::launch_row_geglu_fused(st, rp, H / 32, small_blocks, h->pi, row_grid)) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
+    if (!opl::launch_row_geglu_fused(st, rp, H / 32, small_blocks, pi, row_grid)) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
     OP_TRY(L.end());
     OP_TRY(clear_h());
 
@@ -761,21 +734,21 @@ struct ChunkPass {
       // x += h Wo^T ; q, k, v^T of the NEXT layer = RoPE / transpose of LN(x) Wqkv^T
       RowGemmParams rq = qkv_params(li + 1);
       rq.a1_fp = ws.h_hi;
-      rq.w1p = lw.wo2_pk;
+      rq.w1p = weight(li, W_MLP_OUT, PF_PK);
       rq.k1_steps = I / 32;
       rq.x_io = ws.x;
       OP_TRY(L.begin(PK_FUSED_MLP_OUT_QKV));
-      if (!opl::launch_row_qkv_fused(st, rq, H / 32, small_blocks, h->pi, row_grid)) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
+      if (!opl::launch_row_qkv_fused(st, rq, H / 32, small_blocks, pi, row_grid)) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
       OP_TRY(L.end());
       OP_TRY(clear_qkv());
     } else {
       KStreamParams kp;
       kp.a_fp = ws.h_hi;
-      kp.wp = lw.wo2_pk;
+      kp.wp = weight(li, W_MLP_OUT, PF_PK);
       kp.n_ksteps = I / 32;
       kp.x = ws.x;
       OP_TRY(L.begin(PK_KSTREAM_MLP_OUT));
-      if (!opl::launch_kstream(st, kp, H / 16, h->pi, (unsigned)(r_pad / ROW_BM))) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
+      if (!opl::launch_kstream(st, kp, H / 16, pi, (unsigned)(r_pad / ROW_BM))) return fail(h, OP_ERR_UNSUPPORTED, no_kernel, H);
       OP_TRY(L.end());
     }
     return OP_OK;
@@ -787,14 +760,8 @@ struct ChunkPass {
     const bool is_global = h->cfg.layer_is_global[li] != 0;
     // ---- panel path (hidden % 256 == 0): LayerNorm -> fragment-packed planes, k-streamed panel GEMMs ----
     const dim3 ln_grid((unsigned)(r_pad / 16));
-    const bool pf8 = o_f8;  // kernel sets 3 / 4: activations as fp16 pieces + e4m3 pieces (x 2^12) of their lo part
-    // kernel sets 8 / 9: the attention side on the "f16" kernels (pi = PI_F16), the MLP -- LayerNorm(mlp_norm), Wi + GeGLU
-    // with h as fp16 + e4m3 pieces, MLP output projection -- on the fp16 + e4m3 kernels of sets 4 / 3
-    // -- layer by layer: op_calibrate keeps the fp16 + e4m3 MLP only in the layers the tolerance needs it in (mlp_layers)
-    const bool mlp8 = f16 && h->mlp_f8 && (li >= 64 || ((h->mlp_layers >> li) & 1ull) != 0);
-    const bool wlo8 = h->pi == opl::PI_F16_F8_W || (h->wi_f8 && h->pi == opl::PI_ALL_TERMS) || (mlp8 && h->mlp_wlo);
-    // OP_FLAG_PANEL_F8_WI: the format in the Wi GEMM alone -- its LayerNorm writes fp16 + e4m3 pieces, its epilogue
-    // writes h as the (hi, lo) bf16 pieces the MLP output projection's kernel reads
+    const bool pf8 = o_f8;  // kernel sets 3 / 4 / 10 / 11: activations as fp16 pieces + e4m3 pieces (x 2^12) of their lo part
+    const bool m8 = mlp8[li];
     auto layer_norm_fp = [&](const float* w, bool with_lo, bool clear, bool f8_here = false) -> int {
       OP_TRY(L.begin(PK_LN));
       if (pf8 || f8_here) {
@@ -823,10 +790,10 @@ struct ChunkPass {
       const unsigned per_xcd = ((unsigned)(r_pad / ROW_BM) + 7) / 8;  // row blocks each XCD owns
       const unsigned groups = (per_xcd + q.row_group - 1) / q.row_group;
       const dim3 grid(8u * groups * (unsigned)q.row_group * (unsigned)n_tiles);  // XCD-aware block map: see panel_gemm_kernel
-      const bool ok = f8_here ? opl::launch_panel_f8(st, q, 103, wlo8, grid)
+      const bool ok = f8_here ? opl::launch_panel_f8(st, q, PANEL_EPI_GEGLU_BF16_H, wlo8, grid)
                       : f8_full ? opl::launch_panel_f8(st, q, epi, wlo8, grid)
-                      : pf8   ? (epi == 102 ? opl::launch_panel_f8_qkv(st, q, wlo8, attn16, grid) : opl::launch_panel_f8(st, q, epi, wlo8, grid))
-                              : (epi == 102 ? opl::launch_panel_qkv(st, q, h->pi, grid) : opl::launch_panel(st, q, epi, h->pi, grid));
+                      : pf8   ? (epi == PANEL_EPI_QKV ? opl::launch_panel_f8_qkv(st, q, wlo8, attn16, grid) : opl::launch_panel_f8(st, q, epi, wlo8, grid))
+                              : (epi == PANEL_EPI_QKV ? opl::launch_panel_qkv(st, q, pi, grid) : opl::launch_panel(st, q, epi, pi, grid));
       if (!ok) return fail(h, OP_ERR_UNSUPPORTED, "internal: no panel kernel");
       return L.end();
     };
@@ -844,53 +811,50 @@ struct ChunkPass {
     pp.a_fp = ws.ln_hi;
     pp.a_lo8 = ws.ln_lo;
     pp.n_ksteps = H / 32;
-    pp.wp = pf8 ? lw.wqkv_p16 : (f16 ? lw.wqkv_h16 : lw.wqkv_pk);
-    pp.wp8 = lw.wqkv_p8;
+    pp.wp = weight(li, W_QKV, fmt_side);
+    pp.wp8 = weight(li, W_QKV, PF_PANEL8);
     pp.w8_lo_off = (size_t)3 * H * H / 2;  // u16 elements: the tensor's e4m3(w) slabs, then those of lo(w)
     pp.o0 = ws.q_hi;
     pp.o1 = ws.k_hi;
     if (pf8 || !(h->cfg.flags & OP_FLAG_NO_LAYER_FUSION)) {  // q, k, v^T in one launch
       pp.o2 = ws.vt_hi;
       pp.n_qk_tiles = 2 * H / 256;
-      OP_TRY(panel(PK_GEMM_QKV_ROPE, 102, pp, 3 * H / 256));
+      OP_TRY(panel(PK_GEMM_QKV_ROPE, PANEL_EPI_QKV, pp, 3 * H / 256));
     } else {
       OP_TRY(panel(PK_GEMM_QK_ROPE, PE_QK, pp, 2 * H / 256));
-      pp.wp = (f16 ? lw.wqkv_h16 : lw.wqkv_pk) + (size_t)(2 * H / 256) * (H / 32) * 2 * 8192;
+      pp.wp = weight(li, W_QKV, fmt_base) + (size_t)(2 * H / 256) * (H / 32) * 2 * 8192;
       pp.o0 = ws.vt_hi;
       OP_TRY(panel(PK_GEMM_V_T, PE_V, pp, H / 256));
     }
-    if (!attn16) {  // (sets 10 / 11 neither write nor read a lo plane of q / k / v^T)
-      OP_TRY(clear_qkv());
-    }
+    OP_TRY(clear_qkv());
     OP_TRY(attention(is_global));
     pp.a_fp = ws.o_hi;
     pp.a_lo8 = ws.o_lo;
-    pp.wp = pf8 ? lw.wo_p16 : (f16 ? lw.wo_h16 : lw.wo_ks);
-    pp.wp8 = lw.wo_p8;
+    pp.wp = weight(li, W_ATTN_OUT, fmt_side);
+    pp.wp8 = weight(li, W_ATTN_OUT, PF_PANEL8);
     pp.w8_lo_off = (size_t)H * H / 2;
     pp.x = ws.x;
     pp.ld_out = H;
-    OP_TRY(panel(PK_GEMM_ATTN_OUT, 100, pp, H / 256));
-    const bool wi8 = h->wi_f8 && !pf8;
-    OP_TRY(layer_norm_fp(lw.mlp_norm, (V.wi & 1) != 0, clr_ln_mlp && !wi8, wi8 || mlp8));
+    OP_TRY(panel(PK_GEMM_ATTN_OUT, PANEL_EPI_ATTN_OUT, pp, H / 256));
+    OP_TRY(layer_norm_fp(lw.mlp_norm, (V.wi & 1) != 0, clr_ln_mlp && !wi8, wi8 || m8));
     pp.a_fp = ws.ln_hi;
     pp.a_lo8 = ws.ln_lo;
-    pp.wp = (pf8 || wi8 || mlp8) ? lw.wi_p16 : (f16 ? lw.wi_h16 : lw.wi_pk);
-    pp.wp8 = lw.wi_p8;
+    pp.wp = weight(li, W_WI, m8 ? fmt_f8 : fmt_wi);
+    pp.wp8 = weight(li, W_WI, PF_PANEL8);
     pp.w8_lo_off = (size_t)2 * I * H / 2;
     pp.o0 = ws.h_hi;
     pp.o0_lo8 = ws.h_lo;
     pp.ld_out = I;
-    OP_TRY(panel(PK_GEMM_WI_GEGLU, PE_GEGLU, pp, I / 128, wi8, mlp8));
+    OP_TRY(panel(PK_GEMM_WI_GEGLU, PE_GEGLU, pp, I / 128, wi8, m8));
     OP_TRY(clear_h());
     pp.a_fp = ws.h_hi;
     pp.a_lo8 = ws.h_lo;
     pp.n_ksteps = I / 32;
-    pp.wp = (pf8 || mlp8) ? lw.wo2_p16 : (f16 ? lw.wo2_h16 : lw.wo2_pk);
-    pp.wp8 = lw.wo2_p8;
+    pp.wp = weight(li, W_MLP_OUT, m8 ? fmt_f8 : fmt_side);
+    pp.wp8 = weight(li, W_MLP_OUT, PF_PANEL8);
     pp.w8_lo_off = (size_t)H * I / 2;
     pp.ld_out = H;
-    OP_TRY(panel(PK_GEMM_MLP_OUT, 101, pp, H / 256, false, mlp8));
+    OP_TRY(panel(PK_GEMM_MLP_OUT, PANEL_EPI_MLP_OUT, pp, H / 256, false, m8));
     return OP_OK;
   }
 
@@ -927,8 +891,8 @@ struct ChunkPass {
     p.rope_sin = h->rope_sin[is_global ? 1 : 0];
     p.max_pos = h->max_pos;
     // q, k = RoPE(x Wq^T), RoPE(x Wk^T)
-    p.w_hi = lw.wqkv_hi;
-    p.w_lo = lw.wqkv_lo;
+    p.w_hi = weight(li, W_QKV, PF_HI);
+    p.w_lo = weight(li, W_QKV, PF_LO);
     p.n_tiles = 2 * H / GEMM_BN;
     p.o0_hi = ws.q_hi;
     p.o0_lo = ws.q_lo;
@@ -937,8 +901,8 @@ struct ChunkPass {
     p.ld_out = H;
     OP_TRY(launch_gemm<EPI_QK_ROPE>(L, PK_GEMM_QK_ROPE, p, split));
     // v^T
-    p.w_hi = lw.wqkv_hi + (size_t)2 * H * H;
-    p.w_lo = lw.wqkv_lo + (size_t)2 * H * H;
+    p.w_hi = weight(li, W_QKV, PF_HI) + (size_t)2 * H * H;
+    p.w_lo = weight(li, W_QKV, PF_LO) + (size_t)2 * H * H;
     p.n_tiles = H / GEMM_BN;
     p.o0_hi = ws.vt_hi;
     p.o0_lo = ws.vt_lo;
@@ -953,8 +917,8 @@ struct ChunkPass {
     // x += attn Wo^T
     p.a_hi = ws.o_hi;
     p.a_lo = ws.o_lo;
-    p.w_hi = lw.wo_hi;
-    p.w_lo = lw.wo_lo;
+    p.w_hi = weight(li, W_ATTN_OUT, PF_HI);
+    p.w_lo = weight(li, W_ATTN_OUT, PF_LO);
     p.K = H;
     p.n_tiles = H / GEMM_BN;
     p.x = ws.x;
@@ -964,8 +928,8 @@ struct ChunkPass {
     OP_TRY(layer_norm(lw.mlp_norm, E.wi));
     p.a_hi = ws.ln_hi;
     p.a_lo = ws.ln_lo;
-    p.w_hi = lw.wi_hi;
-    p.w_lo = lw.wi_lo;
+    p.w_hi = weight(li, W_WI, PF_HI);
+    p.w_lo = weight(li, W_WI, PF_LO);
     p.K = H;
     p.n_tiles = 2 * I / GEMM_BN;
     p.o0_hi = ws.h_hi;
@@ -975,8 +939,8 @@ struct ChunkPass {
     if (split && !(E.mlp_out & 1)) OP_HIP(h, hipMemsetAsync(ws.h_lo, 0, (size_t)r_pad * I * sizeof(u16), st));
     p.a_hi = ws.h_hi;
     p.a_lo = ws.h_lo;
-    p.w_hi = lw.wo2_hi;
-    p.w_lo = lw.wo2_lo;
+    p.w_hi = weight(li, W_MLP_OUT, PF_HI);
+    p.w_lo = weight(li, W_MLP_OUT, PF_LO);
     p.K = I;
     p.n_tiles = H / GEMM_BN;
     p.x = ws.x;
@@ -1028,6 +992,94 @@ int forward_chunk(op_handle* h, Launcher& L, const Workspace& ws, const int32_t*
                   float* keep_prob, const HiddenReq* hid) {
   return ChunkPass(h, L, ws, ids_dev, cu_dev, s0, ns, rows, max_len, total_tokens, plan, prune_out, rank_out, keep_prob, hid).run();
 }
+
+// Every packed form of one GEMM weight tensor (op_load_weight), on the null stream: one method per packing kernel.
+struct WeightPacker {
+  op_handle* h;
+  const WeightDesc& wd;
+  const float* f32;  // the tensor as fp32 [d0][d1]
+  int d0, d1;
+  // A requested policy without the hi x lo(weight) term stores zeros in the lo plane (so that any kernel set gives
+  // that policy's numerics); `any_lo` records whether the tensor had a non-zero lo element at all.
+  int zero_lo;
+  int* any_lo;
+
+  size_t count() const { return (size_t)d0 * d1; }
+  dim3 grid(size_t n) const { return dim3((unsigned)((n + 255) / 256)); }
+  // the fp16 + e4m3 packs raise this flag (any_lo_dev[OP_FAM_COUNT]) for a weight they cannot hold exactly
+  int* not_f16() const { return h->any_lo_dev + OP_FAM_COUNT; }
+
+  // panel-major: [panel][k-step][plane][16 fragments][512], rows permuted per consumer (panel_source_row); f16: fp16 values
+  void panels(u16* dst, int f16) const {
+    int tile0 = 0;
+    for (const PanelSeg& sg : wd.panel) {
+      const int n_tiles = (sg.th * h->H + sg.ti * h->I) / 256;
+      if (n_tiles)
+        hipLaunchKernelGGL(pack_panel_kernel, grid((size_t)n_tiles * 256 * d1), dim3(256), 0, 0, f32, n_tiles, d1, sg.epi, h->H, h->I,
+                           dst + (size_t)tile0 * 256 * d1 * 2, f16 ? 1 : zero_lo, any_lo, f16);
+      tile0 += n_tiles;
+    }
+  }
+  // the fp16 slabs + e4m3 slabs of the same panels
+  void panels_f8(u16* dst16, u16* dst8) const {
+    const size_t lo_off = count();  // bytes of the whole tensor's e4m3(w) slabs: the lo(w) slabs follow
+    int tile0 = 0;
+    for (const PanelSeg& sg : wd.panel) {
+      const int n_tiles = (sg.th * h->H + sg.ti * h->I) / 256;
+      if (n_tiles)
+        hipLaunchKernelGGL(pack_panel_f8_kernel, grid((size_t)n_tiles * 256 * d1), dim3(256), 0, 0, f32, n_tiles, d1, sg.epi, h->H, h->I,
+                           dst16 + (size_t)tile0 * 256 * d1, dst8 + (size_t)tile0 * 256 * d1 / 2, lo_off, zero_lo, not_f16(), h->f16_fit_dev);
+      tile0 += n_tiles;
+    }
+  }
+  // row path: chunk-major (pack_rowgemm_kernel) or k-streamed (pack_kstream_kernel); f16: fp16 values in the hi plane
+  void rows(u16* dst, int f16) const {
+    if (wd.row_mode == ROW_PACK_KSTREAM)
+      hipLaunchKernelGGL(pack_kstream_kernel, grid(count()), dim3(256), 0, 0, f32, d0, d1, 1, dst, f16 ? 1 : zero_lo, any_lo, f16);
+    else
+      hipLaunchKernelGGL(pack_rowgemm_kernel, grid(count()), dim3(256), 0, 0, f32, d0, d1, wd.row_mode, h->H, h->I, dst, f16 ? 1 : zero_lo,
+                         any_lo, f16);
+  }
+  void rows_f8(u16* dst_a, u16* dst_b) const {
+    if (wd.row_mode == ROW_PACK_KSTREAM)
+      hipLaunchKernelGGL(pack_kstream_f8_kernel, grid(count()), dim3(256), 0, 0, f32, d0, d1, 1, dst_a, dst_b, zero_lo, not_f16(), h->f16_fit_dev);
+    else
+      hipLaunchKernelGGL(pack_rowgemm_f8_kernel, grid(count()), dim3(256), 0, 0, f32, d0, d1, wd.row_mode, h->H, h->I, dst_a, zero_lo, not_f16(),
+                         h->f16_fit_dev);
+  }
+  // after the one fp16 + e4m3 pack of the tensor: its energy, then the tensor's verdict (f16_unfit) from what the pack lost
+  void close_f16_fit() const {
+    hipLaunchKernelGGL(weight_energy_kernel, dim3(256), dim3(256), 0, 0, f32, count(), h->f16_fit_dev);
+    hipLaunchKernelGGL(f16_fit_close_tensor_kernel, dim3(1), dim3(1), 0, 0, not_f16(), h->f16_fit_dev);
+  }
+
+  void run(u16* const* pk) const {  // pk[PF_COUNT]: the layer's packs of this weight
+    if (pk[PF_HI])
+      hipLaunchKernelGGL(split_planes_kernel, grid(count()), dim3(256), 0, 0, f32, d0, d1, wd.geglu ? h->I : 0, pk[PF_HI], pk[PF_LO], zero_lo,
+                         any_lo);
+    if (h->panel_path) {
+      if (pk[PF_PANEL16]) {
+        panels_f8(pk[PF_PANEL16], pk[PF_PANEL8]);
+        close_f16_fit();
+      }
+      panels(pk[PF_PK], 0);
+      if (pk[PF_PK16]) panels(pk[PF_PK16], 1);
+    } else if (h->row_path) {
+      rows(pk[PF_PK], 0);
+      if (pk[PF_PK16]) rows(pk[PF_PK16], 1);
+      if (pk[PF_ROW_F8A]) {
+        rows_f8(pk[PF_ROW_F8A], pk[PF_ROW_F8B]);
+        close_f16_fit();
+      }
+      if (pk[PF_L32])  // (hi plane; that kernel runs only when the lo planes are zero)
+        hipLaunchKernelGGL(pack_layer32_kernel, grid(count()), dim3(256), 0, 0, f32, d0, d1, wd.l32_mode, wd.kmajor, h->H, h->I, pk[PF_L32]);
+      for (PackFmt pf : {PF_PAIR, PF_PAIR16})
+        if (pk[pf])
+          hipLaunchKernelGGL(pack_layer16p_kernel, grid(count()), dim3(256), 0, 0, f32, d0, d1, wd.l32_mode, wd.kmajor, h->H, h->I, pk[pf],
+                             pf == PF_PAIR16 ? 1 : 0);
+    }
+  }
+};
 
 }  // namespace
 
@@ -1173,61 +1225,16 @@ int op_create(const op_config* cfg, op_handle** out) {
       h->missing.push_back(pre + "attn_norm.weight");
     }
     OP_CREATE_TRY(dev_alloc(h, &lw.mlp_norm, H));
-    if (!h->row_path && !h->panel_path) {  // tiled path: row-major hi / lo planes
-      OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_hi, 3 * HH));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_lo, 3 * HH));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wo_hi, HH));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wo_lo, HH));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wi_hi, (size_t)2 * I * H));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wi_lo, (size_t)2 * I * H));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wo2_hi, (size_t)H * I));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wo2_lo, (size_t)H * I));
-    } else {  // fragment-ordered layouts (hi and lo planes interleaved): chunk-major (row path) or panel-major
-      OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_pk, 2 * 3 * HH));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wi_pk, (size_t)2 * 2 * I * H));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wo2_pk, (size_t)2 * H * I));
-      OP_CREATE_TRY(dev_alloc(h, &lw.wo_ks, 2 * HH));
-      if (h->h16_packs) {
-        OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_h16, 2 * 3 * HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wi_h16, (size_t)2 * 2 * I * H));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo2_h16, (size_t)2 * H * I));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo_h16, 2 * HH));
-      }
-      if (h->f8_packs && h->panel_path) {  // 4 bytes per weight element: fp16 + e4m3(w) + e4m3(lo(w))
-        OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_p16, 3 * HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_p8, 3 * HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo_p16, HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo_p8, HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wi_p16, (size_t)2 * I * H));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wi_p8, (size_t)2 * I * H));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo2_p16, (size_t)H * I));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo2_p8, (size_t)H * I));
-      }
-      if (h->f8_packs && h->row_path) {  // 4 bytes per weight element: fp16 + e4m3 + e4m3 of the lo part (fp16 for the MLP's Wo)
-        OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_f8, 3 * HH * 2));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wi_f8, (size_t)2 * I * H * 2));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo_f16, HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo_f8, HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo2_f16, (size_t)2 * H * I));
-      }
-      if (h->row_path && H == 256) {
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo_p32, HH));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wi_p32, (size_t)2 * I * H));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wo2_p32, (size_t)H * I));
-        OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_p32, 3 * HH));
-        for (int f = 0; f < (h->h16_packs ? 2 : 1); ++f) {
-          OP_CREATE_TRY(dev_alloc(h, &lw.wo_pp[f], HH));
-          OP_CREATE_TRY(dev_alloc(h, &lw.wi_pp[f], (size_t)2 * I * H));
-          OP_CREATE_TRY(dev_alloc(h, &lw.wo2_pp[f], (size_t)H * I));
-          OP_CREATE_TRY(dev_alloc(h, &lw.wqkv_pp[f], 3 * HH));
+    // the GEMM weights in every format this handle's path and flags build (pack_exists); fp16 + e4m3: 4 bytes per weight element
+    for (const AllocStep& step : kAllocOrder)
+      for (Weight w : step.order)
+        for (int f = 0; f < step.n_fmt; ++f) {
+          const PackFmt pf = step.fmt[f];
+          if (kPackElems[w][pf] && pack_exists(pf, h->row_path, h->panel_path, h->f8_packs, h->h16_packs, H))
+            OP_CREATE_TRY(dev_alloc(h, &lw.pack[w][pf], weight_elems(w, H, I) * kPackElems[w][pf]));
         }
-      }
-    }
     h->missing.push_back(pre + "mlp_norm.weight");
-    h->missing.push_back(pre + "attn.Wqkv.weight");
-    h->missing.push_back(pre + "attn.Wo.weight");
-    h->missing.push_back(pre + "mlp.Wi.weight");
-    h->missing.push_back(pre + "mlp.Wo.weight");
+    for (const WeightDesc& wd : kWeights) h->missing.push_back(pre + wd.tail);
   }
   OP_CREATE_TRY(dev_alloc(h, &h->cov_bits, ((size_t)h->V + 31) / 32));
   OP_CREATE_TRY(dev_alloc(h, &h->cov_state, (size_t)opl::COV_WORDS));
@@ -1267,20 +1274,10 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
   const int64_t d0 = shape[0], d1 = ndim == 2 ? shape[1] : 1;
   const int H = h->H, I = h->I;
 
-  enum Kind { F32_COPY, F32_TRANSPOSE, PLANES, PLANES_GEGLU };
-  u16* dst_pk = nullptr;
-  u16* dst_ks = nullptr;  // additional k-streamed packing (attention Wo)
-  u16* dst_p32 = nullptr; // additional packing for the 32x32x16 whole-layer kernel
-  u16* const* dst_pp = nullptr;  // the wave-pair kernel's packs ([0] bf16, [1] fp16)
-  u16 *dst_f8a = nullptr, *dst_f8b = nullptr;  // "f16 + fp8" packs: chunked (a) or k-streamed fp16 (a) + e4m3 (b)
-  u16 *dst_p16 = nullptr, *dst_p8 = nullptr;   // ... on the panel path: fp16 slabs + e4m3 slabs
-  u16 *dst_pk_h16 = nullptr, *dst_ks_h16 = nullptr;  // kernel set "f16": the layouts of dst_pk / dst_ks with fp16 values
-  int p32_mode = 0, p32_kmajor = 0;
-  int pk_mode = -1;
-  int family = -1;        // op_gemm_family of a GEMM weight
-  Kind kind = F32_COPY;
+  bool transpose = false;
   float* dst_f32 = nullptr;
-  u16 *dst_hi = nullptr, *dst_lo = nullptr;
+  const WeightDesc* wd = nullptr;  // a GEMM weight ...
+  u16* const* packs = nullptr;     // ... and the layer's packs of it
   int64_t want0 = 0, want1 = 1;
   auto expect = [&](int64_t a, int64_t b) {
     want0 = a;
@@ -1295,7 +1292,7 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
   } else if (name == "model.final_norm.weight") {
     dst_f32 = h->final_norm; expect(H, 1);
   } else if (name == "head.dense.weight") {
-    dst_f32 = h->dense_t; kind = F32_TRANSPOSE; expect(H, H);
+    dst_f32 = h->dense_t; transpose = true; expect(H, H);
   } else if (name == "head.norm.weight") {
     dst_f32 = h->head_norm; expect(H, 1);
   } else if (name == "classifier.weight") {
@@ -1317,36 +1314,14 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
       dst_f32 = lw.attn_norm; expect(H, 1);
     } else if (t == "mlp_norm.weight") {
       dst_f32 = lw.mlp_norm; expect(H, 1);
-    } else if (t == "attn.Wqkv.weight") {
-      kind = PLANES; dst_hi = lw.wqkv_hi; dst_lo = lw.wqkv_lo; expect(3 * H, H);
-      dst_pk = lw.wqkv_pk; pk_mode = RE_QKV; family = OP_FAM_WQKV;
-      dst_p32 = lw.wqkv_p32; dst_pp = lw.wqkv_pp; p32_mode = L32_QKV; p32_kmajor = 0;
-      dst_f8a = lw.wqkv_f8;
-      dst_p16 = lw.wqkv_p16; dst_p8 = lw.wqkv_p8;
-      dst_pk_h16 = lw.wqkv_h16;
-    } else if (t == "attn.Wo.weight") {
-      kind = PLANES; dst_hi = lw.wo_hi; dst_lo = lw.wo_lo; expect(H, H);
-      dst_pk = nullptr; pk_mode = 101; dst_ks = lw.wo_ks; family = OP_FAM_ATTN_OUT;
-      dst_p32 = lw.wo_p32; dst_pp = lw.wo_pp; p32_mode = L32_RESID; p32_kmajor = 1;
-      dst_f8a = lw.wo_f16; dst_f8b = lw.wo_f8;
-      dst_p16 = lw.wo_p16; dst_p8 = lw.wo_p8;
-      dst_ks_h16 = lw.wo_h16;
-    } else if (t == "mlp.Wi.weight") {
-      kind = PLANES_GEGLU; dst_hi = lw.wi_hi; dst_lo = lw.wi_lo; expect(2 * I, H);
-      dst_pk = lw.wi_pk; pk_mode = RE_GEGLU; family = OP_FAM_WI;
-      dst_p32 = lw.wi_p32; dst_pp = lw.wi_pp; p32_mode = L32_GEGLU; p32_kmajor = 0;
-      dst_f8a = lw.wi_f8;
-      dst_p16 = lw.wi_p16; dst_p8 = lw.wi_p8;
-      dst_pk_h16 = lw.wi_h16;
-    } else if (t == "mlp.Wo.weight") {
-      kind = PLANES; dst_hi = lw.wo2_hi; dst_lo = lw.wo2_lo; expect(H, I);
-      dst_pk = lw.wo2_pk; pk_mode = 100; family = OP_FAM_MLP_OUT;  // k-streamed
-      dst_p32 = lw.wo2_p32; dst_pp = lw.wo2_pp; p32_mode = L32_RESID; p32_kmajor = 1;
-      dst_f8a = lw.wo2_f16;
-      dst_p16 = lw.wo2_p16; dst_p8 = lw.wo2_p8;
-      dst_pk_h16 = lw.wo2_h16;
     } else {
-      return fail(h, OP_ERR_INVALID, "op_load_weight: unknown tensor name '%s'", name_c);
+      for (int w = 0; w < W_COUNT; ++w)
+        if (t == kWeights[w].tail) {
+          wd = &kWeights[w];
+          packs = lw.pack[w];
+          expect((int64_t)weight_rows((Weight)w, H, I), (int64_t)weight_cols((Weight)w, H, I));
+        }
+      if (!wd) return fail(h, OP_ERR_INVALID, "op_load_weight: unknown tensor name '%s'", name_c);
     }
   }
   if (d0 != want0 || d1 != want1)
@@ -1367,124 +1342,19 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
   }
   const unsigned blocks = (unsigned)((count + 255) / 256);
   hipLaunchKernelGGL(convert_to_f32_kernel, dim3(blocks), dim3(256), 0, 0, raw, dtype, count, f32);
-  // A requested policy without the hi x lo(weight) term stores zeros in the lo plane (so that any kernel set gives
-  // that policy's numerics); `any_lo` records whether the tensor had a non-zero lo element at all.
-  int zero_lo = 0;
-  int* any_lo = h->any_lo_dev;
-  if (family >= 0) {
+  if (wd) {
     const int req_mask[OP_FAM_COUNT] = {h->req.wqkv, h->req.qk, h->req.pv, h->req.attn_out, h->req.wi, h->req.mlp_out};
-    zero_lo = (req_mask[family] & OP_TERM_RIGHT_LO) ? 0 : 1;
-    any_lo = h->any_lo_dev + family;
     h->resolved = false;
     // a kernel set pinned by op_select_kernel_set or measured by op_calibrate belongs to the weights it was chosen on: new
     // GEMM weights start from the default selection again (and from the compact formats, if op_set_compact_operands left them)
     h->forced_set = -1;
     h->forced_mlp_layers = ~0ull;
     h->f8_off = false;
-  }
-  switch (kind) {
-    case F32_COPY:
-      e = hipMemcpyAsync(dst_f32, f32, count * sizeof(float), hipMemcpyDeviceToDevice, 0);
-      break;
-    case F32_TRANSPOSE:
-      hipLaunchKernelGGL(transpose_f32_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, dst_f32);
-      break;
-    case PLANES:
-      if (dst_hi)
-        hipLaunchKernelGGL(split_planes_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, 0, dst_hi, dst_lo,
-                           zero_lo, any_lo);
-      break;
-    case PLANES_GEGLU:
-      if (dst_hi)
-        hipLaunchKernelGGL(split_planes_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, I, dst_hi, dst_lo,
-                           zero_lo, any_lo);
-      break;
-  }
-  if (h->panel_path && (dst_pk || dst_ks)) {
-    // panel-major packing: [panel][k-step][plane][16 fragments][512], rows permuted per consumer (panel_source_row)
-    const int K = (int)d1;
-    auto pack = [&](int n_tiles, int mode, u16* dst) {
-      const size_t total = (size_t)n_tiles * 256 * K;
-      hipLaunchKernelGGL(pack_panel_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, f32, n_tiles, K, mode,
-                         H, I, dst, zero_lo, any_lo);
-    };
-    if (dst_p16) {  // the fp16 + e4m3 packs of the same panels (kernel sets 3 / 4)
-      int* not_f16 = h->any_lo_dev + OP_FAM_COUNT;
-      const size_t lo_off = count;  // bytes of the whole tensor's e4m3(w) slabs: the lo(w) slabs follow
-      auto pack8 = [&](int n_tiles, int mode, int tile0) {
-        const size_t total = (size_t)n_tiles * 256 * K;
-        hipLaunchKernelGGL(pack_panel_f8_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, f32, n_tiles, K, mode, H, I,
-                           dst_p16 + (size_t)tile0 * 256 * K, dst_p8 + (size_t)tile0 * 256 * K / 2, lo_off, zero_lo, not_f16, h->f16_fit_dev);
-      };
-      if (pk_mode == RE_QKV) {
-        pack8(2 * H / 256, PE_QK, 0);
-        pack8(H / 256, PE_V, 2 * H / 256);
-      } else if (pk_mode == RE_GEGLU) {
-        pack8(I / 128, PE_GEGLU, 0);
-      } else {
-        pack8(H / 256, PE_RESIDUAL, 0);
-      }
-      hipLaunchKernelGGL(weight_energy_kernel, dim3(256), dim3(256), 0, 0, f32, count, h->f16_fit_dev);
-      hipLaunchKernelGGL(f16_fit_close_tensor_kernel, dim3(1), dim3(1), 0, 0, not_f16, h->f16_fit_dev);
-    }
-    if (pk_mode == RE_QKV) {
-      pack(2 * H / 256, PE_QK, dst_pk);
-      pack(H / 256, PE_V, dst_pk + (size_t)(2 * H / 256) * (K / 32) * 2 * 8192);
-    } else if (pk_mode == 101) {
-      pack(H / 256, PE_RESIDUAL, dst_ks);  // attention output projection
-    } else if (pk_mode == RE_GEGLU) {
-      pack(I / 128, PE_GEGLU, dst_pk);
-    } else {
-      pack(H / 256, PE_RESIDUAL, dst_pk);  // MLP output projection
-    }
-    if (dst_pk_h16 || dst_ks_h16) {  // kernel set "f16": the same panels with fp16 values
-      auto pack16 = [&](int n_tiles, int mode, u16* dst) {
-        const size_t total = (size_t)n_tiles * 256 * K;
-        hipLaunchKernelGGL(pack_panel_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, f32, n_tiles, K, mode,
-                           H, I, dst, 1, any_lo, 1);
-      };
-      if (pk_mode == RE_QKV) {
-        pack16(2 * H / 256, PE_QK, dst_pk_h16);
-        pack16(H / 256, PE_V, dst_pk_h16 + (size_t)(2 * H / 256) * (K / 32) * 2 * 8192);
-      } else if (pk_mode == 101) {
-        pack16(H / 256, PE_RESIDUAL, dst_ks_h16);
-      } else if (pk_mode == RE_GEGLU) {
-        pack16(I / 128, PE_GEGLU, dst_pk_h16);
-      } else {
-        pack16(H / 256, PE_RESIDUAL, dst_pk_h16);
-      }
-    }
-  }
-  if ((dst_pk || dst_ks) && h->row_path) {
-    if (dst_pk && pk_mode == 100)
-      hipLaunchKernelGGL(pack_kstream_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, 1, dst_pk, zero_lo, any_lo);
-    else if (dst_pk)
-      hipLaunchKernelGGL(pack_rowgemm_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, pk_mode, H, I, dst_pk,
-                         zero_lo, any_lo);
-    if (dst_ks)
-      hipLaunchKernelGGL(pack_kstream_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, 1, dst_ks, zero_lo, any_lo);
-    // kernel set "f16": the same layouts with fp16 values in the hi plane
-    if (dst_pk_h16 && pk_mode == 100)
-      hipLaunchKernelGGL(pack_kstream_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, 1, dst_pk_h16, 1, any_lo, 1);
-    else if (dst_pk_h16)
-      hipLaunchKernelGGL(pack_rowgemm_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, pk_mode, H, I, dst_pk_h16, 1, any_lo, 1);
-    if (dst_ks_h16)
-      hipLaunchKernelGGL(pack_kstream_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, 1, dst_ks_h16, 1, any_lo, 1);
-    if (dst_f8a) {  // "f16 + fp8" kernel set; raises the not-fp16 flag (any_lo_dev[OP_FAM_COUNT]) for a weight it cannot hold exactly
-      int* not_f16 = h->any_lo_dev + OP_FAM_COUNT;
-      if (pk_mode == 100 || pk_mode == 101)
-        hipLaunchKernelGGL(pack_kstream_f8_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, 1, dst_f8a, dst_f8b, zero_lo, not_f16, h->f16_fit_dev);
-      else
-        hipLaunchKernelGGL(pack_rowgemm_f8_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, pk_mode, H, I, dst_f8a, zero_lo, not_f16, h->f16_fit_dev);
-      hipLaunchKernelGGL(weight_energy_kernel, dim3(256), dim3(256), 0, 0, f32, count, h->f16_fit_dev);
-      hipLaunchKernelGGL(f16_fit_close_tensor_kernel, dim3(1), dim3(1), 0, 0, not_f16, h->f16_fit_dev);
-    }
-    if (dst_p32)  // the 32x32x16 whole-layer kernel's order (hi plane; that kernel runs only when the lo planes are zero)
-      hipLaunchKernelGGL(pack_layer32_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, p32_mode, p32_kmajor, H, I,
-                         dst_p32);
-    for (int f = 0; dst_pp && f < 2; ++f)  // (the modes of Layer32Pack and Layer16pPack are the same numbers)
-      if (dst_pp[f])
-        hipLaunchKernelGGL(pack_layer16p_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, p32_mode, p32_kmajor, H, I, dst_pp[f], f);
+    WeightPacker{h, *wd, f32, (int)d0, (int)d1, (req_mask[wd->family] & OP_TERM_RIGHT_LO) ? 0 : 1, h->any_lo_dev + wd->family}.run(packs);
+  } else if (transpose) {
+    hipLaunchKernelGGL(transpose_f32_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, dst_f32);
+  } else {
+    e = hipMemcpyAsync(dst_f32, f32, count * sizeof(float), hipMemcpyDeviceToDevice, 0);
   }
   if (e == hipSuccess) e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(0);
@@ -1498,57 +1368,35 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
 }  // extern "C"
 
 namespace {
-// op_kernel_set number of the handle's current selection (op_effective_policy)
-int public_set(const op_handle* h) {
-  if (h->emulate) return -1;
-  if (h->pi == opl::PI_F16 && h->mlp_f8) return h->mlp_wlo ? OP_KS_F16_MLP_F8_W : OP_KS_F16_MLP_F8;
-  if (h->pi == opl::PI_F16) return OP_KS_F16;
-  if (h->attn_f16 && h->pi == opl::PI_F16_F8_W) return OP_KS_F16_F8_W_ATTN_F16;
-  if (h->attn_f16 && h->pi == opl::PI_F16_F8) return OP_KS_F16_F8_ATTN_F16;
-  return h->wi_f8 ? 5 + h->pi : h->pi;  // 5 / 6: sets 0 / 1 with the Wi GEMM in the fp16 + e4m3 format
-}
-
 // Can this handle run kernel set `set` (op_kernel_set numbering)?  Packs present, a path that has the kernels, and no
-// weight tensor below the reach of an fp16 plane for the sets that carry one.
+// weight tensor below the reach of an fp16 plane for the sets that carry one: the set's `needs` (op_sets.h).
 bool set_available(const op_handle* h, int set) {
-  const bool fast_path = h->row_path || h->panel_path;
-  const bool row_layer_ok = !h->row_path || !(h->cfg.flags & (OP_FLAG_NO_LAYER_FUSION | OP_FLAG_LAYER_8X16 | OP_FLAG_LAYER_M32));
+  if (set < 0 || set >= OP_KS_COUNT) return false;
   if (h->cfg.flags & OP_FLAG_NO_POLICY_KERNELS) return set == OP_KS_BF16X3;
-  switch (set) {
-    case OP_KS_BF16X3: return true;
-    case OP_KS_BF16_WEIGHTS:
-    case OP_KS_BF16: return fast_path;
-    case OP_KS_F16_F8:
-    case OP_KS_F16_F8_W: return fast_path && h->f8_packs && !h->f16_unfit && row_layer_ok;
-    case OP_KS_BF16X3_WI_F8:
-    case OP_KS_BF16_WEIGHTS_WI_F8: return h->panel_path && h->f8_packs && !h->f16_unfit;
-    case OP_KS_F16: return h->h16_packs && !h->f16_unfit && row_layer_ok;
-    case OP_KS_F16_MLP_F8_W:
-    case OP_KS_F16_MLP_F8: return h->panel_path && h->h16_packs && h->f8_packs && !h->f16_unfit;
-    case OP_KS_F16_F8_W_ATTN_F16:
-    case OP_KS_F16_F8_ATTN_F16: return h->panel_path && h->f8_packs && !h->f16_unfit;
-    default: return false;
-  }
+  const unsigned needs = kKernelSets[set].needs;
+  if ((needs & NEED_FAST) && !h->row_path && !h->panel_path) return false;
+  if ((needs & NEED_PANEL) && !h->panel_path) return false;
+  if ((needs & NEED_F8_PACKS) && !h->f8_packs) return false;
+  if ((needs & NEED_H16_PACKS) && !h->h16_packs) return false;
+  if ((needs & NEED_F16_FIT) && h->f16_unfit) return false;
+  if ((needs & NEED_ROW_LAYER) && h->row_path && (h->cfg.flags & (OP_FLAG_NO_LAYER_FUSION | OP_FLAG_LAYER_8X16 | OP_FLAG_LAYER_M32)))
+    return false;
+  return true;
 }
 
-// Run kernel set `set`: the evaluated terms become the set's own (a set with fewer terms than the checkpoint carries is
-// an approximation -- op_calibrate measures it before choosing it).
-void apply_set(op_handle* h, int set) {
-  h->wi_f8 = set == OP_KS_BF16X3_WI_F8 || set == OP_KS_BF16_WEIGHTS_WI_F8;
-  h->mlp_f8 = set == OP_KS_F16_MLP_F8_W || set == OP_KS_F16_MLP_F8;
-  h->mlp_wlo = set == OP_KS_F16_MLP_F8_W;
-  h->mlp_layers = (h->mlp_f8 && set == h->forced_set) ? h->forced_mlp_layers : ~0ull;
-  h->attn_f16 = set == OP_KS_F16_F8_W_ATTN_F16 || set == OP_KS_F16_F8_ATTN_F16;
-  h->pi = (set == OP_KS_F16 || h->mlp_f8) ? opl::PI_F16 : (h->wi_f8 ? set - 5 : set);
-  if (h->attn_f16) h->pi = set == OP_KS_F16_F8_W_ATTN_F16 ? opl::PI_F16_F8_W : opl::PI_F16_F8;
-  h->eff = opl::kPolicies[h->pi];
-  if (h->attn_f16) h->eff.qk = h->eff.pv = 0;
-  h->emulate = false;
+// MFMA pipe time per algorithmic product of a kernel set on this handle's path: op_calibrate's order of candidates
+float set_cost(const op_handle* h, int set) { return h->panel_path ? kKernelSets[set].cost_panel : kKernelSets[set].cost_row; }
+
+// The forward runs kernel set `set`; -1: the all-terms kernels with the lo operands `eff` does not carry cleared.
+void use_set(op_handle* h, int set) {
+  h->set = set;
+  h->ks = set >= 0 ? &kKernelSets[set] : &kClearedOperands;
+  h->mlp_layers = (mlp_by_layer(*h->ks) && set == h->forced_set) ? h->forced_mlp_layers : ~0ull;
 }
 
 // Evaluated policy = requested policy minus the hi x lo(weight) terms whose lo planes are identically zero for this
-// checkpoint (bf16 weights: dropping the term changes no bit of the result), then the curated kernel set that has
-// exactly those terms -- or kernel set 0 with the unused lo operands cleared.
+// checkpoint (bf16 weights: dropping the term changes no bit of the result), then the kernel set that has exactly those
+// terms -- or the all-terms kernels with the unused lo operands cleared.
 int resolve_policy(op_handle* h) {
   if (h->resolved) return OP_OK;
   // [OP_FAM_COUNT]: some GEMM weight is not exactly an fp16 value; [+ 2]: some weight TENSOR sits on fp16's subnormal grid
@@ -1562,68 +1410,37 @@ int resolve_policy(op_handle* h) {
   if (!any_lo[OP_FAM_WI]) e.wi &= ~OP_TERM_RIGHT_LO;
   if (!any_lo[OP_FAM_MLP_OUT]) e.mlp_out &= ~OP_TERM_RIGHT_LO;
   h->eff = e;
-  h->pi = 0;
-  h->emulate = true;
-  h->wi_f8 = false;
-  h->mlp_f8 = h->mlp_wlo = false;
-  h->mlp_layers = ~0ull;
-  h->attn_f16 = false;
-  if (!(h->cfg.flags & OP_FLAG_NO_POLICY_KERNELS)) {
-    for (int i = 0; i < opl::N_POLICIES; ++i)
-      if (opl::kPolicies[i] == e) {
-        h->pi = i;
-        h->emulate = false;
-        break;
-      }
-    // bf16-valued weights that are also exact fp16 values, on the whole-layer kernel's shapes: the "f16 + fp8" kernel
-    // set evaluates the same terms at 1.5 instead of 2 MFMA units per product (op_internal.h)
-    const bool f8_ok = !h->emulate && h->f8_packs && !h->f8_off && !any_lo[OP_FAM_COUNT + 2] &&
-                       !(h->cfg.flags & (OP_FLAG_NO_LAYER_FUSION | OP_FLAG_LAYER_8X16 | OP_FLAG_LAYER_M32));
-    // Panel path (hidden 512 / 768).  The whole layer in the format (OP_FLAG_PANEL_F8) costs 0.45-1.0e-3 on logits at the
-    // published depths: opt-in.  The Wi GEMM ALONE -- 52 % of the GEMM FLOPs -- costs 1-1.5e-4 (base / large / en-gte at
-    // 19-25 layers: <= 5.4e-4 against the oracle where the (hi, lo) bf16 sets give <= 4.7e-4; scripts/f8_depth_check.py,
-    // profiles/r04_f8_depth_check.txt) and takes the fp32-valued Wi GEMM from 3 to 2 MFMA units per product: +5.6 %
-    // pairs/s on base -- the DEFAULT for fp32-valued weights.  For bf16-valued weights (2 -> 1.5 units in a GEMM that
-    // is not pipe-bound there) it measures +0.7 %: only on request (OP_FLAG_PANEL_F8_WI).
-    const bool full_f8 = h->row_path || (h->cfg.flags & OP_FLAG_PANEL_F8);
-    const bool wi_only = h->panel_path && !full_f8;
-    h->wi_f8 = wi_only && f8_ok &&
-               (h->pi == opl::PI_ALL_TERMS || ((h->cfg.flags & OP_FLAG_PANEL_F8_WI) && h->pi == opl::PI_BF16_WEIGHTS && !any_lo[OP_FAM_COUNT]));
-    if (!wi_only) {
-      if (f8_ok && h->pi == opl::PI_BF16_WEIGHTS && !any_lo[OP_FAM_COUNT]) h->pi = opl::PI_F16_F8;
-      // every term requested and carried (fp32-valued weights): the same format with the weights' lo part as a third
-      // plane -- one kernel per layer at 2 MFMA units per product instead of two kernels at 3
-      if (f8_ok && h->pi == opl::PI_ALL_TERMS) h->pi = opl::PI_F16_F8_W;
-    }
-  } else if (opl::kPolicies[0] == e) {
-    h->emulate = false;
-  }
   h->f16_unfit = any_lo[OP_FAM_COUNT + 2] != 0;
-  h->default_set = public_set(h);
-  // a kernel set pinned by op_select_kernel_set / chosen by op_calibrate replaces the default selection
-  if (h->forced_set >= 0 && set_available(h, h->forced_set)) apply_set(h, h->forced_set);
+  // the default selection: the (hi, lo) bf16 set with exactly these terms (OP_FLAG_NO_POLICY_KERNELS: the all-terms one only)
+  int set = -1;
+  const int n_bf16_sets = (h->cfg.flags & OP_FLAG_NO_POLICY_KERNELS) ? 1 : OP_KS_BF16 + 1;
+  for (int s = n_bf16_sets - 1; s >= 0; --s)
+    if (kKernelSets[s].terms == e) set = s;
+  // bf16-valued weights that are also exact fp16 values, on the whole-layer kernel's shapes: the "f16 + fp8" kernel
+  // set evaluates the same terms at 1.5 instead of 2 MFMA units per product (op_internal.h)
+  const bool f8_ok = set >= 0 && h->f8_packs && !h->f8_off && !h->f16_unfit &&
+                     !(h->cfg.flags & (OP_FLAG_NO_POLICY_KERNELS | OP_FLAG_NO_LAYER_FUSION | OP_FLAG_LAYER_8X16 | OP_FLAG_LAYER_M32));
+  const bool exact_f16 = !any_lo[OP_FAM_COUNT];
+  // Panel path (hidden 512 / 768).  The whole layer in the format (OP_FLAG_PANEL_F8) costs 0.45-1.0e-3 on logits at the
+  // published depths: opt-in.  The Wi GEMM ALONE -- 52 % of the GEMM FLOPs -- costs 1-1.5e-4 (base / large / en-gte at
+  // 19-25 layers: <= 5.4e-4 against the oracle where the (hi, lo) bf16 sets give <= 4.7e-4; scripts/f8_depth_check.py,
+  // profiles/r04_f8_depth_check.txt) and takes the fp32-valued Wi GEMM from 3 to 2 MFMA units per product: +5.6 %
+  // pairs/s on base -- the DEFAULT for fp32-valued weights.  For bf16-valued weights (2 -> 1.5 units in a GEMM that
+  // is not pipe-bound there) it measures +0.7 %: only on request (OP_FLAG_PANEL_F8_WI).
+  const bool wi_only = h->panel_path && !(h->cfg.flags & OP_FLAG_PANEL_F8);
+  // every term requested and carried (fp32-valued weights): the same format with the weights' lo part as a third
+  // plane -- one kernel per layer at 2 MFMA units per product instead of two kernels at 3
+  if (f8_ok && set == OP_KS_BF16X3) set = wi_only ? OP_KS_BF16X3_WI_F8 : OP_KS_F16_F8_W;
+  else if (f8_ok && set == OP_KS_BF16_WEIGHTS && exact_f16 && (!wi_only || (h->cfg.flags & OP_FLAG_PANEL_F8_WI)))
+    set = wi_only ? OP_KS_BF16_WEIGHTS_WI_F8 : OP_KS_F16_F8;
+  // A kernel set pinned by op_select_kernel_set / chosen by op_calibrate replaces the default selection, and the evaluated
+  // terms become the set's own (a set with fewer terms than the checkpoint carries is an approximation -- op_calibrate
+  // measures it before choosing it).
+  const bool pinned = h->forced_set >= 0 && set_available(h, h->forced_set);
+  use_set(h, pinned ? h->forced_set : set);
+  if (pinned) h->eff = h->ks->terms;
   h->resolved = true;
   return OP_OK;
-}
-
-// ---- calibration: the cheapest kernel set whose outputs stay within `tolerance` of the (hi, lo) bf16 kernels' ----------
-// MFMA pipe time per algorithmic product of each kernel set, in 16-bit units (the panel path's sets 4
-// and 5 measured in that order on base: 5.15 k vs 4.80 k pairs/s).  Candidates are tried in this order.
-float set_cost(const op_handle* h, int set) {
-  switch (set) {
-    case OP_KS_F16: return 1.0f;
-    case OP_KS_BF16: return 1.01f;  // same MFMA count as "f16", 8 instead of 11 significant bits: tried second
-    case OP_KS_F16_MLP_F8: return 1.375f;
-    case OP_KS_F16_F8_ATTN_F16: return 1.45f;
-    case OP_KS_F16_F8: return 1.5f;
-    case OP_KS_F16_MLP_F8_W: return 1.74f;
-    case OP_KS_BF16_WEIGHTS_WI_F8: return 1.75f;
-    case OP_KS_F16_F8_W_ATTN_F16: return 1.9f;
-    case OP_KS_BF16_WEIGHTS: return 2.0f;
-    case OP_KS_F16_F8_W: return h->panel_path ? 2.1f : 1.99f;
-    case OP_KS_BF16X3_WI_F8: return 2.5f;
-    default: return 3.0f;
-  }
 }
 
 // deterministic calibration batch: 24 rows of min(512, max_pos) tokens + 14 ragged rows, ids uniform over the vocabulary
@@ -1674,7 +1491,7 @@ int op_set_compact_operands(op_handle* h, int enabled, int* changed) {
   if (!h) return fail(nullptr, OP_ERR_INVALID, "op_set_compact_operands: NULL handle");
   int rc = op_weights_ready(h);
   if (rc != OP_OK) return rc;
-  const int before = public_set(h);
+  const int before = h->set;
   h->f8_off = enabled == 0;
   if (!enabled) {  // a pinned / calibrated compact set goes too
     h->forced_set = -1;
@@ -1682,7 +1499,7 @@ int op_set_compact_operands(op_handle* h, int enabled, int* changed) {
   }
   h->resolved = false;
   rc = resolve_policy(h);
-  if (changed) *changed = (rc == OP_OK && public_set(h) != before) ? 1 : 0;
+  if (changed) *changed = (rc == OP_OK && h->set != before) ? 1 : 0;
   return rc;
 }
 
@@ -1704,7 +1521,7 @@ int op_mlp_correction_layers(op_handle* h, uint64_t* layer_mask) {
   if (rc != OP_OK) return rc;
   const int n = h->cfg.num_layers;
   const uint64_t all = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-  *layer_mask = h->mlp_f8 ? (h->mlp_layers & all) : 0ull;
+  *layer_mask = mlp_by_layer(*h->ks) ? (h->mlp_layers & all) : 0ull;
   return OP_OK;
 }
 
@@ -1758,11 +1575,11 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   h->forced_mlp_layers = ~0ull;
   h->resolved = false;
   OP_TRY(resolve_policy(h));
-  const int default_set = public_set(h);
+  const int default_set = h->set;
   h->f8_off = true;
   h->resolved = false;
   OP_TRY(resolve_policy(h));
-  const int reference_set = public_set(h);
+  const int reference_set = h->set;
   h->f8_off = f8_off_before;
   h->resolved = false;
   OP_TRY(resolve_policy(h));
@@ -1785,7 +1602,7 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
     h->forced_mlp_layers = forced_mlp_before;
     h->resolved = false;
     OP_TRY(resolve_policy(h));
-    rep.chosen_set = public_set(h);
+    rep.chosen_set = h->set;
     return finish();
   };
   if (default_set < 0 || reference_set < 0) return finish_unchanged();  // a custom policy on the all-terms kernels: nothing cheaper is defined
@@ -1945,8 +1762,8 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   const int rc2 = resolve_policy(h);
   if (rc != OP_OK) return rc;
   if (rc2 != OP_OK) return rc2;
-  rep.chosen_set = public_set(h);
-  rep.mlp_layers = h->mlp_f8 ? (h->mlp_layers & all_layers) : 0ull;
+  rep.chosen_set = h->set;
+  rep.mlp_layers = mlp_by_layer(*h->ks) ? (h->mlp_layers & all_layers) : 0ull;
   return finish();
 }
 
@@ -1960,7 +1777,7 @@ int op_effective_policy(op_handle* h, uint8_t* terms_out, int* kernel_set) {
   terms_out[OP_FAM_ATTN_OUT] = (uint8_t)h->eff.attn_out;
   terms_out[OP_FAM_WI] = (uint8_t)h->eff.wi;
   terms_out[OP_FAM_MLP_OUT] = (uint8_t)h->eff.mlp_out;
-  *kernel_set = public_set(h);
+  *kernel_set = h->set;
   return OP_OK;
 }
 
@@ -2274,8 +2091,8 @@ int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_se
 // detour through the reference set and back finds the coverage as it left it.
 static int coverage_prepare(op_handle* h, hipStream_t stream) {
   OP_HIP(h, hipSetDevice(h->cfg.device_id));
-  const int set = h->resolved ? public_set(h) : -2;
-  const uint64_t mlp = (h->resolved && h->mlp_f8) ? h->mlp_layers : 0ull;
+  const int set = h->resolved ? h->set : -2;
+  const uint64_t mlp = (h->resolved && mlp_by_layer(*h->ks)) ? h->mlp_layers : 0ull;
   if (h->cov_clear || set != h->cov_set || mlp != h->cov_mlp_layers) {
     OP_HIP(h, hipMemsetAsync(h->cov_bits, 0, (((size_t)h->V + 31) / 32) * sizeof(uint32_t), stream));
     OP_HIP(h, hipMemsetAsync(h->cov_state, 0, opl::COV_WORDS * sizeof(uint32_t), stream));

@@ -113,6 +113,21 @@ FLAG_RUNS = {
 }
 # the three attention families of the window sweep: (model, set)
 WINDOW_RUNS = [("row", "bf16x3"), ("row", "f16"), ("panel512", "f16-f8-w+attn-f16")]
+# the evaluated term masks a pinned set reports, in _lib.OP_FAMILIES order (wqkv, qk, pv, attn_out, wi, mlp_out)
+SET_TERMS = {
+    "bf16x3": (3, 3, 3, 3, 3, 3),
+    "bf16-weights": (1, 3, 3, 1, 1, 1),
+    "bf16": (0, 0, 0, 0, 0, 0),
+    "f16-f8": (1, 3, 3, 1, 1, 1),
+    "f16-f8-w": (3, 3, 3, 3, 3, 3),
+    "bf16x3+wi-f16-f8-w": (3, 3, 3, 3, 3, 3),
+    "bf16-weights+wi-f16-f8": (1, 3, 3, 1, 1, 1),
+    "f16": (0, 0, 0, 0, 0, 0),
+    "f16+mlp-f16-f8-w": (0, 0, 0, 0, 0, 0),
+    "f16+mlp-f16-f8": (0, 0, 0, 0, 0, 0),
+    "f16-f8-w+attn-f16": (3, 0, 0, 3, 3, 3),
+    "f16-f8+attn-f16": (1, 0, 0, 1, 1, 1),
+}
 
 TABLE: list[str] = []
 
@@ -279,6 +294,7 @@ def _check(model, kernel_set, flag_names, recipe, window, lengths=tuple(LENGTHS)
 # -- which sets each path has -------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("model,flag", [(m, None) for m in MODELS] + [k for k in SUPPORTED_WITH_FLAG])
 def test_supported_sets_are_exactly_the_expected_ones(model, flag):
+    from open_provence_amd import _lib
     from open_provence_amd._lib import HipLibraryError
     from open_provence_amd.engine import HipEncoder
 
@@ -289,7 +305,9 @@ def test_supported_sets_are_exactly_the_expected_ones(model, flag):
         for name in ALL_SETS:
             if name in expected:
                 enc.select_kernel_set(name)
-                assert enc.effective_policy()["kernel_set"] == name
+                policy = enc.effective_policy()
+                assert policy["kernel_set"] == name
+                assert tuple(policy["terms"][f] for f in _lib.OP_FAMILIES) == SET_TERMS[name], (name, policy["terms"])
             else:
                 with pytest.raises(HipLibraryError):
                     enc.select_kernel_set(name)
