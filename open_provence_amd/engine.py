@@ -2,21 +2,26 @@
 
 PyTorch-ROCm is used here for exactly three things -- owning device buffers (ids, outputs, workspace),
 naming the current HIP stream, and reading checkpoint tensors -- never for arithmetic on the forward
-path.  Everything numerical happens inside ``op_forward_packed`` (``include/open_provence_hip.h``).
+path.  Everything numerical happens inside ``op_forward_packed`` (``include/open_provence_hip.h``).  How a calibrated kernel
+set is re-checked on real batches -- the policy, its state and the one audit path -- is ``audit.py``; the encoder supplies the
+device steps.
 """
 
 from __future__ import annotations
 
 import ctypes
 import os
-from contextlib import contextmanager
+import warnings
+from contextlib import contextmanager, nullcontext
 from dataclasses import dataclass
-from typing import Iterator, Mapping, Sequence
+from typing import Iterator, Mapping, NamedTuple, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib
+from .audit import (DEFAULT_AUDIT_TOKENS, DEFAULT_CALIBRATION_TOLERANCE, MIN_AUDIT_TOKENS, AuditState, coverage_counts,  # noqa: F401
+                    first_batch_audit, maybe_audit, resolve_audit_mode, select_audit_rows)
 from .config import EncoderDims
 from .packing import pack_rows
 
@@ -53,6 +58,25 @@ class HiddenRequest:
     pad_width: int = 0
 
 
+class PackedCall(NamedTuple):
+    """What one ``op_forward_packed[_hidden]`` call needs: the batch, where its logits go, and what it runs with."""
+
+    ids: torch.Tensor  # int32 [total] on the device
+    cu_seqlens: torch.Tensor  # int32 [n_seqs + 1] on the device
+    cu_host: np.ndarray  # the same, int32, on the host
+    n_seqs: int
+    total: int
+    max_seqlen: int
+    prune: torch.Tensor  # fp32 [total, 2]: written by the call
+    rank: torch.Tensor  # fp32 [n_seqs, num_labels]: written by the call
+    keep_prob: "torch.Tensor | None"
+    ws: "torch.Tensor | None"  # uint8 workspace (None only for an empty batch, which is never launched)
+    stream: int  # raw HIP stream
+    hidden_req: "_lib.OpHiddenRequest | None" = None
+    ids_host: "np.ndarray | None" = None
+    rows: "torch.Tensor | None" = None  # of an audit's sub-batch: the rows it was gathered from (int32 on the device)
+
+
 def parse_precision(precision: "str | Mapping[str, int]") -> tuple[int, list[int]]:
     """``"bf16x3" | "bf16x2" | "bf16"`` or a per-family term-mask mapping / ``"wqkv=1,qk=3,..."`` string
     (families: ``_lib.OP_FAMILIES``; mask bit 0 = lo(activation) x hi, bit 1 = hi x lo(weight / key / value);
@@ -77,7 +101,6 @@ def parse_precision(precision: "str | Mapping[str, int]") -> tuple[int, list[int
     return _lib.OP_PRECISION_CUSTOM, terms
 _DTYPES = {torch.float32: _lib.OP_DTYPE_F32, torch.bfloat16: _lib.OP_DTYPE_BF16, torch.float16: _lib.OP_DTYPE_F16}
 
-DEFAULT_CALIBRATION_TOLERANCE = 1e-4  # max |logit difference| to the (hi, lo) bf16 kernels; the path's bar is 1e-3
 PATH_TOLERANCE = 1e-3  # BASELINE.json north_star: logits within 1e-3 of the fp32 CPU reference
 
 
@@ -110,62 +133,6 @@ def resolve_calibration_tolerance(calibrate: "bool | float | None") -> float:
         except ValueError as exc:
             raise ValueError(f"OPEN_PROVENCE_CALIBRATE must be 0 / off or a tolerance below {PATH_TOLERANCE:g}, got {env!r}") from exc
     return DEFAULT_CALIBRATION_TOLERANCE
-
-
-AUDIT_MODES = ("off", "first", "running")
-# Tokens one running audit may re-run on the reference set.  A forward of up to 16 k tokens sits at the 0.68 - 0.72 ms launch
-# floor on xsmall (profiles/r06_small_request.txt), so half of that is priced like the smallest forward -- ON THE CHOSEN SET: what
-# the reference set costs at this size has not been measured.
-DEFAULT_AUDIT_TOKENS = 8192
-MIN_AUDIT_TOKENS = 64  # batches below this are not audited (first-batch audit and running audit alike)
-
-
-def resolve_audit_mode(audit: "str | bool | None") -> str:
-    """``"off" | "first" | "running"``; ``False`` / ``True`` = ``"off"`` / ``"first"``; ``None`` = ``OPEN_PROVENCE_AUDIT``
-    (``0 / off / false / no`` -> ``"off"``, ``running`` -> ``"running"``, anything else or unset -> ``"first"``)."""
-
-    if isinstance(audit, (bool, np.bool_)):
-        return "first" if audit else "off"
-    if audit is None:
-        env = os.environ.get("OPEN_PROVENCE_AUDIT", "1").strip().lower()
-        return "off" if env in ("0", "off", "false", "no") else "running" if env == "running" else "first"
-    mode = str(audit).strip().lower()
-    if mode not in AUDIT_MODES:
-        raise ValueError(f"audit must be one of {AUDIT_MODES}, got {audit!r}")
-    return mode
-
-
-def coverage_counts(ids: np.ndarray, cu_seqlens: np.ndarray, covered: np.ndarray) -> np.ndarray:
-    """Per row of a packed batch, the positions whose token id is not in ``covered`` (bool ``[vocab]``): what
-    ``op_coverage_scan`` writes to ``row_novel_dev``.  Duplicates count once per position; an id outside the table is novel."""
-
-    ids = np.asarray(ids).astype(np.int64, copy=False)
-    inside = (ids >= 0) & (ids < covered.shape[0])
-    novel = np.ones(ids.shape[0], dtype=bool)
-    novel[inside] = ~covered[ids[inside]]
-    csum = np.concatenate(([0], np.cumsum(novel, dtype=np.int64)))
-    cu = np.asarray(cu_seqlens, dtype=np.int64)
-    return (csum[cu[1:]] - csum[cu[:-1]]).astype(np.int32)
-
-
-def select_audit_rows(row_novel: "Sequence[int]", lengths: "Sequence[int]", budget: int, longest: "int | None" = None) -> list[int]:
-    """The rows one running audit re-runs: ``longest`` first (the index of the batch's longest row, given when the length
-    trigger fired), then by (novel positions descending, length descending, index ascending) until the next row would take
-    the sub-batch past ``budget`` tokens.  At least one row is always taken, whatever its length; no rows give ``[]``."""
-
-    n = len(row_novel)
-    if n == 0:
-        return []
-    order = sorted(range(n), key=lambda i: (-int(row_novel[i]), -int(lengths[i]), i))
-    if longest is not None:
-        order = [int(longest)] + [i for i in order if i != int(longest)]
-    picked, tokens = [], 0
-    for i in order:
-        if picked and tokens + int(lengths[i]) > int(budget):
-            break
-        picked.append(i)
-        tokens += int(lengths[i])
-    return picked
 
 
 def require_gpu(device: torch.device | str | int | None = None) -> torch.device:
@@ -204,7 +171,7 @@ class HipEncoder:
     ) -> None:
         """``audit`` / ``audit_every`` / ``audit_tokens``: how a kernel set chosen by :meth:`calibrate` is re-checked on real
         batches -- ``"first"`` (default; ``None`` reads ``OPEN_PROVENCE_AUDIT``): once, on the first real batch
-        (:meth:`_audit_first_batch`); ``"running"``: also later, see :meth:`_maybe_audit`; ``"off"``: never."""
+        (``audit.first_batch_audit``); ``"running"``: also later, see ``audit.maybe_audit``; ``"off"``: never."""
 
         self.audit_mode = resolve_audit_mode(audit)
         self.audit_every = int(audit_every)
@@ -259,6 +226,12 @@ class HipEncoder:
         self._capture: torch.Tensor | None = None
         self._capture_result: torch.Tensor | None = None
         self.calibration: dict | None = None  # report of the last calibrate() (load_state_dict runs it by default)
+        self.audit_state = AuditState(dims.vocab_size)
+        self.audit_factor = 3.0  # an audit's bound, in calibration tolerances
+        self.audit_collective = False  # under a process group the ranks audit TOGETHER (sharding.collective_audit)
+        self.fallbacks = 0  # fp16 range-guard fallbacks: reported by process() (timing / performance_trace)
+        self._f8_active: bool | None = None  # cache of f8_active(); None = ask the handle
+        self._profiling = False
 
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self) -> None:
@@ -309,8 +282,8 @@ class HipEncoder:
         # for every GEMM weight that changes (ABI 8); a state dict that reloads only norms / heads / embeddings keeps the
         # weights the set was measured on, but the measurement covered those tensors too -- back to the default selection.
         _lib.check(self.lib, self._handle, self.lib.op_select_kernel_set(self._handle, int(_lib.OP_KS_AUTO)), "op_select_kernel_set(auto)")
-        self.__dict__["_f8_active"] = None
-        self.__dict__["_audit_pending"] = False
+        self._f8_active = None
+        self.audit_state.pending = False
         self._reset_coverage(running=False)
         self.calibration = None
         pinned = kernel_set or os.environ.get("OPEN_PROVENCE_KERNEL_SET")
@@ -326,7 +299,7 @@ class HipEncoder:
         fewer product terms than the checkpoint carries is an approximation: :meth:`calibrate` is what measures one."""
 
         self._select_kernel_set(name)
-        self.__dict__["_audit_pending"] = False  # (a pinned set is the caller's decision: nothing to audit)
+        self.audit_state.pending = False  # (a pinned set is the caller's decision: nothing to audit)
         self._reset_coverage(running=False)
 
     def _select_kernel_set(self, name: "str | None") -> None:
@@ -336,7 +309,7 @@ class HipEncoder:
         if number is None:
             raise ValueError(f"unknown kernel set {name!r}; expected one of {sorted(_lib.KERNEL_SET_IDS)} or 'auto'")
         _lib.check(self.lib, self._handle, self.lib.op_select_kernel_set(self._handle, int(number)), f"op_select_kernel_set({name})")
-        self.__dict__["_f8_active"] = None
+        self._f8_active = None
 
     def _repin_calibrated(self, chosen: str) -> None:
         """Pin the calibrated set again after a detour through another one (the audits run the reference set in between):
@@ -382,7 +355,7 @@ class HipEncoder:
             code = self.lib.op_calibrate(self._handle, ctypes.c_float(float(tolerance)), *args, ctypes.byref(report))
         _lib.check(self.lib, self._handle, code, "op_calibrate")
         names = _lib.KERNEL_SET_NAMES
-        self.__dict__["_f8_active"] = None
+        self._f8_active = None
         self.calibration = {
             "tolerance": float(report.tolerance),
             "reference_set": names.get(int(report.reference_set), str(report.reference_set)),
@@ -400,11 +373,11 @@ class HipEncoder:
             mask = int(report.mlp_layers)
             self.calibration["mlp_correction_layers"] = [li for li in range(self.dims.num_layers) if (mask >> li) & 1]
             self.calibration["mlp_correction_err"] = float(report.mlp_layers_err)
-        # a set chosen on SYNTHETIC token ids is audited on the first real batch (_audit_first_batch); the caller's own rows
+        # a set chosen on SYNTHETIC token ids is audited on the first real batch (audit.first_batch_audit); the caller's own rows
         # are real inputs already.  audit="off" / OPEN_PROVENCE_AUDIT=0 switches the audit off; audit="running" keeps auditing.
-        mode = getattr(self, "audit_mode", None) or resolve_audit_mode(None)
+        mode = self.audit_mode
         cheaper = self.calibration["chosen_set"] != self.calibration["default_set"]
-        self.__dict__["_audit_pending"] = rows is None and cheaper and mode != "off"
+        self.audit_state.pending = rows is None and cheaper and mode != "off"
         self._reset_coverage(running=(mode == "running" and cheaper and self.calibration["reference_set"] in _lib.KERNEL_SET_IDS
                                       and self.calibration["reference_set"] != self.calibration["chosen_set"]
                                       and hasattr(self.lib, "op_coverage_scan")))
@@ -438,10 +411,9 @@ class HipEncoder:
         """True while the forward runs on kernel sets 3 / 4 (fp16 hi + e4m3 lo operands): their fp16 plane has fp16's
         range, and an MLP activation beyond it comes out as NaN by design (never clamped)."""
 
-        cached = self.__dict__.get("_f8_active")
-        if cached is None:
-            cached = self.__dict__["_f8_active"] = self.effective_policy()["kernel_set"] in _lib.FP16_PLANE_SETS
-        return cached
+        if self._f8_active is None:
+            self._f8_active = self.effective_policy()["kernel_set"] in _lib.FP16_PLANE_SETS
+        return self._f8_active
 
     def fall_back_from_f8(self, reason: str = "") -> bool:
         """Switch this model to the (hi, lo) bf16 kernel sets for good (``op_set_compact_operands``: both weight packs are resident,
@@ -454,18 +426,14 @@ class HipEncoder:
         changed = ctypes.c_int(0)
         code = self.lib.op_set_compact_operands(self._handle, 0, ctypes.byref(changed))
         _lib.check(self.lib, self._handle, code, "op_set_compact_operands")
-        self.__dict__["_f8_active"] = None
+        self._f8_active = None
         if changed.value:
-            import warnings
-
             if self.calibration is not None:  # the report names what RUNS, not what was chosen before the fallback
                 self.calibration["chosen_set"] = self.effective_policy()["kernel_set"]
                 self.calibration["fallback"] = "fp16 range guard"
-            self.__dict__["_audit_pending"] = False
+            self.audit_state.pending = False
             self._reset_coverage(running=False)
-
-            self.fallbacks = int(getattr(self, "fallbacks", 0)) + 1  # reported by process() (timing / performance_trace)
-
+            self.fallbacks += 1
             warnings.warn(
                 "open_provence_amd: a forward on the fp16 + e4m3 kernel set returned non-finite values"
                 + (f" ({reason})" if reason else "")
@@ -543,34 +511,66 @@ class HipEncoder:
         (packed ``[n_sel, T, H]`` or padded ``[n_sel, B, pad_width, H]``, zeros at padding); the logits are bit-identical
         to those of the same forward without the request.  ``ids_host`` (optional): the host copy of ``ids`` the caller
         already holds (what it handed to :meth:`check_ids`); the running audit decides coverage on it without touching the
-        device (:meth:`_maybe_audit`).
+        device (``audit.maybe_audit``).
 
         Asynchronous on the current torch stream of ``self.device`` (a forward that is audited synchronises it once)."""
 
-        total, n_seqs = self._check_packed_inputs(ids, cu_seqlens, keep_prob)
-        cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
-        if cu_host.shape[0] != n_seqs + 1:
-            raise ValueError("cu_seqlens_host length mismatch")
-        req = self._hidden_request(hidden, n_seqs, total, int(max_seqlen)) if hidden is not None else None
-        prune = torch.empty((total, 2), dtype=torch.float32, device=self.device)
-        rank = torch.empty((n_seqs, self.dims.num_labels), dtype=torch.float32, device=self.device)
-        if n_seqs == 0:
-            return (prune, rank) if req is None else (prune, rank, req[0])
-        ws = self._ensure_workspace(n_seqs, total, int(max_seqlen))
-        if self._capture is not None:
+        if self._capture is not None and ids.numel():
             self._capture = torch.zeros(
-                (self.dims.num_layers + 1, total, self.dims.hidden_size), dtype=torch.float32, device=self.device
+                (self.dims.num_layers + 1, int(ids.numel()), self.dims.hidden_size), dtype=torch.float32, device=self.device
             )
             capture_ptr = ctypes.c_void_p(self._capture.data_ptr())
             _lib.check(self.lib, self._handle, self.lib.op_debug_capture_hidden(self._handle, capture_ptr), "capture")
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, int(max_seqlen),
-                                 prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None,
-                                 ws, stream, req[1] if req is not None else None)
-            self._maybe_audit(ids, cu_seqlens, cu_host, n_seqs, total, int(max_seqlen), prune, rank, keep_prob, ws, stream,
-                              req[1] if req is not None else None, ids_host=ids_host, running=True)
-        return (prune, rank) if req is None else (prune, rank, req[0])
+        call, states = self._forward(None, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host)
+        return (call.prune, call.rank) if states is None else (call.prune, call.rank, states)
+
+    def _forward(self, part: "int | None", ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None, ids_host=None,
+                 running: "bool | None" = True) -> "tuple[PackedCall, torch.Tensor | None]":
+        """The one body of :meth:`forward_packed` (``part`` None: the current stream, the encoder's workspace) and
+        :meth:`forward_packed_on` (pipeline ``part``: its stream and workspace): checks, outputs, workspace, the launch and the
+        audits (``running``: whether the running audit may look at this forward; None: no audit at all) -> (the call with its
+        outputs, the hidden states of a ``hidden`` request)."""
+
+        if ids.dtype != torch.int32 or cu_seqlens.dtype != torch.int32:
+            raise TypeError("ids and cu_seqlens must be int32")
+        if ids.device != self.device or cu_seqlens.device != self.device:
+            raise ValueError(f"ids/cu_seqlens must live on {self.device}")
+        total, n_seqs, max_seqlen = int(ids.numel()), int(cu_seqlens.numel()) - 1, int(max_seqlen)
+        if keep_prob is not None and (
+            keep_prob.dtype != torch.float32 or keep_prob.device != self.device or keep_prob.numel() != total
+            or not keep_prob.is_contiguous()
+        ):
+            raise ValueError("keep_prob must be a contiguous fp32 tensor of total_tokens elements on the encoder's device")
+        cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
+        if cu_host.shape[0] != n_seqs + 1:
+            raise ValueError("cu_seqlens_host length mismatch")
+        states, req = self._hidden_request(hidden, n_seqs, total, max_seqlen) if hidden is not None else (None, None)
+        slots = self._split_streams() if part is not None else None
+        # The outputs of a pipeline come from the SIDE stream's pool of the caching allocator (allocated under that stream): a
+        # block of that pool is only ever recycled in side-stream order, so the kernels that write them can never land on memory
+        # a still-queued reader of the caller's stream owns (allocated from the caller's pool, a block freed there and
+        # whose last reader is still queued could be handed out here and overwritten early: nothing orders the side
+        # stream behind the caller's).  Consumers wait on pipeline_stream(part) before reading; a consumer that reads
+        # them on ANOTHER stream and drops them right away should record_stream() them there, as with any tensor that
+        # crosses streams.
+        with torch.cuda.device(self.device), (torch.cuda.stream(slots["streams"][part]) if slots else nullcontext()):
+            prune = torch.empty((total, 2), dtype=torch.float32, device=self.device)
+            rank = torch.empty((n_seqs, self.dims.num_labels), dtype=torch.float32, device=self.device)
+            if n_seqs == 0:
+                ws = None
+            elif slots is None:
+                ws = self._ensure_workspace(n_seqs, total, max_seqlen)
+            else:
+                ws = slots["ws"][part] = self._grown_workspace(slots["ws"][part], n_seqs, total, max_seqlen)
+            call = PackedCall(ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws,
+                              torch.cuda.current_stream(self.device).cuda_stream, req, ids_host)
+            if n_seqs:
+                self._forward_native(call)
+                # (an audit synchronises the call's stream once; on a pipeline, the other one must not be mid-forward on another
+                # host thread while it runs -- the pipelines of one encoder are driven from ONE thread everywhere in this package)
+                if running is not None:
+                    maybe_audit(self, call, running)
+        return call, states
 
     def _hidden_request(self, hidden: "HiddenRequest", n_seqs: int, total: int, max_seqlen: int):
         """-> (output tensor, ``_lib.OpHiddenRequest``) of one forward; the struct keeps its select array alive."""
@@ -603,12 +603,12 @@ class HipEncoder:
         req._flags = flags  # (keeps the array alive as long as the struct)
         return out, req
 
-    # -- the audit under a process group: ONE verdict for all ranks (sharding.collective_audit) -----------------------
+    # -- the audits of a calibrated kernel set: the device steps of audit.py ------------------------------------------------
     @property
     def audit_pending(self) -> bool:
         """True while a kernel set chosen on the library's synthetic batch has not seen real rows yet."""
 
-        return bool(self.__dict__.get("_audit_pending"))
+        return self.audit_state.pending
 
     def audit_rows(self, rows: "Sequence[Sequence[int]]") -> "bool | None":
         """The first-real-batch audit as an explicit call that only MEASURES: ``rows`` through the calibrated set and through the
@@ -619,100 +619,58 @@ class HipEncoder:
         if not self.audit_pending:
             return None
         ids_np, cu_np, max_len = pack_rows(rows)
-        total, n_seqs = int(cu_np[-1]), len(cu_np) - 1
-        if total < MIN_AUDIT_TOKENS:
+        if int(cu_np[-1]) < MIN_AUDIT_TOKENS:
             return None
         self.check_ids(ids_np)
         ids = torch.from_numpy(ids_np).to(self.device)
         cu = torch.from_numpy(cu_np).to(self.device)
-        cal = self.calibration or {}
-        chosen, reference = cal.get("chosen_set"), cal.get("reference_set")
-        self.__dict__["_audit_pending"] = False
-        if not chosen or chosen == cal.get("default_set") or reference not in _lib.KERNEL_SET_IDS:
-            return None
-        outs = {}
-        outs[chosen] = self.forward_packed(ids, cu, cu_np, max_len)  # (what is pinned now: the calibrated set, its layer mask included)
-        with self._reference_detour(chosen, reference):
-            outs[reference] = self.forward_packed(ids, cu, cu_np, max_len)
-        err = float(torch.maximum((outs[chosen][0] - outs[reference][0]).abs().max(), (outs[chosen][1] - outs[reference][1]).abs().max()).item())
-        bound = float(cal.get("tolerance", DEFAULT_CALIBRATION_TOLERANCE)) * float(getattr(self, "audit_factor", 3.0))
-        passed = err == err and err <= bound
-        cal["audit"] = {"tokens": total, "rows": n_seqs, "max_abs_err": err, "bound": bound, "passed": bool(passed), "collective": True}
-        return bool(passed)
+        call, _ = self._forward(None, ids, cu, cu_np, max_len, running=None)  # (what is pinned now: the calibrated set, its layer mask included)
+        return first_batch_audit(self, call, collective=True)
 
-    def revert_to_default(self, reason: str) -> str:
-        """Back to the default selection of ``op_weights_ready`` for good (what a failed audit does), with a warning."""
-
-        import warnings
+    def revert_to_default(self, reason: str, *, warning: "str | None" = None, stacklevel: int = 3,
+                          recompute: "PackedCall | None" = None) -> str:
+        """Back to the default selection of ``op_weights_ready`` for good (what a failed audit does), with a warning, and
+        ``recompute`` -- the forward whose audit failed -- run again there, into the caller's outputs.  ``warning`` (the
+        first-batch audit's own sentence, ``{after!r}`` = the set that runs from now on) replaces the standard one and keeps
+        ``reason`` out of the report."""
 
         before = self.effective_policy()["kernel_set"]
         self.select_kernel_set("auto")
         after = self.effective_policy()["kernel_set"]
         if self.calibration is not None:
             self.calibration["chosen_set"] = after
-            self.calibration["reverted"] = reason
-        if after != before:
+            if warning is None:
+                self.calibration["reverted"] = reason
+        if warning is not None:
+            warnings.warn(warning.format(after=after), RuntimeWarning, stacklevel=stacklevel)
+        elif after != before:
             warnings.warn(f"open_provence_amd: kernel set {before!r} dropped ({reason}); this model runs on {after!r} from now on.",
-                          RuntimeWarning, stacklevel=3)
+                          RuntimeWarning, stacklevel=stacklevel)
+        if recompute is not None:
+            self._forward_native(recompute)
         return after
 
-    # -- the running audit's state: which ids audited rows have held, on the host and (op_coverage_*) on the device ---------
     def _reset_coverage(self, running: bool) -> None:
         """Forget what was audited, on the host and in the handle (a new arithmetic has seen nothing), and switch the running
         audit on or off."""
 
-        self.__dict__["_running_on"] = bool(running)
-        self.__dict__["_cov_mirror"] = None  # bool [vocab], allocated by the first audit
-        self.__dict__["_cov_max_len"] = 0
-        self.__dict__["_since_audit"] = 0
-        if hasattr(self.lib, "op_coverage_reset") and getattr(self, "_handle", None):
+        self.audit_state.reset(running)
+        if hasattr(self.lib, "op_coverage_reset") and self._handle:
             self.lib.op_coverage_reset(self._handle)
 
-    @contextmanager
-    def _reference_detour(self, chosen: str, reference: str) -> Iterator[None]:
-        """Run what is inside on the calibration's ``reference`` kernel set, then pin ``chosen`` again -- whatever happens in
-        between.  Per-kernel profiling is suspended (the audit's launches are not the caller's workload).  The running
-        audit's coverage stays as it is on both sides: the handle's belongs to the arithmetic it was collected under and is
-        looked at again only once ``chosen`` is back."""
+    def _audit_blocked(self) -> bool:
+        """No audit now: a debug hidden capture, a process group's collective audit, or a stream being captured into a hipGraph."""
 
-        profiling = bool(self.__dict__.get("_profiling"))
-        if profiling:
-            self.lib.op_profile_enable(self._handle, 0)
-        self._select_kernel_set(reference)
-        try:
-            yield
-        finally:
-            self._repin_calibrated(chosen)
-            if profiling:
-                self.lib.op_profile_enable(self._handle, 1)
+        return self._capture is not None or bool(self.audit_collective) or torch.cuda.is_current_stream_capturing()
 
-    def _commit_coverage(self, ids: torch.Tensor, cu: torch.Tensor, rows_dev: torch.Tensor, n_rows: int) -> None:
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        code = self.lib.op_coverage_commit(self._handle, ctypes.c_void_p(ids.data_ptr()), ctypes.c_void_p(cu.data_ptr()),
-                                           int(cu.numel()) - 1, int(ids.numel()), ctypes.c_void_p(rows_dev.data_ptr()), int(n_rows),
-                                           ctypes.c_void_p(stream))
+    def _commit_coverage(self, call: PackedCall) -> None:
+        """Every row of ``call`` into the handle's coverage bitmap (``op_coverage_commit`` on the current stream)."""
+
+        rows_dev = torch.arange(call.n_seqs, dtype=torch.int32, device=self.device)
+        vp = ctypes.c_void_p
+        code = self.lib.op_coverage_commit(self._handle, vp(call.ids.data_ptr()), vp(call.cu_seqlens.data_ptr()), call.n_seqs, call.total,
+                                           vp(rows_dev.data_ptr()), call.n_seqs, vp(call.stream))
         _lib.check(self.lib, self._handle, code, "op_coverage_commit")
-
-    def _commit_audited(self, sub_ids_host: np.ndarray, sub_lengths: np.ndarray, sub_ids: torch.Tensor, sub_cu: torch.Tensor) -> None:
-        """An audit passed: its rows' ids join the coverage and the longest audited length rises, in the host mirror and in
-        the handle's bitmap, both from the sub-batch's ids."""
-
-        mirror = self.__dict__.get("_cov_mirror")
-        if mirror is None:
-            mirror = self.__dict__["_cov_mirror"] = np.zeros(self.dims.vocab_size, dtype=bool)
-        mirror[np.asarray(sub_ids_host, dtype=np.int64)] = True
-        if len(sub_lengths):
-            self.__dict__["_cov_max_len"] = max(int(self.__dict__.get("_cov_max_len") or 0), int(np.max(sub_lengths)))
-        n_rows = int(sub_cu.numel()) - 1
-        self._commit_coverage(sub_ids, sub_cu, torch.arange(n_rows, dtype=torch.int32, device=self.device), n_rows)
-
-    def _record_audit(self, trigger: str, rows: "Sequence[int]", tokens: int, err: float, bound: float, passed: bool) -> None:
-        audits = (self.calibration or {}).setdefault("audits", {"count": 0, "by_trigger": {}, "last": None})
-        audits["count"] += 1
-        audits["by_trigger"][trigger] = audits["by_trigger"].get(trigger, 0) + 1
-        audits["last"] = {"rows": [int(r) for r in rows], "tokens": int(tokens), "max_abs_err": float(err), "bound": float(bound),
-                          "passed": bool(passed), "trigger": trigger}
-        self.__dict__["_since_audit"] = 0
 
     def coverage_scan_device(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, n_seqs: int, total: int) -> "tuple[torch.Tensor, dict]":
         """``op_coverage_scan`` on the current stream (synchronised once): ``(row_novel[int32, n_seqs] on the device, {"novel",
@@ -730,200 +688,63 @@ class HipEncoder:
         return row_novel[:n_seqs], {"novel": int(report.novel_tokens), "longest": int(report.longest_row_tokens),
                                     "longest_row": int(report.longest_row), "max_audited": int(report.max_audited_tokens)}
 
-    def _maybe_audit(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req=None,
-                     ids_host=None, running=False) -> None:
-        """The audits of a calibrated kernel set, from EITHER forward entry point (``forward_packed`` / ``forward_packed_on``).
+    def _reference_call(self, call: PackedCall, rows: "Sequence[int] | None" = None) -> PackedCall:
+        """The forward an audit runs on the reference set: ``call``'s batch, or its ``rows`` gathered into a sub-batch on the
+        device (``op_gather_rows``), into outputs of its own, with no ``keep_prob`` and no hidden request."""
 
-        The first-real-batch audit of a synthetically calibrated set (modes ``"first"`` and ``"running"``) is skipped -- and left
-        pending -- for batches under 64 tokens, while hidden states are captured (the debug hook; a per-call request is
-        audited like any batch), and while the stream is being captured into a hipGraph (the audit synchronises and switches
-        the handle's kernel set in the middle of the forward).
-
-        The RUNNING audit (mode ``"running"``, a calibrated set that is not the default one) re-checks later forwards when a
-        trigger fires: ``audit_every`` forwards have passed since the last audit (0 = never), or the batch holds positions
-        whose token id was in no audited row so far, or a row longer than any audited row (``"coverage"``).  Coverage is
-        decided where the ids are: on ``ids_host`` in numpy against a host mirror of the handle's bitmap -- a forward that
-        does not audit then synchronises nothing -- or, without it, by ``op_coverage_scan`` (one small kernel and one
-        synchronisation per forward).  An audit re-runs up to ``audit_tokens`` tokens of the batch (:func:`select_audit_rows`)
-        on the reference set and compares on the device (:meth:`_running_audit`).  It is skipped -- the forward counts
-        towards ``audit_every`` all the same -- for batches under 64 tokens, under a debug hidden capture, on a capturing
-        stream, from ``forward_packed_on`` (the pipelined path), and on an encoder with ``audit_collective`` set: a process
-        group keeps its collective first-batch audit, and a collective running audit is future work."""
-
-        pending = bool(self.__dict__.get("_audit_pending"))
-        running = bool(running and self.__dict__.get("_running_on"))
-        if not pending and not running:
-            return
-        if running:
-            self.__dict__["_since_audit"] = int(self.__dict__.get("_since_audit") or 0) + 1
-        if total < MIN_AUDIT_TOKENS or self._capture is not None:
-            return
-        if getattr(self, "audit_collective", False):  # under a process group the ranks audit TOGETHER (sharding.collective_audit)
-            return
-        if torch.cuda.is_current_stream_capturing():
-            return
-        if pending:
-            verdict = self._audit_first_batch(ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream, hidden_req)
-            if running and verdict is not None:
-                # in running mode the first batch is the first running audit too: every row of it was just audited
-                first = (self.calibration or {}).get("audit", {})
-                self._record_audit("coverage", range(n_seqs), total, first.get("max_abs_err", float("nan")), first.get("bound", 0.0), verdict)
-                if verdict:
-                    self._commit_audited(ids_host if ids_host is not None else ids.cpu().numpy(), np.diff(cu_host), ids, cu_seqlens)
-            return
-        lengths = np.diff(cu_host)
-        longest = int(lengths.argmax())
-        if ids_host is not None:
-            mirror = self.__dict__.get("_cov_mirror")
-            if mirror is None:
-                mirror = self.__dict__["_cov_mirror"] = np.zeros(self.dims.vocab_size, dtype=bool)
-            too_long = int(lengths[longest]) > int(self.__dict__.get("_cov_max_len") or 0)
-            row_novel = None
-            if too_long or not mirror[ids_host].all():
-                row_novel = coverage_counts(ids_host, cu_host, mirror)
-        else:
-            novel_dev, report = self.coverage_scan_device(ids, cu_seqlens, n_seqs, total)
-            too_long = report["longest"] > report["max_audited"]
-            row_novel = novel_dev.cpu().numpy() if (too_long or report["novel"] > 0) else None
-        trigger = "coverage" if row_novel is not None else None
-        if trigger is None and self.audit_every > 0 and self.__dict__["_since_audit"] >= self.audit_every:
-            trigger, row_novel = "every_n", np.zeros(n_seqs, dtype=np.int32)
-        if trigger is None:
-            return
-        rows = select_audit_rows(row_novel, lengths, self.audit_tokens, longest=longest if too_long else None)
-        self._running_audit(trigger, rows, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream,
-                            hidden_req, ids_host)
-
-    def _running_audit(self, trigger, rows, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream,
-                       hidden_req, ids_host) -> None:
-        """One running audit: ``rows`` of the batch gathered into a sub-batch on the device (``op_gather_rows``), run on the
-        calibration's reference set, compared on the device with the logits the chosen set just wrote for those rows
-        (``op_audit_compare``; per-row outputs do not depend on the batch's composition, so the comparison is exact), one
-        float read back.  Within ``audit_factor`` x the calibration tolerance: the rows' ids join the coverage.  Beyond it,
-        or non-finite: what a failed first-batch audit does -- :meth:`revert_to_default`, one ``RuntimeWarning``, and THIS
-        batch recomputed there (with the caller's hidden-state request) before it is returned."""
-
-        cal = self.calibration or {}
-        chosen, reference = cal.get("chosen_set"), cal.get("reference_set")
-        lengths = np.diff(cu_host)
-        sub_lengths = lengths[rows].astype(np.int32)
+        if rows is None:
+            return call._replace(prune=torch.empty_like(call.prune), rank=torch.empty_like(call.rank), keep_prob=None, hidden_req=None)
+        sub_lengths = np.diff(call.cu_host)[list(rows)]
         sub_cu_host = np.concatenate(([0], np.cumsum(sub_lengths))).astype(np.int32)
+        sub_ids_host = None if call.ids_host is None else np.concatenate([call.ids_host[call.cu_host[r]: call.cu_host[r + 1]] for r in rows])
         n_sub, sub_total, sub_max = len(rows), int(sub_cu_host[-1]), int(sub_lengths.max())
         rows_dev = torch.tensor(rows, dtype=torch.int32, device=self.device)
         sub_ids = torch.empty(sub_total, dtype=torch.int32, device=self.device)
         sub_cu = torch.empty(n_sub + 1, dtype=torch.int32, device=self.device)
         vp = ctypes.c_void_p
-        code = self.lib.op_gather_rows(self._handle, vp(ids.data_ptr()), vp(cu_seqlens.data_ptr()), n_seqs, total, vp(rows_dev.data_ptr()),
-                                       n_sub, vp(sub_ids.data_ptr()), vp(sub_cu.data_ptr()), vp(stream))
+        code = self.lib.op_gather_rows(self._handle, vp(call.ids.data_ptr()), vp(call.cu_seqlens.data_ptr()), call.n_seqs, call.total,
+                                       vp(rows_dev.data_ptr()), n_sub, vp(sub_ids.data_ptr()), vp(sub_cu.data_ptr()), vp(call.stream))
         _lib.check(self.lib, self._handle, code, "op_gather_rows")
-        p_ref = torch.empty((sub_total, 2), dtype=torch.float32, device=self.device)
-        r_ref = torch.empty((n_sub, self.dims.num_labels), dtype=torch.float32, device=self.device)
-        if int(self.lib.op_workspace_bytes(self._handle, n_sub, sub_total, sub_max)) + 256 > ws.numel():
-            ws = torch.empty(int(self.lib.op_workspace_bytes(self._handle, n_sub, sub_total, sub_max)) + 256, dtype=torch.uint8, device=self.device)
+        return PackedCall(sub_ids, sub_cu, sub_cu_host, n_sub, sub_total, sub_max,
+                          torch.empty((sub_total, 2), dtype=torch.float32, device=self.device),
+                          torch.empty((n_sub, self.dims.num_labels), dtype=torch.float32, device=self.device), None,
+                          self._grown_workspace(call.ws, n_sub, sub_total, sub_max), call.stream, None, sub_ids_host, rows_dev)
+
+    def _logit_error(self, call: PackedCall, ref: PackedCall) -> float:
+        """max |logit difference| between ``call``'s outputs and those of ``ref`` (:meth:`_reference_call`); synchronises.  The
+        whole batch: in torch (a non-finite logit gives NaN).  A sub-batch: ``op_audit_compare`` against its rows (+inf)."""
+
+        if ref.rows is None:
+            return float(torch.maximum((call.prune - ref.prune).abs().max(), (call.rank - ref.rank).abs().max()).item())
         err_dev = torch.empty(1, dtype=torch.float32, device=self.device)
-        with self._reference_detour(chosen, reference):
-            self._forward_native(sub_ids.data_ptr(), sub_cu.data_ptr(), sub_cu_host, n_sub, sub_total, sub_max,
-                                 p_ref.data_ptr(), r_ref.data_ptr(), None, ws, stream)
-        code = self.lib.op_audit_compare(self._handle, vp(prune.data_ptr()), vp(rank.data_ptr()), vp(cu_seqlens.data_ptr()), n_seqs, total,
-                                         vp(rows_dev.data_ptr()), n_sub, vp(p_ref.data_ptr()), vp(r_ref.data_ptr()), vp(sub_cu.data_ptr()),
-                                         vp(err_dev.data_ptr()), vp(stream))
+        vp = ctypes.c_void_p
+        code = self.lib.op_audit_compare(self._handle, vp(call.prune.data_ptr()), vp(call.rank.data_ptr()), vp(call.cu_seqlens.data_ptr()),
+                                         call.n_seqs, call.total, vp(ref.rows.data_ptr()), ref.n_seqs, vp(ref.prune.data_ptr()),
+                                         vp(ref.rank.data_ptr()), vp(ref.cu_seqlens.data_ptr()), vp(err_dev.data_ptr()), vp(call.stream))
         _lib.check(self.lib, self._handle, code, "op_audit_compare")
-        err = float(err_dev.item())  # (synchronises: the one float an audit reads back)
-        bound = float(cal.get("tolerance", DEFAULT_CALIBRATION_TOLERANCE)) * float(getattr(self, "audit_factor", 3.0))
-        passed = err <= bound  # (+inf -- a non-finite logit on either side -- fails)
-        self._record_audit(trigger, rows, sub_total, err, bound, passed)
-        if passed:
-            if ids_host is not None:
-                sub_ids_host = np.concatenate([ids_host[cu_host[r]: cu_host[r + 1]] for r in rows])
-            else:
-                sub_ids_host = sub_ids.cpu().numpy()
-            self._commit_audited(sub_ids_host, sub_lengths, sub_ids, sub_cu)
-            return
-        self.revert_to_default(f"running audit ({trigger}): {err:.2e} from the {reference!r} kernels on rows {list(rows)[:8]} "
-                               f"of a batch, bound {bound:.1e}")
-        self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, max_seqlen,
-                             prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None, ws, stream,
-                             hidden_req)
+        return float(err_dev.item())
 
-    def _audit_first_batch(self, ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws, stream,
-                           hidden_req=None) -> "bool | None":
-        """The calibration ran on synthetic token ids; the FIRST real batch a calibrated model sees is its audit: the same
-        batch once more through the reference kernel set of the calibration, max |logit difference| against what the chosen
-        set just returned.  Within ``audit_factor`` (3) x the calibration tolerance -- 3e-4, still 3 x inside the path's bar;
-        the forward fuzz puts the worst row of other inputs at <= 2.7 x a calibration batch's maximum -- the choice stands
-        (one synchronisation, two extra forwards, once per load).  Beyond it, or non-finite: the model goes back to the
-        default selection of ``op_weights_ready`` for good, warns, and THIS batch is recomputed there before it is returned
-        (with the caller's hidden-state request, ``hidden_req``: the reference forward of the audit itself writes none).
-        Returns the verdict (None: there was nothing to audit)."""
+    def _grown_workspace(self, ws: "torch.Tensor | None", n_seqs: int, total: int, max_seqlen: int) -> torch.Tensor:
+        """``ws`` if it holds a forward of this geometry (``op_workspace_bytes`` + 256 for alignment), else a new one that does."""
 
-        self.__dict__["_audit_pending"] = False
-        cal = self.calibration or {}
-        chosen, reference = cal.get("chosen_set"), cal.get("reference_set")
-        if not chosen or chosen == cal.get("default_set") or reference not in _lib.KERNEL_SET_IDS:
-            return None
-        p_ref, r_ref = torch.empty_like(prune), torch.empty_like(rank)
-        with self._reference_detour(chosen, reference):
-            self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, max_seqlen,
-                                 p_ref.data_ptr(), r_ref.data_ptr(), None, ws, stream)
-        err = float(torch.maximum((prune - p_ref).abs().max(), (rank - r_ref).abs().max()).item())  # (synchronises)
-        bound = float(cal.get("tolerance", DEFAULT_CALIBRATION_TOLERANCE)) * float(getattr(self, "audit_factor", 3.0))
-        passed = err == err and err <= bound  # (NaN fails)
-        cal["audit"] = {"tokens": int(total), "rows": int(n_seqs), "max_abs_err": err, "bound": bound, "passed": bool(passed)}
-        if passed:
-            return True
-        import warnings
+        need = int(self.lib.op_workspace_bytes(self._handle, n_seqs, total, max_seqlen)) + 256
+        return ws if ws is not None and ws.numel() >= need else torch.empty(need, dtype=torch.uint8, device=self.device)
 
-        self.select_kernel_set("auto")
-        cal["chosen_set"] = self.effective_policy()["kernel_set"]
-        warnings.warn(
-            f"open_provence_amd: the first real batch disagrees with the load-time calibration: kernel set {chosen!r} is {err:.2e} from "
-            f"the {reference!r} kernels on it (bound {bound:.1e}); this model runs on {cal['chosen_set']!r} from now on.  "
-            "Pass calibration_rows= (a sample of real token ids) to calibrate on representative inputs.",
-            RuntimeWarning, stacklevel=4,
-        )
-        self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, max_seqlen,
-                             prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None, ws, stream,
-                             hidden_req)
-        return False
+    def _forward_native(self, call: PackedCall) -> None:
+        """``op_forward_packed[_hidden]``: the only place a :class:`PackedCall` becomes C arguments."""
 
-    def _check_packed_inputs(self, ids: torch.Tensor, cu_seqlens: torch.Tensor, keep_prob: torch.Tensor | None) -> tuple[int, int]:
-        """Shared argument checks of forward_packed / forward_packed_on -> (total_tokens, n_seqs)."""
-
-        if ids.dtype != torch.int32 or cu_seqlens.dtype != torch.int32:
-            raise TypeError("ids and cu_seqlens must be int32")
-        if ids.device != self.device or cu_seqlens.device != self.device:
-            raise ValueError(f"ids/cu_seqlens must live on {self.device}")
-        total = int(ids.numel())
-        if keep_prob is not None and (
-            keep_prob.dtype != torch.float32 or keep_prob.device != self.device or keep_prob.numel() != total
-            or not keep_prob.is_contiguous()
-        ):
-            raise ValueError("keep_prob must be a contiguous fp32 tensor of total_tokens elements on the encoder's device")
-        return total, int(cu_seqlens.numel()) - 1
-
-    def _forward_native(self, ids_ptr, cu_ptr, cu_host: np.ndarray, n_seqs: int, total: int, max_seqlen: int,
-                        prune_ptr, rank_ptr, keep_ptr, ws: torch.Tensor, stream: int, hidden_req=None) -> None:
-        base = ws.data_ptr()
+        vp = ctypes.c_void_p
+        base = call.ws.data_ptr()
         aligned = (base + 255) // 256 * 256
-        extra = () if hidden_req is None else (ctypes.byref(hidden_req),)
-        entry = self.lib.op_forward_packed if hidden_req is None else self.lib.op_forward_packed_hidden
+        extra = () if call.hidden_req is None else (ctypes.byref(call.hidden_req),)
+        entry = self.lib.op_forward_packed if call.hidden_req is None else self.lib.op_forward_packed_hidden
         code = entry(
-            self._handle,
-            ctypes.c_void_p(ids_ptr),
-            ctypes.c_void_p(cu_ptr),
-            cu_host.ctypes.data_as(ctypes.c_void_p),
-            n_seqs,
-            total,
-            max_seqlen,
-            ctypes.c_void_p(prune_ptr),
-            ctypes.c_void_p(rank_ptr),
-            ctypes.c_void_p(keep_ptr) if keep_ptr is not None else None,
-            ctypes.c_void_p(aligned),
-            ctypes.c_size_t(ws.numel() - (aligned - base)),
-            ctypes.c_void_p(stream),
-            *extra,
+            self._handle, vp(call.ids.data_ptr()), vp(call.cu_seqlens.data_ptr()), call.cu_host.ctypes.data_as(vp),
+            call.n_seqs, call.total, call.max_seqlen, vp(call.prune.data_ptr()), vp(call.rank.data_ptr()),
+            vp(call.keep_prob.data_ptr()) if call.keep_prob is not None else None,
+            vp(aligned), ctypes.c_size_t(call.ws.numel() - (aligned - base)), vp(call.stream), *extra,
         )
-        _lib.check(self.lib, self._handle, code, "op_forward_packed" if hidden_req is None else "op_forward_packed_hidden")
+        _lib.check(self.lib, self._handle, code, "op_forward_packed" if call.hidden_req is None else "op_forward_packed_hidden")
 
     def _split_streams(self) -> dict:
         """Two HIP streams of their own (hipExtStreamCreateWithCUMask with the full mask: own hardware queues, no CU partition since
@@ -989,35 +810,8 @@ class HipEncoder:
             raise RuntimeError("hidden-state capture is not available on the pipelined path (use forward_packed)")
         if hidden is not None:
             raise NotImplementedError("hidden-state requests are not available on the pipelined path (use forward_packed(hidden=...))")
-        total, n_seqs = self._check_packed_inputs(ids, cu_seqlens, keep_prob)
-        cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
-        if cu_host.shape[0] != n_seqs + 1:
-            raise ValueError("cu_seqlens_host length mismatch")
-        st = self._split_streams()
-        side = st["streams"][part]
-        # The outputs come from the SIDE stream's pool of the caching allocator (allocated under that stream): a block of
-        # that pool is only ever recycled in side-stream order, so the kernels that write them can never land on memory a
-        # still-queued reader of the caller's stream owns (allocated from the caller's pool, a block freed there and
-        # whose last reader is still queued could be handed out here and overwritten early: nothing orders the side
-        # stream behind the caller's).  Consumers wait on pipeline_stream(part) before reading; a consumer that reads
-        # them on ANOTHER stream and drops them right away should record_stream() them there, as with any tensor that
-        # crosses streams.
-        with torch.cuda.device(self.device), torch.cuda.stream(side):
-            prune = torch.empty((total, 2), dtype=torch.float32, device=self.device)
-            rank = torch.empty((n_seqs, self.dims.num_labels), dtype=torch.float32, device=self.device)
-            if n_seqs == 0:
-                return prune, rank
-            need = int(self.lib.op_workspace_bytes(self._handle, n_seqs, total, int(max_seqlen)))
-            ws = st["ws"][part]
-            if ws is None or ws.numel() < need + 256:
-                ws = st["ws"][part] = torch.empty(need + 256, dtype=torch.uint8, device=self.device)
-            self._forward_native(ids.data_ptr(), cu_seqlens.data_ptr(), cu_host, n_seqs, total, int(max_seqlen),
-                                 prune.data_ptr(), rank.data_ptr(), keep_prob.data_ptr() if keep_prob is not None else None,
-                                 ws, side.cuda_stream)
-            # (the audit synchronises this pipeline's stream once; the other pipeline must not be mid-forward on another
-            # host thread while it runs -- the pipelines of one encoder are driven from ONE thread everywhere in this package)
-            self._maybe_audit(ids, cu_seqlens, cu_host, n_seqs, total, int(max_seqlen), prune, rank, keep_prob, ws, side.cuda_stream)
-        return prune, rank
+        call, _ = self._forward(part, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, running=False)
+        return call.prune, call.rank
 
     def pipeline_stream(self, part: int) -> torch.cuda.Stream:
         return self._split_streams()["streams"][part]
@@ -1170,7 +964,7 @@ class HipEncoder:
 
     def profile_enable(self, enabled: bool) -> None:
         _lib.check(self.lib, self._handle, self.lib.op_profile_enable(self._handle, 1 if enabled else 0), "profile")
-        self.__dict__["_profiling"] = bool(enabled)
+        self._profiling = bool(enabled)
 
     def profile_reset(self) -> None:
         _lib.check(self.lib, self._handle, self.lib.op_profile_reset(self._handle), "profile_reset")

@@ -225,7 +225,7 @@ class OpenProvenceModel:
     ) -> None:
         # kernel_set / calibrate / calibration_rows: how the arithmetic is chosen from the loaded weights
         # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615);
-        # audit / audit_every / audit_tokens: how a calibrated choice is re-checked on real batches (HipEncoder._maybe_audit)
+        # audit / audit_every / audit_tokens: how a calibrated choice is re-checked on real batches (audit.maybe_audit)
         self._kernel_set_request = kernel_set
         self._calibrate_request = calibrate
         self._calibration_rows = calibration_rows

@@ -23,7 +23,7 @@ import torch
 ROOT = Path(__file__).resolve().parents[1]
 sys.path.insert(0, str(ROOT))
 
-from open_provence_amd.engine import HipEncoder  # noqa: E402
+from open_provence_amd.engine import HipEncoder, PackedCall  # noqa: E402
 from open_provence_amd.packing import pack_rows  # noqa: E402
 from open_provence_amd.synthetic import named_dims, refinit_state_dict, synth_pair_batch  # noqa: E402
 
@@ -92,7 +92,7 @@ def main() -> None:
 
         def step():
             for j, (ids, cu, cu_np, n, total, max_len, prune, rank, ws) in enumerate(work):
-                enc._forward_native(ids.data_ptr(), cu.data_ptr(), cu_np, n, total, max_len, prune.data_ptr(), rank.data_ptr(), None, ws, streams[j].cuda_stream)
+                enc._forward_native(PackedCall(ids, cu, cu_np, n, total, max_len, prune, rank, None, ws, streams[j].cuda_stream))
 
         for _ in range(6):
             step()
@@ -134,7 +134,7 @@ def main() -> None:
                     if offset_us > 0:
                         with torch.cuda.stream(streams[1]):
                             torch.cuda._sleep(int(offset_us * cyc_per_us))
-                enc._forward_native(ids.data_ptr(), cu.data_ptr(), cu_np, n, total, max_len, prune.data_ptr(), rank.data_ptr(), None, ws, streams[j].cuda_stream)
+                enc._forward_native(PackedCall(ids, cu, cu_np, n, total, max_len, prune, rank, None, ws, streams[j].cuda_stream))
 
         for i in range(6):
             step(i)

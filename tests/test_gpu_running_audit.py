@@ -301,14 +301,14 @@ def test_coverage_fires_on_new_ids_and_on_a_longer_row_only(fixture):
         _run(running, fixture["short"])
         _run(running, fixture["short"])
         assert _audits(running)["count"] == 1  # the second run holds nothing new
-        assert running.__dict__["_cov_max_len"] == 64
+        assert running.audit_state.cov_max_len == 64
         _run(running, fixture["with_long_row"])  # known ids, but a 130-token row after rows of at most 64
         audits = _audits(running)
         assert audits["count"] == 2 and audits["by_trigger"] == {"coverage": 2}
         last = audits["last"]
         # the longest row is always taken; the budget of 200 tokens then leaves room for the next 64-token row only
         assert last["passed"] and last["rows"][0] == 2 and last["tokens"] <= 200, last
-        assert running.__dict__["_cov_max_len"] == 130
+        assert running.audit_state.cov_max_len == 130
         _run(running, fixture["with_long_row"])
         assert _audits(running)["count"] == 2
     assert running.effective_policy()["kernel_set"] == "f16"
