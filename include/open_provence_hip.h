@@ -266,7 +266,9 @@ int op_set_compact_operands(op_handle* h, int enabled, int* changed);
  *   rank_logits_dev  [n_seqs, num_labels] fp32 (ranking_logits)
  *   keep_prob_dev    [total_tokens] fp32 or NULL: softmax(pruning_logits, -1)[:, 1] evaluated as
  *                    sigmoid(l1 - l0) in the same kernel (replaces standalone.py:2918-2924)
- * Work is enqueued on hip_stream (a hipStream_t, NULL = default stream). */
+ * Work is enqueued on hip_stream (a hipStream_t, NULL = default stream).
+ * The workspace may hold anything on entry: the outputs depend on ids, cu_seqlens and the weights only, and nothing outside
+ * [workspace_dev, workspace_dev + op_workspace_bytes) and the output buffers is written. */
 int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev,
                       const int32_t* cu_seqlens_host, int n_seqs, int total_tokens, int max_seqlen,
                       float* prune_logits_dev, float* rank_logits_dev, float* keep_prob_dev,
@@ -410,6 +412,27 @@ int op_segment_means(op_handle* h, const float* keep_prob_dev, int n_values, con
  * states, fp32 [num_layers+1, total_tokens, hidden]; entry num_layers is the post-final_norm
  * tensor, as in HF (transformers >= 5).  Pass NULL to switch capturing off. */
 int op_debug_capture_hidden(op_handle* h, float* hidden_dev);
+
+/* Test hook.  Replaces: nothing.  The regions op_forward_packed carves out of a workspace of this geometry, in order, as the
+ * carving code itself hands them out (a region added there appears here): entries[i] = {name of the region, offset from
+ * the 256-aligned workspace base, bytes used, kind}.  Every region starts on a 256-byte boundary; the last one, rounded up
+ * to 256, ends at op_workspace_bytes.  Returns the number of regions (at most max_entries are written; entries may be NULL
+ * with max_entries = 0 to ask for the count), OP_ERR_INVALID on a NULL handle or a negative size.  `name` points into the
+ * library.  Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).  For tests that fill a workspace
+ * with a pattern per kind: an index region must only ever be given in-range values. */
+enum op_workspace_kind {
+  OP_WS_FLOAT = 0, /* floating-point operands of a kernel (fp32, bf16 / fp16 planes, e4m3 pieces) */
+  OP_WS_INDEX = 1, /* int32 row maps and offsets: kernels address memory through them */
+  OP_WS_FLAG = 2   /* an int32 flag */
+};
+typedef struct op_workspace_region {
+  const char* name;
+  uint64_t offset;
+  uint64_t bytes;
+  int32_t kind; /* enum op_workspace_kind */
+} op_workspace_region;
+int op_debug_workspace_layout(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen, op_workspace_region* entries,
+                              int max_entries);
 
 /* Measurement hook: when enabled every kernel launch of the forward is bracketed by HIP events
  * on the launch stream; op_profile_read returns accumulated milliseconds and launch counts per

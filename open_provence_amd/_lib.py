@@ -68,6 +68,7 @@ EXPORTED_SYMBOLS = (
     "op_gather_rows",
     "op_audit_compare",
     "op_segment_means",
+    "op_debug_workspace_layout",
     "op_debug_capture_hidden",
     "op_profile_enable",
     "op_profile_read",
@@ -175,6 +176,20 @@ class OpCoverageReport(ctypes.Structure):
     ]
 
 
+class OpWorkspaceRegion(ctypes.Structure):
+    """``op_workspace_region``: one region of the forward's workspace (``op_debug_workspace_layout``)."""
+
+    _fields_ = [
+        ("name", ctypes.c_char_p),
+        ("offset", ctypes.c_uint64),
+        ("bytes", ctypes.c_uint64),
+        ("kind", ctypes.c_int32),
+    ]
+
+
+OP_WS_FLOAT, OP_WS_INDEX, OP_WS_FLAG = 0, 1, 2
+WORKSPACE_KINDS = {OP_WS_FLOAT: "float", OP_WS_INDEX: "index", OP_WS_FLAG: "flag"}
+
 OP_CAL_FULL_REPORT = 1
 OP_CAL_WHOLE_DEPTH = 2
 
@@ -257,6 +272,9 @@ def load_library() -> ctypes.CDLL:
         lib.op_gather_rows.argtypes = [vp, vp, vp, ci, ci, vp, ci, vp, vp, vp]
         lib.op_audit_compare.restype = ci
         lib.op_audit_compare.argtypes = [vp, vp, vp, vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]
+    if hasattr(lib, "op_debug_workspace_layout"):  # (test hook, additive to ABI 10)
+        lib.op_debug_workspace_layout.restype = ci
+        lib.op_debug_workspace_layout.argtypes = [vp, ci, ci, ci, ctypes.POINTER(OpWorkspaceRegion), ci]
     lib.op_segment_means.restype = ci
     lib.op_segment_means.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     lib.op_debug_capture_hidden.restype = ci

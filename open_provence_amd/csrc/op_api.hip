@@ -247,36 +247,42 @@ int chunk_row_capacity(const op_handle* h, int n_seqs, int total_tokens, int max
   return (int)std::min<long>(all_rows, cap);
 }
 
-void carve(const op_handle* h, char* base, int cap_rows_pad, int n_seqs, Workspace& ws) {
+// Every region is handed out through WS_TAKE: the member's own name and what it holds go to `layout` (op_debug_workspace_layout),
+// so a region added here is reported without a second list to keep in step.
+void carve(const op_handle* h, char* base, int cap_rows_pad, int n_seqs, Workspace& ws,
+           std::vector<op_workspace_region>* layout = nullptr) {
   size_t off = 0;
-  auto take = [&](size_t bytes) {
+  auto take = [&](const char* name, int kind, size_t bytes) {
     char* p = base ? base + off : nullptr;
+    if (layout) layout->push_back(op_workspace_region{name, (uint64_t)off, (uint64_t)bytes, (int32_t)kind});
     off += align_up_sz(bytes, 256);
     return p;
   };
+#define WS_TAKE(member, kind, bytes) ws.member = reinterpret_cast<decltype(ws.member)>(take(#member, kind, bytes))
   const size_t R = (size_t)cap_rows_pad;
   const size_t H = (size_t)h->H, I = (size_t)h->I;
-  ws.x = (float*)take(R * H * 4);
-  ws.ln_hi = (u16*)take(R * H * 2);
-  ws.ln_lo = (u16*)take(R * H * 2);
-  ws.q_hi = (u16*)take(R * H * 2);
-  ws.q_lo = (u16*)take(R * H * 2);
-  ws.k_hi = (u16*)take(R * H * 2);
-  ws.k_lo = (u16*)take(R * H * 2);
-  ws.vt_hi = (u16*)take(R * H * 2);
-  ws.vt_lo = (u16*)take(R * H * 2);
-  ws.o_hi = (u16*)take(R * H * 2);
-  ws.o_lo = (u16*)take(R * H * 2);
-  ws.h_hi = (u16*)take(R * I * 2);
-  ws.h_lo = (u16*)take(R * I * 2);
-  ws.row_seq = (int32_t*)take(R * 4);
-  ws.row_pos = (int32_t*)take(R * 4);
-  ws.row_tok = (int32_t*)take(R * 4);
-  ws.roff = (int32_t*)take(((size_t)n_seqs + 1) * 4);
-  ws.qboff = (int32_t*)take(((size_t)n_seqs + 1) * 4);
-  ws.qboff_l = (int32_t*)take(((size_t)n_seqs + 1) * 4);
-  ws.cls = (float*)take(std::max<size_t>((size_t)n_seqs, 1) * H * 4);
-  ws.range_flag = (int*)take(sizeof(int));
+  WS_TAKE(x, OP_WS_FLOAT, R * H * 4);
+  WS_TAKE(ln_hi, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(ln_lo, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(q_hi, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(q_lo, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(k_hi, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(k_lo, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(vt_hi, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(vt_lo, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(o_hi, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(o_lo, OP_WS_FLOAT, R * H * 2);
+  WS_TAKE(h_hi, OP_WS_FLOAT, R * I * 2);
+  WS_TAKE(h_lo, OP_WS_FLOAT, R * I * 2);
+  WS_TAKE(row_seq, OP_WS_INDEX, R * 4);
+  WS_TAKE(row_pos, OP_WS_INDEX, R * 4);
+  WS_TAKE(row_tok, OP_WS_INDEX, R * 4);
+  WS_TAKE(roff, OP_WS_INDEX, ((size_t)n_seqs + 1) * 4);
+  WS_TAKE(qboff, OP_WS_INDEX, ((size_t)n_seqs + 1) * 4);
+  WS_TAKE(qboff_l, OP_WS_INDEX, ((size_t)n_seqs + 1) * 4);
+  WS_TAKE(cls, OP_WS_FLOAT, std::max<size_t>((size_t)n_seqs, 1) * H * 4);
+  WS_TAKE(range_flag, OP_WS_FLAG, sizeof(int));
+#undef WS_TAKE
   ws.bytes = off;
 }
 
@@ -1788,6 +1794,17 @@ size_t op_workspace_bytes(const op_handle* h, int n_seqs, int total_tokens, int 
   Workspace ws;
   carve(h, nullptr, cap_pad, n_seqs, ws);
   return ws.bytes;
+}
+
+int op_debug_workspace_layout(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen, op_workspace_region* entries,
+                              int max_entries) {
+  if (!h || n_seqs < 0 || total_tokens < 0 || max_seqlen < 0 || max_entries < 0 || (!entries && max_entries > 0)) return OP_ERR_INVALID;
+  const int cap_pad = align_up(chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen) + 64, 256);  // (as op_workspace_bytes)
+  Workspace ws;
+  std::vector<op_workspace_region> layout;
+  carve(h, nullptr, cap_pad, n_seqs, ws, &layout);
+  for (size_t i = 0; i < layout.size() && i < (size_t)max_entries; ++i) entries[i] = layout[i];
+  return (int)layout.size();
 }
 
 int op_debug_capture_hidden(op_handle* h, float* hidden_dev) {

@@ -470,6 +470,19 @@ class HipEncoder:
             self._workspace = ws
         return ws
 
+    def workspace_layout(self, n_seqs: int, total_tokens: int, max_seqlen: int) -> "list[dict]":
+        """Test hook (``op_debug_workspace_layout``): the regions a forward of this geometry carves out of its workspace, in
+        order, ``[{"name", "offset", "bytes", "kind": "float" | "index" | "flag"}]``; offsets from the 256-aligned base."""
+
+        if not hasattr(self.lib, "op_debug_workspace_layout"):
+            raise _lib.HipLibraryError("this library has no op_debug_workspace_layout")
+        count = int(self.lib.op_debug_workspace_layout(self._handle, n_seqs, total_tokens, max_seqlen, None, 0))
+        _lib.check(self.lib, self._handle, min(count, 0), "op_debug_workspace_layout")
+        entries = (_lib.OpWorkspaceRegion * count)()
+        assert int(self.lib.op_debug_workspace_layout(self._handle, n_seqs, total_tokens, max_seqlen, entries, count)) == count
+        return [{"name": e.name.decode(), "offset": int(e.offset), "bytes": int(e.bytes), "kind": _lib.WORKSPACE_KINDS[int(e.kind)]}
+                for e in entries]
+
     def segment_means(self, values: torch.Tensor, segments: torch.Tensor) -> torch.Tensor:
         """``values[T]`` fp32 and ``segments[S, 2]`` int32 (token ranges ``[start, end)``) on this device ->
         ``[S]`` fp32: ``values[start:end].mean()`` in numpy's float32 pairwise order, bit for bit; 1.0 for an empty
