@@ -88,6 +88,7 @@ enum op_flags {
   OP_FLAG_PANEL_F8 = 2048,        /* hidden 512 / 768 (panel GEMMs): select the fp16 + e4m3 kernel sets there too.  OFF by default: through 19-25 layers their error against the fp32 reference reaches 0.45-1.0e-3 on logits (the (hi, lo) bf16 sets: 0.2-0.5e-3), too close to the 1e-3 bar of the path for +2.5 % (bf16 checkpoint) / +14 % (fp32) pairs/s.  On this opt-in path the MLP activation h is an fp16 operand converted with saturation: a value beyond 65504 is CLAMPED, not reported (the row path's sets turn it into NaN and fall back; the default panel sets keep h as (hi, lo) bf16 pairs with fp32's range) */
   OP_FLAG_PANEL_F8_WI = 4096,     /* hidden 512 / 768: the fp16 + e4m3 format in the Wi GEMM alone (52 % of the GEMM FLOPs; LayerNorm(mlp_norm) written in that format, h still as (hi, lo) bf16 pieces for the MLP output projection): the cheapest place for the format's error.  DEFAULT for fp32-valued weights (+5.6 % pairs/s on base, <= 5.4e-4 at 19-25 layers); this flag requests it for bf16-valued weights too (+0.7 %).  OP_FLAG_NO_F8 switches it off */
   OP_FLAG_NO_LAYER_PAIRS = 8192,  /* hidden = 256, single-pass kernel sets ("f16" / "bf16"): keep the 8 waves x 16 rows whole-layer kernel instead of the wave-pair kernel (opk_layer16p.hip.h) (A/B and test hook) */
+  OP_FLAG_F32_PACKS = 16384,      /* op_load_weight also keeps a row-major fp32 copy of the four GEMM weights of every layer (4 bytes per weight element more on the device): what kernel set 12 ("fp32", OP_KS_F32) runs on.  Without it no handle's device footprint or allocation order changes, and OP_KS_F32 is refused */
   OP_FLAG_NO_F8 = 512             /* never select kernel set 3 (fp16 hi + e4m3 lo operands in the whole-layer kernel): keep the (hi, lo) bf16 kernel sets (A/B and bit-identity test hook) */
 };
 
@@ -192,13 +193,20 @@ enum op_kernel_set {
    * (scripts/family_error_probe.py). */
   OP_KS_F16_F8_W_ATTN_F16 = 10,
   OP_KS_F16_F8_ATTN_F16 = 11,
-  OP_KS_COUNT = 12
+  /* "fp32": every contraction of a layer on the fp32-input MFMA (v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulate, a
+   * k-ordered fmaf chain; 1/16 of the 16-bit rate), fp32 activation planes, the checkpoint's fp32 weights as loaded, exact erff
+   * and expf -- the reference's fp32 arithmetic up to the order of its sums.  Any handle shape (row, panel or tiled) created
+   * with OP_FLAG_F32_PACKS.  Never a default and never cheaper than another set: pinned by op_select_kernel_set, or the
+   * reference / escalation target of op_calibrate under OP_CAL_REFERENCE_F32.  No fp16 plane: no range guard applies. */
+  OP_KS_F32 = 12,
+  OP_KS_COUNT = 13
 };
 
 /* Pin the kernel set the forward runs on (OP_KS_AUTO: un-pin).  A set with fewer product terms than the loaded
  * checkpoint carries (e.g. OP_KS_F16 on any checkpoint, OP_KS_F16_F8 on fp32-valued weights) is an APPROXIMATION of the
  * requested policy: op_calibrate is the call that measures it first.  OP_ERR_UNSUPPORTED when the handle cannot run the
- * set (shape without those kernels, packs not built because of OP_FLAG_NO_F8, a weight tensor below fp16's reach).
+ * set (shape without those kernels, packs not built because of OP_FLAG_NO_F8, a weight tensor below fp16's reach; OP_KS_F32
+ * on a handle created without OP_FLAG_F32_PACKS: the message names the flag).
  * Replaces: the reference choosing its arithmetic from the device and what loads (standalone.py:219-244, 1589-1615). */
 int op_select_kernel_set(op_handle* h, int kernel_set);
 
@@ -217,7 +225,7 @@ int op_select_kernel_set(op_handle* h, int kernel_set);
 typedef struct op_calibration {
   uint32_t struct_bytes; /* = sizeof(op_calibration), checked when a report is requested */
   float tolerance;
-  int32_t reference_set; /* the (hi, lo) bf16 kernel set the candidates were compared with */
+  int32_t reference_set; /* the (hi, lo) bf16 kernel set the candidates were compared with (OP_CAL_REFERENCE_F32: 12) */
   int32_t default_set;   /* what op_weights_ready selects for this checkpoint */
   int32_t chosen_set;    /* what the forward runs on from now on */
   int32_t n_candidates;
@@ -236,6 +244,11 @@ typedef struct op_calibration {
 } op_calibration;
 #define OP_CAL_FULL_REPORT 1u /* measure every candidate (the report lists them all); default: cheapest first, stop at the first that holds */
 #define OP_CAL_WHOLE_DEPTH 2u /* sets 8 / 9 for the whole depth or not at all (no per-layer search) */
+/* Opt-in, on a handle created with OP_FLAG_F32_PACKS (ignored without the packs): the candidates and the default set are
+ * compared with kernel set 12 ("fp32") instead of the (hi, lo) bf16 set -- reference_set = 12 --, the (hi, lo) bf16 set is
+ * a candidate like any other (where it is cheaper than the default), and a default beyond 10 x tolerance escalates to
+ * set 12.  Without the bit nothing about the call or its report changes. */
+#define OP_CAL_REFERENCE_F32 4u
 int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const int32_t* cu_seqlens_host, int n_seqs,
                  op_calibration* report);
 

@@ -31,12 +31,13 @@ OP_FLAG_ATTN_XCD_GROUP = 1024
 OP_FLAG_PANEL_F8 = 2048
 OP_FLAG_PANEL_F8_WI = 4096
 OP_FLAG_NO_LAYER_PAIRS = 8192
+OP_FLAG_F32_PACKS = 16384  # keep the fp32 GEMM weights on the device too: kernel set "fp32" (12) needs them
 OP_POOL_CLS, OP_POOL_MEAN = 0, 1
 # enum op_kernel_set (op_effective_policy / op_select_kernel_set / op_calibrate)
 OP_KS_AUTO = -1
 KERNEL_SET_NAMES = {0: "bf16x3", 1: "bf16-weights", 2: "bf16", 3: "f16-f8", 4: "f16-f8-w", 5: "bf16x3+wi-f16-f8-w",
                     6: "bf16-weights+wi-f16-f8", 7: "f16", 8: "f16+mlp-f16-f8-w", 9: "f16+mlp-f16-f8",
-                    10: "f16-f8-w+attn-f16", 11: "f16-f8+attn-f16",
+                    10: "f16-f8-w+attn-f16", 11: "f16-f8+attn-f16", 12: "fp32",
                     -1: "all-terms kernels, cleared lo operands"}
 KERNEL_SET_IDS = {name: number for number, name in KERNEL_SET_NAMES.items() if number >= 0}
 # kernel sets with an fp16 operand plane: an activation beyond fp16's range comes out as NaN (range guard in engine.py)
@@ -192,6 +193,7 @@ WORKSPACE_KINDS = {OP_WS_FLOAT: "float", OP_WS_INDEX: "index", OP_WS_FLAG: "flag
 
 OP_CAL_FULL_REPORT = 1
 OP_CAL_WHOLE_DEPTH = 2
+OP_CAL_REFERENCE_F32 = 4  # op_calibrate compares with kernel set "fp32" (a handle created with OP_FLAG_F32_PACKS)
 
 
 class OpProfileEntry(ctypes.Structure):

@@ -88,6 +88,7 @@ struct op_handle {
   bool f8_packs = false;           // the "f16 + fp8" weight packs exist (row path, hidden a multiple of 128)
   bool f8_off = false;             // op_set_compact_operands(h, 0): keep the (hi, lo) bf16 sets although the packs exist
   bool h16_packs = false;          // the fp16 single-plane weight packs of kernel set "f16" exist
+  bool f32_packs = false;          // OP_FLAG_F32_PACKS: the row-major fp32 weight packs of kernel set "fp32" exist
   int forced_set = -1;             // op_select_kernel_set / op_calibrate: run this kernel set (op_kernel_set numbering), -1 = the default selection
   bool f16_unfit = false;          // some weight TENSOR sits on fp16's subnormal grid: no kernel set with an fp16 weight plane
   uint64_t mlp_layers = ~0ull;     // sets 8 / 9: the layers whose MLP runs in that format (bit li); the others run the "f16" set's MLP
@@ -225,6 +226,11 @@ int drain_profile(op_handle* h) {
   return OP_OK;
 }
 
+// kernel set "fp32" only: its fp32 planes (carved behind the regions every set has; nullptr under every other set)
+struct WorkspaceF32 {
+  float *ln, *q, *k, *v, *o, *h;
+};
+
 struct Workspace {
   float* x;
   u16 *ln_hi, *ln_lo;
@@ -235,6 +241,7 @@ struct Workspace {
   int32_t *row_seq, *row_pos, *row_tok, *roff, *qboff, *qboff_l;
   float* cls;
   int* range_flag;  // panel path, fp16 + e4m3 format: "an fp16 operand was out of range" (PanelParams::range_flag)
+  WorkspaceF32 f;  // reported as regions ln_f .. h_f
   size_t bytes;
 };
 
@@ -249,7 +256,8 @@ int chunk_row_capacity(const op_handle* h, int n_seqs, int total_tokens, int max
 
 // Every region is handed out through WS_TAKE: the member's own name and what it holds go to `layout` (op_debug_workspace_layout),
 // so a region added here is reported without a second list to keep in step.
-void carve(const op_handle* h, char* base, int cap_rows_pad, int n_seqs, Workspace& ws,
+// f32: the planes of kernel set "fp32" follow the regions every set has (whose offsets therefore never move).
+void carve(const op_handle* h, char* base, int cap_rows_pad, int n_seqs, bool f32, Workspace& ws,
            std::vector<op_workspace_region>* layout = nullptr) {
   size_t off = 0;
   auto take = [&](const char* name, int kind, size_t bytes) {
@@ -283,6 +291,17 @@ void carve(const op_handle* h, char* base, int cap_rows_pad, int n_seqs, Workspa
   WS_TAKE(cls, OP_WS_FLOAT, std::max<size_t>((size_t)n_seqs, 1) * H * 4);
   WS_TAKE(range_flag, OP_WS_FLAG, sizeof(int));
 #undef WS_TAKE
+  ws.f = WorkspaceF32{};
+  if (f32) {
+#define WS_TAKE_F32(member, bytes) ws.f.member = reinterpret_cast<float*>(take(#member "_f", OP_WS_FLOAT, bytes))
+    WS_TAKE_F32(ln, R * H * 4);
+    WS_TAKE_F32(q, R * H * 4);
+    WS_TAKE_F32(k, R * H * 4);
+    WS_TAKE_F32(v, R * H * 4);
+    WS_TAKE_F32(o, R * H * 4);
+    WS_TAKE_F32(h, R * I * 4);
+#undef WS_TAKE_F32
+  }
   ws.bytes = off;
 }
 
@@ -342,7 +361,7 @@ struct ChunkPass {
   int pi;       // ... its opl::kPolicies index
   bool clr_q, clr_k, clr_v, clr_o, clr_h, clr_ln_attn, clr_ln_mlp, zero_p_lo, split;
   // the operand formats of the handle's kernel set (h->ks, op_sets.h), decided once here
-  bool o_f8, f16, attn16, wi8, wlo8, range_flagged, embed_in_qkv0;
+  bool o_f8, f16, f32, attn16, wi8, wlo8, range_flagged, embed_in_qkv0;
   bool mlp8[OP_MAX_LAYERS];  // sets 8 / 9, per layer: the MLP in the fp16 + e4m3 format
   PackFmt fmt_base, fmt_f8, fmt_side, fmt_wi;  // weight packs: layer-0 q / k / v, the fp16 + e4m3 GEMMs, attention side, Wi
   size_t plane_bytes;  // one row-major plane (tiled path)
@@ -378,6 +397,7 @@ struct ChunkPass {
     V = opl::kPolicies[pi];
     o_f8 = ks.side == FMT_F8;   // o = fp16 pieces (ws.o_hi) + e4m3 pieces (ws.o_lo); panel path: every GEMM in that format
     f16 = ks.side == FMT_F16;   // kernel set "f16": set 2's layouts, fp16 values, the fp16 weight packs
+    f32 = ks.side == FMT_F32;   // kernel set "fp32": fp32 planes and weights, its own layer (f32_layer) on every path
     // kernel sets 10 / 11 (panel path): q / k / v^T as single-plane fp16, attention on set 7's kernels with o in sets 3 / 4's
     // format; they neither write nor read a lo plane of q / k / v^T
     attn16 = o_f8 && ks.attn == FMT_F16;
@@ -410,7 +430,7 @@ struct ChunkPass {
     fmt_wi = (o_f8 || wi8) ? fmt_f8 : fmt_base;
     // Row path without hidden-state capture: the layer-0 q / k / v kernel gathers and normalises the embeddings itself
     // (RowGemmParams::emb_table) -- no embedding launch, the residual rows are written once and not read back.
-    embed_in_qkv0 = h->row_path && !h->capture && !(h->cfg.flags & OP_FLAG_NO_HEAD_FUSION);
+    embed_in_qkv0 = h->row_path && !f32 && !h->capture && !(h->cfg.flags & OP_FLAG_NO_HEAD_FUSION);
     plane_bytes = (size_t)r_pad * H * sizeof(u16);
     q_tiles = (max_len + ATT_BQ - 1) / ATT_BQ;
     // 4 waves x 32 rows = 128-row blocks, two per CU.  Small batches (at most one such block per CU) use 4 waves x
@@ -419,7 +439,7 @@ struct ChunkPass {
     row_grid = (unsigned)(r_pad / (small_blocks ? 64 : ROW_BM));
     // Kernel sets whose GEMM weights are single-plane run a whole layer (attention output projection, MLP, next q/k/v
     // projection) as ONE kernel with h kept on chip; the all-terms set keeps the two fused kernels per layer.
-    layer_fused = h->row_path && h->set >= 0 && opl::has_row_layer_fused(pi) && !(h->cfg.flags & OP_FLAG_NO_LAYER_FUSION);
+    layer_fused = h->row_path && !f32 && h->set >= 0 && opl::has_row_layer_fused(pi) && !(h->cfg.flags & OP_FLAG_NO_LAYER_FUSION);
     head_in_last_layer = layer_fused && h->cfg.pooling != OP_POOL_MEAN && !h->capture && !(h->cfg.flags & OP_FLAG_NO_HEAD_FUSION);
     // (!split: the single-pass sets "f16" / "bf16")
     pair_layers = layer_fused && H == 256 && I % 64 == 0 && !split && !h->capture &&
@@ -444,7 +464,10 @@ struct ChunkPass {
 
     // rows >= `rows` are never produced by the attention kernel: keep its output finite there
     if (range_flagged) OP_HIP(h, hipMemsetAsync(ws.range_flag, 0, sizeof(int), st));
-    if (fp_layout && o_f8) {
+    if (f32) {  // (the other sets' o planes are not read)
+      const size_t tail_bytes = (size_t)(r_pad - rows) * H * sizeof(float);
+      if (tail_bytes) OP_HIP(h, hipMemsetAsync(ws.f.o + (size_t)rows * H, 0, tail_bytes, st));
+    } else if (fp_layout && o_f8) {
       const size_t n16 = (size_t)((r_pad - rows) / 16);
       if (n16) OP_HIP(h, hipMemsetAsync(ws.o_hi + (size_t)(rows / 16) * (H / 32) * 512, 0, n16 * (H / 32) * 512 * sizeof(u16), st));
       if (n16) OP_HIP(h, hipMemsetAsync(ws.o_lo + (size_t)(rows / 16) * h->nh * 512, 0, n16 * h->nh * 512 * sizeof(u16), st));
@@ -955,6 +978,82 @@ struct ChunkPass {
     return OP_OK;
   }
 
+  // one layer of kernel set "fp32" (opk_f32.hip.h), on a handle of any path: LayerNorm, q / k / v projection, attention,
+  // attention output projection, LayerNorm, Wi + GeGLU, MLP output projection -- fp32 planes, the fp32 weights as loaded
+  int f32_layer(int li) {
+    const LayerWeights& lw = h->layers[li];
+    const bool is_global = h->cfg.layer_is_global[li] != 0;
+    auto f32_weight = [&](Weight w) { return reinterpret_cast<const float*>(weight(li, w, PF_F32)); };
+    // layer 0: attn_norm is the identity, the residual stream is the operand
+    auto layer_norm = [&](const float* w, const float*& plane) -> int {
+      plane = ws.x;
+      if (!w) return OP_OK;
+      OP_TRY(L.begin(PK_LN));
+      opl::launch_f32_ln(st, ws.x, w, h->cfg.norm_eps, H, r_pad, ws.f.ln);
+      plane = ws.f.ln;
+      return L.end();
+    };
+    auto gemm = [&](int kind, const F32GemmParams& p, int epi) -> int {
+      OP_TRY(L.begin(kind));
+      if (!opl::launch_f32_gemm(st, p, epi)) return fail(h, OP_ERR_UNSUPPORTED, "internal: no fp32 GEMM epilogue %d", epi);
+      return L.end();
+    };
+    F32GemmParams p;
+    memset(&p, 0, sizeof(p));
+    p.m_tiles = m_tiles;
+    p.hidden = H;
+    p.inter = I;
+    p.row_pos = ws.row_pos;
+    p.rope_cos = h->rope_cos[is_global ? 1 : 0];
+    p.rope_sin = h->rope_sin[is_global ? 1 : 0];
+    p.max_pos = h->max_pos;
+    // q, k = RoPE(LN(x) Wq^T), RoPE(LN(x) Wk^T); v = LN(x) Wv^T
+    OP_TRY(layer_norm(li != 0 ? lw.attn_norm : nullptr, p.a));
+    p.w = f32_weight(W_QKV);
+    p.K = H;
+    p.n_tiles = 3 * H / GEMM_BN;
+    p.o0 = ws.f.q;
+    p.o1 = ws.f.k;
+    p.o2 = ws.f.v;
+    p.ld_out = H;
+    OP_TRY(gemm(PK_GEMM_QKV_ROPE, p, F32_EPI_QKV));
+
+    OP_TRY(L.begin(is_global ? PK_ATTN_GLOBAL : PK_ATTN_LOCAL));
+    F32AttnParams ap;
+    ap.q = ws.f.q;
+    ap.k = ws.f.k;
+    ap.v = ws.f.v;
+    ap.o = ws.f.o;
+    ap.cu = cu_dev;
+    ap.s0 = s0;
+    ap.roff = ws.roff;
+    ap.H = H;
+    ap.window = is_global ? -1 : h->cfg.local_attention / 2;
+    opl::launch_f32_attn(st, ap, dim3((unsigned)q_tiles, (unsigned)h->nh, (unsigned)ns));
+    OP_TRY(L.end());
+
+    // x += o Wo^T
+    p.a = ws.f.o;
+    p.w = f32_weight(W_ATTN_OUT);
+    p.n_tiles = H / GEMM_BN;
+    p.x = ws.x;
+    OP_TRY(gemm(PK_GEMM_ATTN_OUT, p, F32_EPI_RESIDUAL));
+    // x += (gelu(a) * g) Wo^T,  (a, g) = LN(x) Wi^T
+    OP_TRY(layer_norm(lw.mlp_norm, p.a));
+    p.w = f32_weight(W_WI);
+    p.n_tiles = I / 64;
+    p.o0 = ws.f.h;
+    p.ld_out = I;
+    OP_TRY(gemm(PK_GEMM_WI_GEGLU, p, F32_EPI_GEGLU));
+    p.a = ws.f.h;
+    p.w = f32_weight(W_MLP_OUT);
+    p.K = I;
+    p.n_tiles = H / GEMM_BN;
+    p.ld_out = H;
+    OP_TRY(gemm(PK_GEMM_MLP_OUT, p, F32_EPI_RESIDUAL));
+    return OP_OK;
+  }
+
   // final_norm + pruning head (unless the last whole-layer launch did it), ranking head
   int heads() {
     const int mean_pool = h->cfg.pooling == OP_POOL_MEAN ? 1 : 0;
@@ -970,7 +1069,11 @@ struct ChunkPass {
       OP_TRY(L.end());
     }
     OP_TRY(L.begin(PK_RANK_HEAD));
-    hipLaunchKernelGGL(rank_head_kernel, dim3((unsigned)ns), dim3(256), 0, st, ws.cls, ws.x, cu_dev, s0, ws.roff, mean_pool,
+    if (f32)
+      opl::launch_f32_rank_head(st, ns, ws.cls, ws.x, cu_dev, s0, ws.roff, mean_pool, H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps,
+                                h->cls_w, h->cls_b, rank_out);
+    else
+      hipLaunchKernelGGL(rank_head_kernel, dim3((unsigned)ns), dim3(256), 0, st, ws.cls, ws.x, cu_dev, s0, ws.roff, mean_pool,
                        H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps, h->cls_w, h->cls_b, rank_out,
                        range_flagged ? ws.range_flag : nullptr);
     OP_TRY(L.end());
@@ -982,7 +1085,8 @@ struct ChunkPass {
     if (!embed_in_qkv0) OP_TRY(hidden(0));
     for (int li = 0; li < h->N; ++li) {
       OP_TRY(capture(li));
-      if (h->row_path) OP_TRY(row_layer(li));
+      if (f32) OP_TRY(f32_layer(li));
+      else if (h->row_path) OP_TRY(row_layer(li));
       else if (h->panel_path) OP_TRY(panel_layer(li));
       else OP_TRY(tiled_layer(li));
       // output of layer li = entry li + 1 (entry N is the head's input: heads() / the last whole-layer launch), unless the
@@ -1211,6 +1315,7 @@ int op_create(const op_config* cfg, op_handle** out) {
   // another layer structure
   h->h16_packs = ((h->row_path && (H == 128 || H == 256)) || h->panel_path) &&
                  !(cfg->flags & (OP_FLAG_NO_F8 | OP_FLAG_NO_LAYER_FUSION | OP_FLAG_NO_POLICY_KERNELS));
+  h->f32_packs = (cfg->flags & OP_FLAG_F32_PACKS) != 0;
   OP_CREATE_TRY(dev_alloc(h, &h->emb, (size_t)h->V * H));
   OP_CREATE_TRY(dev_alloc(h, &h->emb_norm, H));
   OP_CREATE_TRY(dev_alloc(h, &h->final_norm, H));
@@ -1236,7 +1341,7 @@ int op_create(const op_config* cfg, op_handle** out) {
       for (Weight w : step.order)
         for (int f = 0; f < step.n_fmt; ++f) {
           const PackFmt pf = step.fmt[f];
-          if (kPackElems[w][pf] && pack_exists(pf, h->row_path, h->panel_path, h->f8_packs, h->h16_packs, H))
+          if (kPackElems[w][pf] && pack_exists(pf, h->row_path, h->panel_path, h->f8_packs, h->h16_packs, h->f32_packs, H))
             OP_CREATE_TRY(dev_alloc(h, &lw.pack[w][pf], weight_elems(w, H, I) * kPackElems[w][pf]));
         }
     h->missing.push_back(pre + "mlp_norm.weight");
@@ -1357,6 +1462,8 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
     h->forced_mlp_layers = ~0ull;
     h->f8_off = false;
     WeightPacker{h, *wd, f32, (int)d0, (int)d1, (req_mask[wd->family] & OP_TERM_RIGHT_LO) ? 0 : 1, h->any_lo_dev + wd->family}.run(packs);
+    // kernel set "fp32": the tensor as it is
+    if (packs[PF_F32]) e = hipMemcpyAsync(packs[PF_F32], f32, count * sizeof(float), hipMemcpyDeviceToDevice, 0);
   } else if (transpose) {
     hipLaunchKernelGGL(transpose_f32_kernel, dim3(blocks), dim3(256), 0, 0, f32, (int)d0, (int)d1, dst_f32);
   } else {
@@ -1378,8 +1485,9 @@ namespace {
 // weight tensor below the reach of an fp16 plane for the sets that carry one: the set's `needs` (op_sets.h).
 bool set_available(const op_handle* h, int set) {
   if (set < 0 || set >= OP_KS_COUNT) return false;
-  if (h->cfg.flags & OP_FLAG_NO_POLICY_KERNELS) return set == OP_KS_BF16X3;
   const unsigned needs = kKernelSets[set].needs;
+  if ((needs & NEED_F32_PACKS) && !h->f32_packs) return false;
+  if (h->cfg.flags & OP_FLAG_NO_POLICY_KERNELS) return set == OP_KS_BF16X3 || set == OP_KS_F32;
   if ((needs & NEED_FAST) && !h->row_path && !h->panel_path) return false;
   if ((needs & NEED_PANEL) && !h->panel_path) return false;
   if ((needs & NEED_F8_PACKS) && !h->f8_packs) return false;
@@ -1513,6 +1621,9 @@ int op_select_kernel_set(op_handle* h, int kernel_set) {
   if (!h) return fail(nullptr, OP_ERR_INVALID, "op_select_kernel_set: NULL handle");
   int rc = op_weights_ready(h);
   if (rc != OP_OK) return rc;
+  if (kernel_set == OP_KS_F32 && !h->f32_packs)
+    return fail(h, OP_ERR_UNSUPPORTED, "op_select_kernel_set: kernel set %d (\"fp32\") needs the fp32 weight packs: create the handle with OP_FLAG_F32_PACKS",
+                kernel_set);
   if (kernel_set != OP_KS_AUTO && !set_available(h, kernel_set))
     return fail(h, OP_ERR_UNSUPPORTED, "op_select_kernel_set: kernel set %d cannot run on this handle (shape, flags or weights)", kernel_set);
   h->forced_set = kernel_set == OP_KS_AUTO ? -1 : kernel_set;
@@ -1585,7 +1696,10 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   h->f8_off = true;
   h->resolved = false;
   OP_TRY(resolve_policy(h));
-  const int reference_set = h->set;
+  // OP_CAL_REFERENCE_F32 on a handle with the fp32 packs: kernel set "fp32" is the reference, the (hi, lo) bf16 set a candidate
+  // like any other (where it is cheaper than the default)
+  const bool ref_f32 = report && (report->flags & OP_CAL_REFERENCE_F32) != 0 && h->set >= 0 && set_available(h, OP_KS_F32);
+  const int reference_set = ref_f32 ? (int)OP_KS_F32 : h->set;
   h->f8_off = f8_off_before;
   h->resolved = false;
   OP_TRY(resolve_policy(h));
@@ -1619,7 +1733,7 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
     if (set != default_set && set_available(h, set) && set_cost(h, set) < set_cost(h, default_set)) cand.push_back(set);
   std::sort(cand.begin(), cand.end(), [&](int a, int b) { return set_cost(h, a) < set_cost(h, b); });
   if (cand.size() > 16) cand.resize(16);
-  if (cand.empty()) return finish_unchanged();
+  if (cand.empty() && !ref_f32) return finish_unchanged();  // (fp32 reference: the default itself is still measured against it)
 
   std::vector<int32_t> ids, cu;
   if (ids_host) {
@@ -1635,7 +1749,12 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   rep.n_rows = n_seqs;
   rep.n_tokens = total;
 
-  const size_t ws_bytes = op_workspace_bytes(h, n_seqs, total, max_len);
+  size_t ws_bytes = op_workspace_bytes(h, n_seqs, total, max_len);
+  if (ref_f32) {  // the largest workspace of the sets that run: the fp32 set's (its planes follow everybody's regions)
+    Workspace sized;
+    carve(h, nullptr, align_up(chunk_row_capacity(h, n_seqs, total, max_len) + 64, 256), n_seqs, true, sized);
+    ws_bytes = std::max(ws_bytes, sized.bytes);
+  }
   const size_t n_prune = (size_t)total * 2, n_rank = (size_t)n_seqs * h->nl;
   int32_t *ids_dev = nullptr, *cu_dev = nullptr;
   float* out_dev = nullptr;
@@ -1792,7 +1911,7 @@ size_t op_workspace_bytes(const op_handle* h, int n_seqs, int total_tokens, int 
   const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
   const int cap_pad = align_up(cap + 64, 256);
   Workspace ws;
-  carve(h, nullptr, cap_pad, n_seqs, ws);
+  carve(h, nullptr, cap_pad, n_seqs, h->set == OP_KS_F32, ws);
   return ws.bytes;
 }
 
@@ -1802,7 +1921,7 @@ int op_debug_workspace_layout(const op_handle* h, int n_seqs, int total_tokens, 
   const int cap_pad = align_up(chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen) + 64, 256);  // (as op_workspace_bytes)
   Workspace ws;
   std::vector<op_workspace_region> layout;
-  carve(h, nullptr, cap_pad, n_seqs, ws, &layout);
+  carve(h, nullptr, cap_pad, n_seqs, h->set == OP_KS_F32, ws, &layout);
   for (size_t i = 0; i < layout.size() && i < (size_t)max_entries; ++i) entries[i] = layout[i];
   return (int)layout.size();
 }
@@ -1912,7 +2031,7 @@ static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32
   const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
   const int cap_pad = align_up(cap + 64, 256);
   Workspace ws;
-  carve(h, reinterpret_cast<char*>(workspace), cap_pad, n_seqs, ws);
+  carve(h, reinterpret_cast<char*>(workspace), cap_pad, n_seqs, h->set == OP_KS_F32, ws);
 
   Launcher L{h, stream};
   int s0 = 0;

@@ -8,6 +8,7 @@
 
 #include "opk_attn.hip.h"
 #include "opk_common.hip.h"
+#include "opk_f32.hip.h"
 #include "opk_layer32.hip.h"
 #include "opk_layer16p.hip.h"
 #include "opk_panel.hip.h"
@@ -93,6 +94,17 @@ bool launch_panel_qkv(hipStream_t st, const opk::PanelParams& p, int pi, dim3 gr
 bool launch_panel_f8(hipStream_t st, const opk::PanelParams& p, int epi, bool wlo, dim3 grid);
 // o16 (kernel sets 10 / 11): q, k, v^T as single-plane fp16 for launch_attn(.., f16_in_f8_out = true)
 bool launch_panel_f8_qkv(hipStream_t st, const opk::PanelParams& p, bool wlo, bool o16, dim3 grid);
+
+// Kernel set "fp32" (opk_f32.hip.h; op_launch_f32.hip): fp32 planes, fp32 weights as loaded, fp32-input MFMAs.
+// epi: opk::F32Epilogue; false when there is no such epilogue.
+void launch_f32_ln(hipStream_t st, const float* x, const float* w, float eps, int H, int r_pad, float* out);
+bool launch_f32_gemm(hipStream_t st, const opk::F32GemmParams& p, int epi);
+// grid: (64-query blocks of the longest sequence, heads, sequences)
+void launch_f32_attn(hipStream_t st, const opk::F32AttnParams& p, dim3 grid);
+// rank_head_kernel's arguments (one block per sequence), exact erff
+void launch_f32_rank_head(hipStream_t st, int n_seqs, const float* cls, const float* y, const int32_t* cu, int s0, const int32_t* roff,
+                          int mean_pool, int H, int nl, const float* dense_t, const float* head_norm, float eps, const float* cls_w,
+                          const float* cls_b, float* rank_out);
 
 // The padded [B, L] boundary (opk_padded.hip.h; op_pack_padded / op_unpack_padded).  Integer types as enum op_int_dtype.
 constexpr int PAD_INT_I32 = 0, PAD_INT_I64 = 1, PAD_INT_U8 = 2;

@@ -14,7 +14,8 @@ namespace ops {
 enum Fmt {
   FMT_BF16,  // (hi, lo) bf16 planes, the lo planes the policy's terms ask for
   FMT_F16,   // one fp16 plane
-  FMT_F8     // fp16 pieces + e4m3 pieces (x 2^12) of their lo part
+  FMT_F8,    // fp16 pieces + e4m3 pieces (x 2^12) of their lo part
+  FMT_F32    // fp32 planes on the fp32-input MFMA (kernel set "fp32": the whole layer, opk_f32.hip.h)
 };
 
 // what a set needs from the handle (set_available)
@@ -24,6 +25,7 @@ enum Need {
   NEED_F8_PACKS = 4,   // the fp16 + e4m3 weight packs
   NEED_H16_PACKS = 8,  // the fp16 single-plane weight packs
   NEED_F16_FIT = 16,   // no weight tensor on fp16's subnormal grid
+  NEED_F32_PACKS = 64, // the row-major fp32 weight packs (OP_FLAG_F32_PACKS)
   NEED_ROW_LAYER = 32  // on the row path: none of OP_FLAG_NO_LAYER_FUSION / LAYER_8X16 / LAYER_M32 (the set is a whole-layer kernel there)
 };
 
@@ -55,6 +57,8 @@ constexpr KernelSet kKernelSets[OP_KS_COUNT] = {
     {opl::PI_F16, FMT_F16, FMT_F16, FMT_F8, FMT_F8, false, {0, 0, 0, 0, 0, 0}, NEED_PANEL | NEED_H16_PACKS | NEED_F8_SET, 1.375f, 1.375f}, //  9 f16+mlp-f16-f8
     {opl::PI_F16_F8_W, FMT_F8, FMT_F16, FMT_F8, FMT_F8, true, {3, 0, 0, 3, 3, 3}, NEED_PANEL | NEED_F8_SET, 1.9f, 1.9f},                   // 10 f16-f8-w+attn-f16
     {opl::PI_F16_F8, FMT_F8, FMT_F16, FMT_F8, FMT_F8, false, {1, 0, 0, 1, 1, 1}, NEED_PANEL | NEED_F8_SET, 1.45f, 1.45f},                  // 11 f16-f8+attn-f16
+    // fp32 operands, 1/16 of the 16-bit MFMA rate: never cheaper than anything (op_calibrate: a reference, an escalation target)
+    {opl::PI_ALL_TERMS, FMT_F32, FMT_F32, FMT_F32, FMT_F32, false, {3, 3, 3, 3, 3, 3}, NEED_F32_PACKS, 16.0f, 16.0f},                      // 12 fp32
 };
 // set number -1: any other term policy, on the all-terms kernels with the lo operands it does not carry cleared
 constexpr KernelSet kClearedOperands = {opl::PI_ALL_TERMS, FMT_BF16, FMT_BF16, FMT_BF16, FMT_BF16, false, {3, 3, 3, 3, 3, 3}, 0, 3.0f, 3.0f};
@@ -77,6 +81,7 @@ enum PackFmt {
   PF_L32,       // hidden = 256: hi plane in the fragment order of the 32x32x16 whole-layer kernel (opk_layer32.hip.h)
   PF_PAIR,      // hidden = 256: one plane in the order of the wave-pair whole-layer kernel (opk_layer16p.hip.h), bf16 values
   PF_PAIR16,    // ... fp16 values
+  PF_F32,       // kernel set "fp32" (OP_FLAG_F32_PACKS): the tensor as loaded, row-major fp32 (two u16 per element)
   PF_COUNT
 };
 
@@ -110,15 +115,15 @@ constexpr size_t weight_elems(Weight w, int H, int I) { return weight_rows(w, H,
 
 // u16 elements allocated per weight element; 0: no such pack
 constexpr int kPackElems[W_COUNT][PF_COUNT] = {
-    // HI LO PK PK16 ROW_F8A ROW_F8B PANEL16 PANEL8 L32 PAIR PAIR16
-    {1, 1, 2, 2, 2, 0, 1, 1, 1, 1, 1},  // W_QKV       [fp16 | e4m3 + e4m3(lo)] chunks
-    {1, 1, 2, 2, 1, 1, 1, 1, 1, 1, 1},  // W_ATTN_OUT  fp16 slabs + e4m3 slabs
-    {1, 1, 2, 2, 2, 0, 1, 1, 1, 1, 1},  // W_WI
-    {1, 1, 2, 2, 2, 0, 1, 1, 1, 1, 1},  // W_MLP_OUT   fp16 slabs of w and of lo(w): no e4m3 plane
+    // HI LO PK PK16 ROW_F8A ROW_F8B PANEL16 PANEL8 L32 PAIR PAIR16 F32
+    {1, 1, 2, 2, 2, 0, 1, 1, 1, 1, 1, 2},  // W_QKV       [fp16 | e4m3 + e4m3(lo)] chunks
+    {1, 1, 2, 2, 1, 1, 1, 1, 1, 1, 1, 2},  // W_ATTN_OUT  fp16 slabs + e4m3 slabs
+    {1, 1, 2, 2, 2, 0, 1, 1, 1, 1, 1, 2},  // W_WI
+    {1, 1, 2, 2, 2, 0, 1, 1, 1, 1, 1, 2},  // W_MLP_OUT   fp16 slabs of w and of lo(w): no e4m3 plane
 };
 
-// does the handle build packs of this format? (tiled = neither fast path; f8 / h16: op_handle::f8_packs / h16_packs)
-constexpr bool pack_exists(PackFmt f, bool row, bool panel, bool f8, bool h16, int H) {
+// does the handle build packs of this format? (tiled = neither fast path; f8 / h16 / f32: op_handle::f8_packs / h16_packs / f32_packs)
+constexpr bool pack_exists(PackFmt f, bool row, bool panel, bool f8, bool h16, bool f32, int H) {
   switch (f) {
     case PF_HI:
     case PF_LO: return !row && !panel;
@@ -131,6 +136,7 @@ constexpr bool pack_exists(PackFmt f, bool row, bool panel, bool f8, bool h16, i
     case PF_L32:
     case PF_PAIR: return row && H == 256;
     case PF_PAIR16: return row && H == 256 && h16;
+    case PF_F32: return f32;
     default: return false;
   }
 }
@@ -151,6 +157,7 @@ constexpr AllocStep kAllocOrder[] = {
     {{PF_L32}, 1, {W_ATTN_OUT, W_WI, W_MLP_OUT, W_QKV}},
     {{PF_PAIR}, 1, {W_ATTN_OUT, W_WI, W_MLP_OUT, W_QKV}},
     {{PF_PAIR16}, 1, {W_ATTN_OUT, W_WI, W_MLP_OUT, W_QKV}},
+    {{PF_F32}, 1, {W_QKV, W_ATTN_OUT, W_WI, W_MLP_OUT}},
 };
 
 }  // namespace ops

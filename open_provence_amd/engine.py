@@ -75,6 +75,9 @@ class PackedCall(NamedTuple):
     hidden_req: "_lib.OpHiddenRequest | None" = None
     ids_host: "np.ndarray | None" = None
     rows: "torch.Tensor | None" = None  # of an audit's sub-batch: the rows it was gathered from (int32 on the device)
+    # an audit's reference call: `ws` is checked against the kernel set selected WHEN THE CALL IS LAUNCHED and replaced if that set
+    # needs more (op_workspace_bytes depends on the selection: kernel set "fp32" has fp32 planes of its own)
+    size_ws_at_launch: bool = False
 
 
 def parse_precision(precision: "str | Mapping[str, int]") -> tuple[int, list[int]]:
@@ -135,6 +138,21 @@ def resolve_calibration_tolerance(calibrate: "bool | float | None") -> float:
     return DEFAULT_CALIBRATION_TOLERANCE
 
 
+CALIBRATION_REFERENCES = ("bf16x3", "fp32")
+
+
+def check_arithmetic_arguments(kernel_set: "str | None", calibration_reference: "str | None") -> "tuple[str | None, str]":
+    """Validate ``kernel_set=`` / ``calibration_reference=`` before anything touches the device: an unknown name is a
+    ``ValueError``.  Returns them normalised (``"auto"`` -> ``None``; no reference given -> ``"bf16x3"``)."""
+
+    if kernel_set is not None and kernel_set != "auto" and str(kernel_set) not in _lib.KERNEL_SET_IDS:
+        raise ValueError(f"unknown kernel set {kernel_set!r}; expected one of {sorted(_lib.KERNEL_SET_IDS)} or 'auto'")
+    reference = "bf16x3" if calibration_reference is None else str(calibration_reference)
+    if reference not in CALIBRATION_REFERENCES:
+        raise ValueError(f"unknown calibration_reference {calibration_reference!r}; expected one of {CALIBRATION_REFERENCES}")
+    return (None if kernel_set in (None, "auto") else str(kernel_set)), reference
+
+
 def require_gpu(device: torch.device | str | int | None = None) -> torch.device:
     """Resolve a HIP device or fail loudly (the product has no CPU path)."""
 
@@ -168,11 +186,19 @@ class HipEncoder:
         audit: "str | bool | None" = None,
         audit_every: int = 0,
         audit_tokens: int = DEFAULT_AUDIT_TOKENS,
+        kernel_set: "str | None" = None,
+        calibration_reference: str = "bf16x3",
     ) -> None:
         """``audit`` / ``audit_every`` / ``audit_tokens``: how a kernel set chosen by :meth:`calibrate` is re-checked on real
         batches -- ``"first"`` (default; ``None`` reads ``OPEN_PROVENCE_AUDIT``): once, on the first real batch
-        (``audit.first_batch_audit``); ``"running"``: also later, see ``audit.maybe_audit``; ``"off"``: never."""
+        (``audit.first_batch_audit``); ``"running"``: also later, see ``audit.maybe_audit``; ``"off"``: never.
 
+        ``kernel_set``: the set :meth:`load_state_dict` pins when it is given none (``None``: ``OPEN_PROVENCE_KERNEL_SET`` or
+        calibration).  ``"fp32"`` (here or in the environment) makes the handle keep the fp32 GEMM weights that set runs on.
+        ``calibration_reference``: what :meth:`calibrate` compares with -- ``"bf16x3"`` (default: the (hi, lo) bf16 set) or
+        ``"fp32"`` (kernel set "fp32"; keeps the fp32 weights too)."""
+
+        self.kernel_set, self.calibration_reference = check_arithmetic_arguments(kernel_set, calibration_reference)
         self.audit_mode = resolve_audit_mode(audit)
         self.audit_every = int(audit_every)
         self.audit_tokens = int(audit_tokens)
@@ -208,6 +234,8 @@ class HipEncoder:
             waves = os.environ.get("OPEN_PROVENCE_ATT_WAVES")
             if waves:
                 flags |= _lib.OP_FLAG_ATT_WAVES_4 if int(waves) == 4 else _lib.OP_FLAG_ATT_WAVES_8
+        if "fp32" in (self.kernel_set, self.calibration_reference) or os.environ.get("OPEN_PROVENCE_KERNEL_SET") == "fp32":
+            flags |= _lib.OP_FLAG_F32_PACKS
         cfg.flags = int(flags)
         cfg.prune_pre_final_norm = 1 if prune_pre_final_norm else 0
         self.prune_pre_final_norm = bool(prune_pre_final_norm)
@@ -223,6 +251,7 @@ class HipEncoder:
         self._handle = handle
         self._split_state: dict | None = None  # the two pipeline streams + their workspaces (forward_packed_on)
         self._workspace: torch.Tensor | None = None
+        self._audit_workspace: torch.Tensor | None = None  # of an audit's reference forward, when the batch's own is too small for it
         self._capture: torch.Tensor | None = None
         self._capture_result: torch.Tensor | None = None
         self.calibration: dict | None = None  # report of the last calibrate() (load_state_dict runs it by default)
@@ -286,7 +315,7 @@ class HipEncoder:
         self.audit_state.pending = False
         self._reset_coverage(running=False)
         self.calibration = None
-        pinned = kernel_set or os.environ.get("OPEN_PROVENCE_KERNEL_SET")
+        pinned = kernel_set or self.kernel_set or os.environ.get("OPEN_PROVENCE_KERNEL_SET")
         if pinned:
             self.select_kernel_set(pinned)
             return
@@ -343,6 +372,8 @@ class HipEncoder:
             whole_depth = os.environ.get("OPEN_PROVENCE_CALIBRATE_WHOLE_DEPTH", "").strip().lower() in ("1", "on", "true", "yes")
         if whole_depth:
             report.flags |= _lib.OP_CAL_WHOLE_DEPTH
+        if self.calibration_reference == "fp32":
+            report.flags |= _lib.OP_CAL_REFERENCE_F32
         if rows is not None:
             ids_np, cu_np, _ = pack_rows(rows)
             self.check_ids(ids_np)
@@ -706,7 +737,8 @@ class HipEncoder:
         device (``op_gather_rows``), into outputs of its own, with no ``keep_prob`` and no hidden request."""
 
         if rows is None:
-            return call._replace(prune=torch.empty_like(call.prune), rank=torch.empty_like(call.rank), keep_prob=None, hidden_req=None)
+            return call._replace(prune=torch.empty_like(call.prune), rank=torch.empty_like(call.rank), keep_prob=None, hidden_req=None,
+                                 size_ws_at_launch=True)
         sub_lengths = np.diff(call.cu_host)[list(rows)]
         sub_cu_host = np.concatenate(([0], np.cumsum(sub_lengths))).astype(np.int32)
         sub_ids_host = None if call.ids_host is None else np.concatenate([call.ids_host[call.cu_host[r]: call.cu_host[r + 1]] for r in rows])
@@ -721,7 +753,7 @@ class HipEncoder:
         return PackedCall(sub_ids, sub_cu, sub_cu_host, n_sub, sub_total, sub_max,
                           torch.empty((sub_total, 2), dtype=torch.float32, device=self.device),
                           torch.empty((n_sub, self.dims.num_labels), dtype=torch.float32, device=self.device), None,
-                          self._grown_workspace(call.ws, n_sub, sub_total, sub_max), call.stream, None, sub_ids_host, rows_dev)
+                          call.ws, call.stream, None, sub_ids_host, rows_dev, True)
 
     def _logit_error(self, call: PackedCall, ref: PackedCall) -> float:
         """max |logit difference| between ``call``'s outputs and those of ``ref`` (:meth:`_reference_call`); synchronises.  The
@@ -747,7 +779,13 @@ class HipEncoder:
         """``op_forward_packed[_hidden]``: the only place a :class:`PackedCall` becomes C arguments."""
 
         vp = ctypes.c_void_p
-        base = call.ws.data_ptr()
+        ws = call.ws
+        if call.size_ws_at_launch:
+            need = int(self.lib.op_workspace_bytes(self._handle, call.n_seqs, call.total, call.max_seqlen)) + 256
+            if ws is None or ws.numel() < need:
+                # kept on the encoder: the forward is asynchronous, and the next audit finds it again
+                ws = self._audit_workspace = self._grown_workspace(self._audit_workspace, call.n_seqs, call.total, call.max_seqlen)
+        base = ws.data_ptr()
         aligned = (base + 255) // 256 * 256
         extra = () if call.hidden_req is None else (ctypes.byref(call.hidden_req),)
         entry = self.lib.op_forward_packed if call.hidden_req is None else self.lib.op_forward_packed_hidden
@@ -755,7 +793,7 @@ class HipEncoder:
             self._handle, vp(call.ids.data_ptr()), vp(call.cu_seqlens.data_ptr()), call.cu_host.ctypes.data_as(vp),
             call.n_seqs, call.total, call.max_seqlen, vp(call.prune.data_ptr()), vp(call.rank.data_ptr()),
             vp(call.keep_prob.data_ptr()) if call.keep_prob is not None else None,
-            vp(aligned), ctypes.c_size_t(call.ws.numel() - (aligned - base)), vp(call.stream), *extra,
+            vp(aligned), ctypes.c_size_t(ws.numel() - (aligned - base)), vp(call.stream), *extra,
         )
         _lib.check(self.lib, self._handle, code, "op_forward_packed" if call.hidden_req is None else "op_forward_packed_hidden")
 

@@ -33,7 +33,7 @@ import torch
 
 from . import pipeline as pl
 from .config import DEFAULT_PROCESS_THRESHOLD, EncoderDims, OpenProvenceConfig
-from .engine import HiddenRequest, HipEncoder, require_gpu
+from .engine import HiddenRequest, HipEncoder, check_arithmetic_arguments, require_gpu
 from .packing import pack_padded, pack_rows, unpack_to_padded
 from .pipeline import ContextState, FragmentRecord, RawPrediction
 from .splitters import SentenceSplitter, is_builtin_splitter, resolve_sentence_splitter
@@ -222,10 +222,13 @@ class OpenProvenceModel:
         audit: "str | bool | None" = None,
         audit_every: int = 0,
         audit_tokens: int | None = None,
+        calibration_reference: str | None = None,
     ) -> None:
         # kernel_set / calibrate / calibration_rows: how the arithmetic is chosen from the loaded weights
         # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615);
+        # calibration_reference: what a calibration compares with, "bf16x3" (default) or "fp32" (kernel set "fp32");
         # audit / audit_every / audit_tokens: how a calibrated choice is re-checked on real batches (audit.maybe_audit)
+        kernel_set, calibration_reference = check_arithmetic_arguments(kernel_set, calibration_reference)
         self._kernel_set_request = kernel_set
         self._calibrate_request = calibrate
         self._calibration_rows = calibration_rows
@@ -252,6 +255,7 @@ class OpenProvenceModel:
             self.dims, device=self._runtime_device, precision=self.precision, chunk_rows=chunk_rows,
             prune_pre_final_norm=self.pruning_hidden_state == "pre_final_norm",
             audit=audit, audit_every=audit_every, **({} if audit_tokens is None else {"audit_tokens": audit_tokens}),
+            kernel_set=kernel_set, calibration_reference=calibration_reference,
         )
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -529,6 +533,7 @@ class OpenProvenceModel:
             audit=kwargs.pop("audit", None),
             audit_every=kwargs.pop("audit_every", 0),
             audit_tokens=kwargs.pop("audit_tokens", None),
+            calibration_reference=kwargs.pop("calibration_reference", None),
         )
         if max_length is not None:
             model.max_length = int(max_length)
