@@ -315,6 +315,46 @@ int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t
                              float* prune_logits_dev, float* rank_logits_dev, float* keep_prob_dev,
                              void* workspace_dev, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req);
 
+/* Replaces: output_attentions=True of the reference forward under eager attention (standalone.py:1689, 1727; HF :166-185):
+ * the softmax probabilities of ONE layer, as a side pass over that layer's input hidden state.  Additive to ABI 10
+ * (op_abi_version() is unchanged: detect the two calls by symbol).  The residual stream is fp32 at every layer boundary on every
+ * kernel set, so the pass is the same whatever set the handle's forward runs on, and it touches none of the forward's kernels
+ * or its workspace:
+ *   hidden_dev  packed fp32 [total_tokens][hidden] = hidden_states[layer], the INPUT of that layer: entry `layer` of
+ *               op_forward_packed_hidden (pad_width 0, OP_HIDDEN_F32)
+ *   out_dev     [n_seqs][num_heads][pad_width][pad_width] fp32; out[s][h][i][j] = the probability query token i of sequence
+ *               s puts on key token j in head h.  Only keys j < len[s] are visible, on a sliding-window layer only those with
+ *               |i - j| <= local_attention / 2; the layer's own RoPE theta, q scaled by head_dim^-0.5 -- what the attention
+ *               kernel of kernel set "fp32" computes before its P V product.
+ * EVERY element of out_dev is written (the caller zeroes nothing, as with op_unpack_padded): exactly +0.0 at masked keys, at keys
+ * >= len[s], on whole query rows i >= len[s], and out to pad_width in both directions.  DIFFERENCE to the reference: it holds a
+ * softmax row at padded query positions (over the visible keys); this call returns zeros there, as the hidden states do.
+ * Arithmetic: the fp32 kernels of kernel set "fp32" -- LayerNorm(attn_norm) (none on layer 0, as in the forward), the q | k
+ * column tiles of the Wqkv projection with RoPE on the fp32-input MFMA (v is not computed) -- and one kernel of the call's own:
+ * two passes over the visible 64-key tiles, the first for the row maximum and sum, the second stores expf(s - max) / sum.  A
+ * probability depends on its own sequence only.  The pass needs the fp32 weight packs: OP_ERR_UNSUPPORTED on a handle created
+ * without OP_FLAG_F32_PACKS (the message names the flag); any handle shape (row, panel, tiled).
+ * Refused with OP_ERR_INVALID before anything is enqueued and before the handle is looked at: a NULL request, a wrong
+ * struct_bytes, a dtype other than OP_HIDDEN_F32, a pad_width below max_seqlen (or 0 for a non-empty batch), hidden_dev /
+ * out_dev NULL for a non-empty batch, n_seqs * pad_width beyond 2^31 - 1 (element counts themselves are size_t).  `layer` is
+ * checked once the handle is known.
+ * The workspace is the call's own: op_attention_workspace_bytes (row maps, the state in the row layout, the LayerNorm plane, q
+ * and k; large batches go through in chunks of sequences, as in the forward).  It may hold anything on entry, and nothing
+ * outside it and out_dev is written.  Asynchronous on hip_stream (cu_seqlens_host == NULL: cu_seqlens_dev is read back, which
+ * synchronises the stream once); no handle state is stored: as stream-safe as op_forward_packed. */
+typedef struct op_attention_request {
+  uint32_t struct_bytes;   /* sizeof(op_attention_request) */
+  int32_t layer;           /* 0 <= layer < num_layers */
+  int32_t dtype;           /* OP_HIDDEN_F32 only for now; anything else OP_ERR_INVALID */
+  int32_t pad_width;       /* >= max_seqlen (and > 0 for a non-empty batch) */
+  const float* hidden_dev; /* packed fp32 [total_tokens][hidden] = hidden_states[layer] */
+  void* out_dev;           /* [n_seqs][num_heads][pad_width][pad_width] fp32 */
+} op_attention_request;
+size_t op_attention_workspace_bytes(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen);
+int op_attention_probs(op_handle* h, const int32_t* cu_seqlens_dev, const int32_t* cu_seqlens_host, int n_seqs, int total_tokens,
+                       int max_seqlen, const op_attention_request* req, void* workspace_dev, size_t workspace_bytes,
+                       void* hip_stream);
+
 /* The padded boundary on the device.  Replaces: the reference forward taking `input_ids[B, L]` + `attention_mask[B, L]` as
  * they come from the tokenizer (standalone.py:1666-1690) and returning `pruning_logits[B, L, 2]` (standalone.py:1695-1739);
  * additive to ABI 10 (op_abi_version() is unchanged: detect the two calls by symbol).

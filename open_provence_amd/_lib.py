@@ -61,6 +61,8 @@ EXPORTED_SYMBOLS = (
     "op_workspace_bytes",
     "op_forward_packed",
     "op_forward_packed_hidden",
+    "op_attention_workspace_bytes",
+    "op_attention_probs",
     "op_pack_padded",
     "op_unpack_padded",
     "op_coverage_scan",
@@ -143,6 +145,19 @@ class OpHiddenRequest(ctypes.Structure):
 
 
 OP_HIDDEN_F32, OP_HIDDEN_BF16 = 0, 1
+
+
+class OpAttentionRequest(ctypes.Structure):
+    """``op_attention_request``: the layer whose attention probabilities one ``op_attention_probs`` call writes."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("layer", ctypes.c_int32),
+        ("dtype", ctypes.c_int32),
+        ("pad_width", ctypes.c_int32),
+        ("hidden_dev", ctypes.c_void_p),
+        ("out_dev", ctypes.c_void_p),
+    ]
 
 
 class OpPaddedReport(ctypes.Structure):
@@ -243,6 +258,11 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "op_forward_packed_hidden"):
         lib.op_forward_packed_hidden.restype = ci
         lib.op_forward_packed_hidden.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, cs, vp, ctypes.POINTER(OpHiddenRequest)]
+    if hasattr(lib, "op_attention_probs"):  # (additive to ABI 10: an older library loaded for an A/B has neither)
+        lib.op_attention_workspace_bytes.restype = cs
+        lib.op_attention_workspace_bytes.argtypes = [vp, ci, ci, ci]
+        lib.op_attention_probs.restype = ci
+        lib.op_attention_probs.argtypes = [vp, vp, vp, ci, ci, ci, ctypes.POINTER(OpAttentionRequest), vp, cs, vp]
     lib.op_effective_policy.restype = ci
     lib.op_effective_policy.argtypes = [vp, ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ci)]
     if hasattr(lib, "op_set_compact_operands"):  # (absent only in an older library loaded for a same-box A/B, see below)

@@ -25,7 +25,7 @@ _COMMON = [CSRC / "opk_common.hip.h"]
 _ROWGEMM = [CSRC / name for name in ("opk_rowgemm.hip.h", "opk_rowgemm_pack.hip.h", "opk_rowgemm_stream.hip.h", "opk_rowgemm_ln.hip.h", "opk_kstream.hip.h",
                                      "opk_rowgemm_phase1.hip.h", "opk_rowgemm_mlp.hip.h", "opk_rowgemm_mlp_ops.inc", "opk_rowgemm_mlp_loop.inc",
                                      "opk_rowgemm_qkv_pairs.hip.h", "opk_rowgemm_chunks.hip.h")]
-_INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_f32.hip.h", CSRC / "opk_attn.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
+_INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_f32.hip.h", CSRC / "opk_attn.hip.h", CSRC / "opk_attn_probs.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
 
 _PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
 _AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
@@ -46,6 +46,7 @@ UNITS = [
     ("op_launch_padded", CSRC / "op_launch_padded.hip", [], _INTERNAL + [_PADDED]),
     ("op_launch_audit", CSRC / "op_launch_audit.hip", [], _INTERNAL + [_AUDIT]),
     ("op_launch_f32", CSRC / "op_launch_f32.hip", [], _INTERNAL),
+    ("op_launch_attn_probs", CSRC / "op_launch_attn_probs.hip", [], _INTERNAL),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = sorted({h for u in UNITS for h in u[3]})

@@ -1984,6 +1984,48 @@ int op_profile_read(op_handle* h, op_profile_entry* entries, int max_entries) {
   return n;
 }
 
+// The batch's cu_seqlens on the host -- the caller's copy, or read back from the device (synchronises the stream once) -- held
+// to what every pass over a packed batch relies on: 0 .. total_tokens, monotone, no row beyond max_seqlen or the RoPE tables.
+static int host_cu_seqlens(op_handle* h, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs, int total_tokens, int max_seqlen,
+                           hipStream_t stream, std::vector<int32_t>& cu_copy, const int32_t** cu_out) {
+  const int32_t* cu = cu_host_in;
+  if (!cu) {
+    cu_copy.resize((size_t)n_seqs + 1);
+    OP_HIP(h, hipMemcpyAsync(cu_copy.data(), cu_dev, cu_copy.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
+    OP_HIP(h, hipStreamSynchronize(stream));
+    cu = cu_copy.data();
+  }
+  if (cu[0] != 0 || cu[n_seqs] != total_tokens)
+    return fail(h, OP_ERR_INVALID, "cu_seqlens must start at 0 and end at total_tokens (%d): got %d..%d", total_tokens,
+                cu[0], cu[n_seqs]);
+  for (int s = 0; s < n_seqs; ++s) {
+    const int len = cu[s + 1] - cu[s];
+    if (len < 0) return fail(h, OP_ERR_INVALID, "cu_seqlens not monotone at %d", s);
+    if (len > max_seqlen) return fail(h, OP_ERR_INVALID, "sequence %d has %d tokens > max_seqlen %d", s, len, max_seqlen);
+    if (len > h->max_pos)
+      return fail(h, OP_ERR_UNSUPPORTED, "sequence %d has %d tokens > max_position_embeddings %d", s, len, h->max_pos);
+  }
+  *cu_out = cu;
+  return OP_OK;
+}
+
+// The chunk of sequences that starts at s0: as many as fit `cap` rows (at least one) -> one past its last sequence, with
+// its rows (every sequence rounded up to ROW_ALIGN) and its longest sequence.
+static int next_chunk(const int32_t* cu, int s0, int n_seqs, int cap, int* rows_out, int* max_len_out) {
+  int rows = 0, s1 = s0, max_len = 0;
+  while (s1 < n_seqs) {
+    const int len = cu[s1 + 1] - cu[s1];
+    const int r = align_up(len, ROW_ALIGN);
+    if (s1 > s0 && rows + r > cap) break;
+    rows += r;
+    max_len = std::max(max_len, len);
+    ++s1;
+  }
+  *rows_out = rows;
+  *max_len_out = max_len;
+  return s1;
+}
+
 // op_forward_packed, and op_forward_packed_hidden with its validated request (hid; nullptr: none)
 static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
                                int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
@@ -2010,23 +2052,8 @@ static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32
   hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
 
   std::vector<int32_t> cu_copy;
-  const int32_t* cu = cu_host_in;
-  if (!cu) {
-    cu_copy.resize((size_t)n_seqs + 1);
-    OP_HIP(h, hipMemcpyAsync(cu_copy.data(), cu_dev, cu_copy.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    OP_HIP(h, hipStreamSynchronize(stream));
-    cu = cu_copy.data();
-  }
-  if (cu[0] != 0 || cu[n_seqs] != total_tokens)
-    return fail(h, OP_ERR_INVALID, "cu_seqlens must start at 0 and end at total_tokens (%d): got %d..%d", total_tokens,
-                cu[0], cu[n_seqs]);
-  for (int s = 0; s < n_seqs; ++s) {
-    const int len = cu[s + 1] - cu[s];
-    if (len < 0) return fail(h, OP_ERR_INVALID, "cu_seqlens not monotone at %d", s);
-    if (len > max_seqlen) return fail(h, OP_ERR_INVALID, "sequence %d has %d tokens > max_seqlen %d", s, len, max_seqlen);
-    if (len > h->max_pos)
-      return fail(h, OP_ERR_UNSUPPORTED, "sequence %d has %d tokens > max_position_embeddings %d", s, len, h->max_pos);
-  }
+  const int32_t* cu = nullptr;
+  OP_TRY(host_cu_seqlens(h, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, stream, cu_copy, &cu));
 
   const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
   const int cap_pad = align_up(cap + 64, 256);
@@ -2036,15 +2063,8 @@ static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32
   Launcher L{h, stream};
   int s0 = 0;
   while (s0 < n_seqs) {
-    int rows = 0, s1 = s0, max_len = 0;
-    while (s1 < n_seqs) {
-      const int len = cu[s1 + 1] - cu[s1];
-      const int r = align_up(len, ROW_ALIGN);
-      if (s1 > s0 && rows + r > cap) break;
-      rows += r;
-      max_len = std::max(max_len, len);
-      ++s1;
-    }
+    int rows = 0, max_len = 0;
+    const int s1 = next_chunk(cu, s0, n_seqs, cap, &rows, &max_len);
     if (rows > cap) return fail(h, OP_ERR_WORKSPACE, "internal: chunk of %d rows exceeds capacity %d", rows, cap);
     // attention work items of the full-attention layers: 256-query blocks (8 waves) once a sequence is longer than
     // 128 tokens, else 128 -- unless that leaves CUs idle (small request): then 128-query blocks, twice as many work
@@ -2114,6 +2134,139 @@ int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t
     return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: out_dev is NULL with %d entries selected", n_sel);
   return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
                              workspace, workspace_bytes, hip_stream, n_sel > 0 ? &hid : nullptr);
+}
+
+// ---- op_attention_probs: the softmax probabilities of one layer, a side pass over that layer's input hidden state ----------
+struct AttnProbsWorkspace {
+  int32_t *roff, *row_seq, *row_pos, *row_tok;
+  float *x, *ln, *q, *k;
+  size_t bytes;
+};
+
+// (the regions in the order they are first written: row maps, the gathered state, LayerNorm(attn_norm), q and k)
+static void carve_attention(const op_handle* h, char* base, int cap_rows_pad, int n_seqs, AttnProbsWorkspace& ws) {
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    char* p = base ? base + off : nullptr;
+    off += align_up_sz(bytes, 256);
+    return p;
+  };
+  const size_t R = (size_t)cap_rows_pad, plane = R * (size_t)h->H * sizeof(float);
+  ws.roff = reinterpret_cast<int32_t*>(take(((size_t)n_seqs + 1) * 4));
+  ws.row_seq = reinterpret_cast<int32_t*>(take(R * 4));
+  ws.row_pos = reinterpret_cast<int32_t*>(take(R * 4));
+  ws.row_tok = reinterpret_cast<int32_t*>(take(R * 4));
+  ws.x = reinterpret_cast<float*>(take(plane));
+  ws.ln = reinterpret_cast<float*>(take(plane));
+  ws.q = reinterpret_cast<float*>(take(plane));
+  ws.k = reinterpret_cast<float*>(take(plane));
+  ws.bytes = off;
+}
+
+size_t op_attention_workspace_bytes(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen) {
+  if (!h || n_seqs < 0 || total_tokens < 0 || max_seqlen < 0) return 0;
+  const int cap_pad = align_up(chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen) + 64, 256);  // (as op_workspace_bytes)
+  AttnProbsWorkspace ws;
+  carve_attention(h, nullptr, cap_pad, n_seqs, ws);
+  return ws.bytes;
+}
+
+int op_attention_probs(op_handle* h, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs, int total_tokens, int max_seqlen,
+                       const op_attention_request* req, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  // (the request's own fields first: none of them needs the handle)
+  if (!req) return fail(h, OP_ERR_INVALID, "op_attention_probs: the request is NULL");
+  if (req->struct_bytes != sizeof(op_attention_request))
+    return fail(h, OP_ERR_INVALID, "op_attention_probs: op_attention_request.struct_bytes is %u, expected %zu", req->struct_bytes,
+                sizeof(op_attention_request));
+  if (req->dtype != OP_HIDDEN_F32) return fail(h, OP_ERR_INVALID, "op_attention_probs: dtype %d is not OP_HIDDEN_F32", req->dtype);
+  if (n_seqs < 0 || total_tokens < 0 || max_seqlen < 0) return fail(h, OP_ERR_INVALID, "op_attention_probs: negative size");
+  const bool empty = n_seqs == 0 || total_tokens == 0;
+  if (req->pad_width < 0 || req->pad_width < max_seqlen || (!empty && req->pad_width == 0))
+    return fail(h, OP_ERR_INVALID, "op_attention_probs: pad_width %d below max_seqlen %d", req->pad_width, max_seqlen);
+  if (!empty && !req->hidden_dev) return fail(h, OP_ERR_INVALID, "op_attention_probs: hidden_dev is NULL");
+  if (!empty && !req->out_dev) return fail(h, OP_ERR_INVALID, "op_attention_probs: out_dev is NULL");
+  if ((size_t)n_seqs * (size_t)req->pad_width > (size_t)INT32_MAX)  // (output rows are 32-bit indices inside a sequence's matrices)
+    return fail(h, OP_ERR_INVALID, "op_attention_probs: %zu output rows per head exceed 2^31 - 1", (size_t)n_seqs * (size_t)req->pad_width);
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_attention_probs: NULL handle");
+  if (req->layer < 0 || req->layer >= h->N)
+    return fail(h, OP_ERR_INVALID, "op_attention_probs: layer %d outside 0 .. %d", req->layer, h->N - 1);
+  if (!h->f32_packs)
+    return fail(h, OP_ERR_UNSUPPORTED, "op_attention_probs: the pass needs the fp32 weight packs: create the handle with OP_FLAG_F32_PACKS");
+  if (op_weights_ready(h) != OP_OK) return OP_ERR_STATE;
+
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  const int width = req->pad_width;
+  const size_t mat_elems = (size_t)h->nh * (size_t)width * (size_t)width;  // one sequence
+  float* out = reinterpret_cast<float*>(req->out_dev);
+  if (n_seqs == 0 || width == 0) return OP_OK;
+  if (total_tokens == 0) {  // only empty sequences: every row is padding
+    OP_HIP(h, hipMemsetAsync(out, 0, (size_t)n_seqs * mat_elems * sizeof(float), stream));
+    return OP_OK;
+  }
+  if (!cu_dev || !workspace) return fail(h, OP_ERR_INVALID, "op_attention_probs: NULL buffer");
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  const size_t need = op_attention_workspace_bytes(h, n_seqs, total_tokens, max_seqlen);
+  if (workspace_bytes < need) return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, need);
+
+  std::vector<int32_t> cu_copy;
+  const int32_t* cu = nullptr;
+  OP_TRY(host_cu_seqlens(h, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, stream, cu_copy, &cu));
+
+  const int li = req->layer, H = h->H;
+  const bool is_global = h->cfg.layer_is_global[li] != 0;
+  const float* attn_norm = li != 0 ? h->layers[li].attn_norm : nullptr;  // layer 0: the identity, as in the forward
+  const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
+  AttnProbsWorkspace ws;
+  carve_attention(h, reinterpret_cast<char*>(workspace), align_up(cap + 64, 256), n_seqs, ws);
+
+  int s0 = 0;
+  while (s0 < n_seqs) {  // chunks of sequences, as the forward takes them
+    int rows = 0, max_len = 0;
+    const int s1 = next_chunk(cu, s0, n_seqs, cap, &rows, &max_len);
+    if (rows > cap) return fail(h, OP_ERR_WORKSPACE, "internal: chunk of %d rows exceeds capacity %d", rows, cap);
+    const int ns = s1 - s0;
+    const int r_pad = align_up(std::max(rows, 1), GEMM_BM);
+    // row map; the state's rows (zero rows where the map holds no token); LayerNorm; q | k with RoPE, q scaled
+    hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, stream, cu_dev, s0, ns, ROW_ALIGN, ROW_ALIGN, ws.roff);
+    hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, stream, cu_dev, s0, ns, ws.roff, r_pad,
+                       ws.row_seq, ws.row_pos, ws.row_tok);
+    opl::launch_attn_probs_gather(stream, req->hidden_dev, ws.row_tok, H, r_pad, ws.x);
+    if (attn_norm) opl::launch_f32_ln(stream, ws.x, attn_norm, h->cfg.norm_eps, H, r_pad, ws.ln);
+    F32GemmParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.a = attn_norm ? ws.ln : ws.x;
+    gp.w = reinterpret_cast<const float*>(h->layers[li].pack[W_QKV][PF_F32]);
+    gp.K = H;
+    gp.n_tiles = 2 * H / GEMM_BN;  // the q and k column tiles only
+    gp.m_tiles = r_pad / GEMM_BM;
+    gp.o0 = ws.q;
+    gp.o1 = ws.k;
+    gp.ld_out = H;
+    gp.hidden = H;
+    gp.inter = h->I;
+    gp.row_pos = ws.row_pos;
+    gp.rope_cos = h->rope_cos[is_global ? 1 : 0];
+    gp.rope_sin = h->rope_sin[is_global ? 1 : 0];
+    gp.max_pos = h->max_pos;
+    if (!opl::launch_f32_gemm(stream, gp, F32_EPI_QKV)) return fail(h, OP_ERR_UNSUPPORTED, "internal: no fp32 GEMM epilogue %d", F32_EPI_QKV);
+    AttnProbsParams ap;
+    ap.q = ws.q;
+    ap.k = ws.k;
+    ap.out = out;
+    ap.cu = cu_dev;
+    ap.s0 = s0;
+    ap.roff = ws.roff;
+    ap.H = H;
+    ap.num_heads = h->nh;
+    ap.window = is_global ? -1 : h->cfg.local_attention / 2;
+    ap.width = width;
+    ap.wide = (width % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
+    opl::launch_attn_probs(stream, ap, ns);
+    OP_HIP(h, hipGetLastError());
+    s0 = s1;
+  }
+  return OP_OK;
 }
 
 int op_pack_padded(op_handle* h, const void* ids_dev, int ids_dtype, const void* mask_dev, int mask_dtype, int n_rows, int width,

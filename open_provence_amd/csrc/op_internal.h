@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "opk_attn.hip.h"
+#include "opk_attn_probs.hip.h"
 #include "opk_common.hip.h"
 #include "opk_f32.hip.h"
 #include "opk_layer32.hip.h"
@@ -105,6 +106,12 @@ void launch_f32_attn(hipStream_t st, const opk::F32AttnParams& p, dim3 grid);
 void launch_f32_rank_head(hipStream_t st, int n_seqs, const float* cls, const float* y, const int32_t* cu, int s0, const int32_t* roff,
                           int mean_pool, int H, int nl, const float* dense_t, const float* head_norm, float eps, const float* cls_w,
                           const float* cls_b, float* rank_out);
+
+// op_attention_probs (opk_attn_probs.hip.h; op_launch_attn_probs.hip) beside launch_f32_ln and launch_f32_gemm(F32_EPI_QKV).
+// packed [total_tokens][H] fp32 -> the row layout [r_pad][H] through row_tok (zero rows where row_tok < 0)
+void launch_attn_probs_gather(hipStream_t st, const float* packed, const int32_t* row_tok, int H, int r_pad, float* x);
+// grid: (64-query blocks of p.width, heads, the n_seqs sequences from p.s0 on); every element of their matrices is written
+void launch_attn_probs(hipStream_t st, const opk::AttnProbsParams& p, int n_seqs);
 
 // The padded [B, L] boundary (opk_padded.hip.h; op_pack_padded / op_unpack_padded).  Integer types as enum op_int_dtype.
 constexpr int PAD_INT_I32 = 0, PAD_INT_I64 = 1, PAD_INT_U8 = 2;

@@ -58,6 +58,19 @@ class HiddenRequest:
     pad_width: int = 0
 
 
+@dataclass(frozen=True)
+class AttentionRequest:
+    """The attention probabilities one forward returns beside its logits (``op_attention_probs``, a side pass over the
+    hidden states the forward hands out; the encoder must have been created with ``attention_outputs=True``).
+
+    ``layers``: the layers 0 .. num_layers - 1 to return; None = all of them.  ``pad_width``: rows and columns of every
+    ``[B, heads, pad_width, pad_width]`` fp32 tensor (zeros at masked keys, beyond each sequence's length and on padded query
+    rows); 0 = ``max_seqlen``, otherwise at least that."""
+
+    layers: "Sequence[int] | None" = None
+    pad_width: int = 0
+
+
 class PackedCall(NamedTuple):
     """What one ``op_forward_packed[_hidden]`` call needs: the batch, where its logits go, and what it runs with."""
 
@@ -188,6 +201,7 @@ class HipEncoder:
         audit_tokens: int = DEFAULT_AUDIT_TOKENS,
         kernel_set: "str | None" = None,
         calibration_reference: str = "bf16x3",
+        attention_outputs: bool = False,
     ) -> None:
         """``audit`` / ``audit_every`` / ``audit_tokens``: how a kernel set chosen by :meth:`calibrate` is re-checked on real
         batches -- ``"first"`` (default; ``None`` reads ``OPEN_PROVENCE_AUDIT``): once, on the first real batch
@@ -196,7 +210,10 @@ class HipEncoder:
         ``kernel_set``: the set :meth:`load_state_dict` pins when it is given none (``None``: ``OPEN_PROVENCE_KERNEL_SET`` or
         calibration).  ``"fp32"`` (here or in the environment) makes the handle keep the fp32 GEMM weights that set runs on.
         ``calibration_reference``: what :meth:`calibrate` compares with -- ``"bf16x3"`` (default: the (hi, lo) bf16 set) or
-        ``"fp32"`` (kernel set "fp32"; keeps the fp32 weights too)."""
+        ``"fp32"`` (kernel set "fp32"; keeps the fp32 weights too).
+        ``attention_outputs``: keep the fp32 GEMM weights (4 bytes per weight element more on the device) so that
+        :meth:`attention_probs` / ``forward_packed(attentions=...)`` can run; it changes nothing else.  ``kernel_set="fp32"``
+        and ``calibration_reference="fp32"`` imply it."""
 
         self.kernel_set, self.calibration_reference = check_arithmetic_arguments(kernel_set, calibration_reference)
         self.audit_mode = resolve_audit_mode(audit)
@@ -236,6 +253,9 @@ class HipEncoder:
                 flags |= _lib.OP_FLAG_ATT_WAVES_4 if int(waves) == 4 else _lib.OP_FLAG_ATT_WAVES_8
         if "fp32" in (self.kernel_set, self.calibration_reference) or os.environ.get("OPEN_PROVENCE_KERNEL_SET") == "fp32":
             flags |= _lib.OP_FLAG_F32_PACKS
+        if attention_outputs:
+            flags |= _lib.OP_FLAG_F32_PACKS
+        self.attention_outputs = bool(flags & _lib.OP_FLAG_F32_PACKS)  # the fp32 weight packs op_attention_probs reads exist
         cfg.flags = int(flags)
         cfg.prune_pre_final_norm = 1 if prune_pre_final_norm else 0
         self.prune_pre_final_norm = bool(prune_pre_final_norm)
@@ -251,6 +271,7 @@ class HipEncoder:
         self._handle = handle
         self._split_state: dict | None = None  # the two pipeline streams + their workspaces (forward_packed_on)
         self._workspace: torch.Tensor | None = None
+        self._attention_workspace: torch.Tensor | None = None  # op_attention_probs' own, reused across layers and calls
         self._audit_workspace: torch.Tensor | None = None  # of an audit's reference forward, when the batch's own is too small for it
         self._capture: torch.Tensor | None = None
         self._capture_result: torch.Tensor | None = None
@@ -475,18 +496,21 @@ class HipEncoder:
             )
         return bool(changed.value)
 
-    def forward_packed_checked(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None, ids_host=None):
+    def forward_packed_checked(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None, ids_host=None,
+                               attentions=None):
         """``forward_packed`` + the range guard: on kernel sets 3 / 4 the outputs are tested for NaN / Inf (one device
         reduction, one synchronisation) and a non-finite batch is repeated on the (hi, lo) bf16 sets.  On those sets
         nothing is tested: whatever comes out is what the reference's arithmetic gives.  With a ``hidden`` request the
-        result is ``(prune, rank, hidden_states)``, the states of the forward whose logits are returned."""
+        result is ``(prune, rank, hidden_states)``, the states of the forward whose logits are returned; with an
+        ``attentions`` request its last element is the list of that forward's attention probabilities."""
 
-        out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden, ids_host=ids_host)
+        extra = {} if attentions is None else {"attentions": attentions}
+        out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden, ids_host=ids_host, **extra)
         if self.f8_active():
             prune, rank = out[0], out[1]
             ok = torch.isfinite(rank).all() & torch.isfinite(prune).all()
             if not bool(ok.item()) and self.fall_back_from_f8("forward"):
-                out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden, ids_host=ids_host)
+                out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden, ids_host=ids_host, **extra)
         return out
 
     # -- forward ---------------------------------------------------------------------------------
@@ -547,6 +571,7 @@ class HipEncoder:
         keep_prob: torch.Tensor | None = None,
         hidden: "HiddenRequest | None" = None,
         ids_host: "np.ndarray | None" = None,
+        attentions: "AttentionRequest | None" = None,
     ) -> tuple[torch.Tensor, ...]:
         """``ids[T]`` / ``cu_seqlens[B+1]`` int32 on this device -> (prune_logits[T, 2], rank_logits[B, nl]) fp32.
         ``keep_prob`` (optional, fp32 ``[T]`` on this device) additionally receives
@@ -555,7 +580,12 @@ class HipEncoder:
         (packed ``[n_sel, T, H]`` or padded ``[n_sel, B, pad_width, H]``, zeros at padding); the logits are bit-identical
         to those of the same forward without the request.  ``ids_host`` (optional): the host copy of ``ids`` the caller
         already holds (what it handed to :meth:`check_ids`); the running audit decides coverage on it without touching the
-        device (``audit.maybe_audit``).
+        device (``audit.maybe_audit``).  ``attentions`` (an :class:`AttentionRequest`; the encoder needs
+        ``attention_outputs=True``): the result tuple gains, as its LAST element, the list of the requested layers' attention
+        probabilities ``[B, heads, W, W]`` fp32.  The forward then runs with a packed fp32 hidden request for those layers'
+        inputs (merged with the caller's ``hidden`` request, whose states are laid out from the merged ones) and
+        ``op_attention_probs`` runs once per layer behind it on the same stream; logits and hidden states are bit-identical to
+        those of the same call without the request.
 
         Asynchronous on the current torch stream of ``self.device`` (a forward that is audited synchronises it once)."""
 
@@ -565,8 +595,101 @@ class HipEncoder:
             )
             capture_ptr = ctypes.c_void_p(self._capture.data_ptr())
             _lib.check(self.lib, self._handle, self.lib.op_debug_capture_hidden(self._handle, capture_ptr), "capture")
+        if attentions is not None:
+            return self._forward_with_attentions(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host, attentions)
         call, states = self._forward(None, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host)
         return (call.prune, call.rank) if states is None else (call.prune, call.rank, states)
+
+    # -- attention probabilities: a side pass over the hidden states the forward hands out ---------------------------------------
+    def _require_attention_outputs(self) -> None:
+        if not self.attention_outputs:
+            raise ValueError("attention probabilities need the fp32 weight packs: create the encoder / model with attention_outputs=True")
+        if not hasattr(self.lib, "op_attention_probs"):
+            raise _lib.HipLibraryError("this library has no op_attention_probs")
+
+    def _forward_with_attentions(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host, attentions):
+        """One forward with the merged hidden request, then ``op_attention_probs`` per requested layer."""
+
+        if not isinstance(attentions, AttentionRequest):
+            raise TypeError("attentions must be an AttentionRequest")
+        self._require_attention_outputs()
+        n_layers = self.dims.num_layers
+        layers = list(range(n_layers)) if attentions.layers is None else [int(i) for i in attentions.layers]
+        if any(i < 0 or i >= n_layers for i in layers):
+            raise ValueError(f"attentions.layers must lie in 0 .. {n_layers - 1}")
+        max_seqlen = int(max_seqlen)
+        width = int(attentions.pad_width) or max_seqlen
+        if width < max_seqlen:
+            raise ValueError(f"attentions.pad_width must be 0 (= max_seqlen) or at least max_seqlen ({max_seqlen}), got {width}")
+        # the caller's own request is validated as it would be alone (its tensors are not needed: the merged request's are)
+        own = None
+        if hidden is not None:
+            own = sorted(set(range(n_layers + 1) if hidden.layers is None else (int(i) for i in hidden.layers)))
+            self._hidden_request(hidden, 0, 0, max_seqlen)
+        # hidden_states[i] is the input of layer i: one packed fp32 request for every entry either side needs
+        merged = sorted(set(layers) | set(own or ()))
+        call, states = self._forward(None, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob,
+                                     HiddenRequest(layers=merged, dtype=torch.float32, pad_width=0), ids_host)
+        slot = {entry: k for k, entry in enumerate(merged)}
+        probs = [self.attention_probs(states[slot[i]], i, cu_seqlens, call.cu_host, max_seqlen, width) for i in layers]
+        if own is None:
+            return call.prune, call.rank, probs
+        mine = states if own == merged else states[[slot[i] for i in own]]
+        if hidden.pad_width > 0:  # (the layout the kernels give a padded request: zeros beyond each sequence's length)
+            from .packing import unpack_to_padded
+
+            mine = torch.stack([unpack_to_padded(entry, call.cu_host, int(hidden.pad_width)) for entry in mine]) if len(own) else \
+                mine.new_zeros((0, call.n_seqs, int(hidden.pad_width), self.dims.hidden_size))
+        return call.prune, call.rank, mine.to(hidden.dtype), probs
+
+    def attention_probs(self, hidden_packed: torch.Tensor, layer: int, cu_seqlens: torch.Tensor, cu_seqlens_host: np.ndarray,
+                        max_seqlen: int, pad_width: int = 0) -> torch.Tensor:
+        """``hidden_packed[T, H]`` fp32 on this device = ``hidden_states[layer]``, the INPUT of that layer (entry ``layer`` of a
+        packed fp32 :class:`HiddenRequest`) -> its attention probabilities ``[B, heads, W, W]`` fp32, ``W = pad_width`` (0:
+        ``max_seqlen``): ``out[s, h, i, j]`` = what query token ``i`` of sequence ``s`` puts on key ``j``; exactly 0 at masked
+        keys, beyond the sequence's length and on padded query rows (every element is written by the call).  fp32 arithmetic
+        of kernel set "fp32" whatever set the forward runs on.  Asynchronous on the current torch stream."""
+
+        self._require_attention_outputs()
+        H, max_seqlen = self.dims.hidden_size, int(max_seqlen)
+        if (hidden_packed.dtype != torch.float32 or hidden_packed.device != self.device or hidden_packed.ndim != 2
+                or hidden_packed.shape[1] != H or not hidden_packed.is_contiguous()):
+            raise ValueError(f"hidden_packed must be a contiguous fp32 [total_tokens, {H}] tensor on {self.device}")
+        if cu_seqlens.dtype != torch.int32 or cu_seqlens.device != self.device:
+            raise ValueError(f"cu_seqlens must be int32 on {self.device}")
+        if not 0 <= int(layer) < self.dims.num_layers:
+            raise ValueError(f"layer must lie in 0 .. {self.dims.num_layers - 1}")
+        total, n_seqs = int(hidden_packed.shape[0]), int(cu_seqlens.numel()) - 1
+        width = int(pad_width) or max_seqlen
+        if width < max_seqlen:
+            raise ValueError(f"pad_width must be 0 (= max_seqlen) or at least max_seqlen ({max_seqlen}), got {width}")
+        cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
+        if cu_host.shape[0] != n_seqs + 1:
+            raise ValueError("cu_seqlens_host length mismatch")
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            out = torch.empty((n_seqs, self.dims.num_heads, width, width), dtype=torch.float32, device=self.device)
+            if out.numel() == 0:
+                return out
+            need = int(self.lib.op_attention_workspace_bytes(self._handle, n_seqs, total, max_seqlen)) + 256
+            ws = self._attention_workspace
+            if ws is None or ws.numel() < need:
+                ws = self._attention_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            base = ws.data_ptr()
+            aligned = (base + 255) // 256 * 256
+            req = _lib.OpAttentionRequest()
+            req.struct_bytes = ctypes.sizeof(_lib.OpAttentionRequest)
+            req.layer = int(layer)
+            req.dtype = _lib.OP_HIDDEN_F32
+            req.pad_width = width
+            req.hidden_dev = vp(hidden_packed.data_ptr()) if total else None
+            req.out_dev = vp(out.data_ptr())
+            code = self.lib.op_attention_probs(
+                self._handle, vp(cu_seqlens.data_ptr()), cu_host.ctypes.data_as(vp), n_seqs, total, max_seqlen, ctypes.byref(req),
+                vp(aligned), ctypes.c_size_t(ws.numel() - (aligned - base)), vp(torch.cuda.current_stream(self.device).cuda_stream),
+            )
+        _lib.check(self.lib, self._handle, code, "op_attention_probs")
+        return out
 
     def _forward(self, part: "int | None", ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None, ids_host=None,
                  running: "bool | None" = True) -> "tuple[PackedCall, torch.Tensor | None]":
@@ -845,6 +968,7 @@ class HipEncoder:
         max_seqlen: int,
         keep_prob: torch.Tensor | None = None,
         hidden: "HiddenRequest | None" = None,
+        attentions: "AttentionRequest | None" = None,
     ) -> tuple[torch.Tensor, torch.Tensor]:
         """``forward_packed`` enqueued on pipeline ``part`` (0 or 1): its own HIP stream (own hardware queue; the whole chip
         since round 6, see ``_split_streams``) and its own workspace -- nothing is ordered against the caller's current stream or the other
@@ -861,6 +985,8 @@ class HipEncoder:
             raise RuntimeError("hidden-state capture is not available on the pipelined path (use forward_packed)")
         if hidden is not None:
             raise NotImplementedError("hidden-state requests are not available on the pipelined path (use forward_packed(hidden=...))")
+        if attentions is not None:
+            raise NotImplementedError("attention requests are not available on the pipelined path (use forward_packed(attentions=...))")
         call, _ = self._forward(part, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, running=False)
         return call.prune, call.rank
 

@@ -33,7 +33,7 @@ import torch
 
 from . import pipeline as pl
 from .config import DEFAULT_PROCESS_THRESHOLD, EncoderDims, OpenProvenceConfig
-from .engine import HiddenRequest, HipEncoder, check_arithmetic_arguments, require_gpu
+from .engine import AttentionRequest, HiddenRequest, HipEncoder, check_arithmetic_arguments, require_gpu
 from .packing import pack_padded, pack_rows, unpack_to_padded
 from .pipeline import ContextState, FragmentRecord, RawPrediction
 from .splitters import SentenceSplitter, is_builtin_splitter, resolve_sentence_splitter
@@ -223,7 +223,10 @@ class OpenProvenceModel:
         audit_every: int = 0,
         audit_tokens: int | None = None,
         calibration_reference: str | None = None,
+        attention_outputs: bool = False,
     ) -> None:
+        # attention_outputs: keep the fp32 GEMM weights on the device so that forward(output_attentions=True) can run
+        # (HipEncoder; nothing else changes);
         # kernel_set / calibrate / calibration_rows: how the arithmetic is chosen from the loaded weights
         # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615);
         # calibration_reference: what a calibration compares with, "bf16x3" (default) or "fp32" (kernel set "fp32");
@@ -255,7 +258,7 @@ class OpenProvenceModel:
             self.dims, device=self._runtime_device, precision=self.precision, chunk_rows=chunk_rows,
             prune_pre_final_norm=self.pruning_hidden_state == "pre_final_norm",
             audit=audit, audit_every=audit_every, **({} if audit_tokens is None else {"audit_tokens": audit_tokens}),
-            kernel_set=kernel_set, calibration_reference=calibration_reference,
+            kernel_set=kernel_set, calibration_reference=calibration_reference, attention_outputs=attention_outputs,
         )
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -534,6 +537,7 @@ class OpenProvenceModel:
             audit_every=kwargs.pop("audit_every", 0),
             audit_tokens=kwargs.pop("audit_tokens", None),
             calibration_reference=kwargs.pop("calibration_reference", None),
+            attention_outputs=bool(kwargs.pop("attention_outputs", False)),
         )
         if max_length is not None:
             model.max_length = int(max_length)
@@ -566,6 +570,7 @@ class OpenProvenceModel:
         labels: torch.Tensor | None = None,
         return_dict: bool | None = None,
         output_hidden_states: bool | None = None,
+        output_attentions: bool | None = None,
         **kwargs: Any,
     ) -> OpenProvenceOutput | tuple[torch.Tensor, ...]:
         """``input_ids[B, L]`` (+ right-padded ``attention_mask``) -> ``ranking_logits[B, nl]`` and
@@ -576,12 +581,20 @@ class OpenProvenceModel:
         padding positions) as the reference returns them (standalone.py:1689, 1727): the embedding LayerNorm output, the
         output of every layer, and last the pruning head's input (``final_norm`` output, or the raw last layer under
         ``prune_pre_final_norm``).  They are views of one device buffer ``[N + 1, B, L, H]`` that the forward's own
-        kernels write; the logits are bit-identical to those of the same call without the flag."""
+        kernels write; the logits are bit-identical to those of the same call without the flag.
+
+        ``output_attentions=True`` (a model created with ``attention_outputs=True``; ``ValueError`` otherwise): ``attentions``
+        is a tuple of num_layers fp32 tensors ``[B, heads, L, L]`` as the reference returns them under eager attention
+        (standalone.py:1689, 1727) -- except that padded QUERY rows are zeros here, where the reference holds a softmax row.
+        A side pass over the hidden states (``op_attention_probs``): logits and hidden states are bit-identical to those of
+        the same call without the flag.  Memory: ``num_layers x B x heads x L^2 x 4`` bytes."""
 
         if input_ids is None:
             raise ValueError("input_ids must be provided")
         if labels is not None:
             raise NotImplementedError("training losses are outside the MI355X inference path")
+        if output_attentions and not self.encoder.attention_outputs:
+            raise ValueError("output_attentions=True needs the fp32 weight packs: create the model with attention_outputs=True")
         dev = self._runtime_device
         # A batch that already lives on the model's GPU is packed, checked and (below) unpacked there by HIP kernels
         # (op_pack_padded / op_unpack_padded: same results, same errors); CPU tensors, and tensors of another GPU, go through
@@ -598,15 +611,19 @@ class OpenProvenceModel:
             cu = torch.from_numpy(cu_np).to(dev)
         width = int(input_ids.shape[1])
         # (the fp16 + e4m3 kernel sets are range-guarded: a non-finite result is repeated on the (hi, lo) bf16 sets)
-        hidden_states = None
+        hidden_states = attentions = None
+        requests: dict[str, Any] = {}
         if output_hidden_states:
-            prune, rank, hidden = self.encoder.forward_packed_checked(
-                ids, cu, cu_np, max_len, hidden=HiddenRequest(dtype=torch.float32, pad_width=width), ids_host=ids_np
-            )
+            requests["hidden"] = HiddenRequest(dtype=torch.float32, pad_width=width)
+        if output_attentions:
+            requests["attentions"] = AttentionRequest(pad_width=width)
+        prune, rank, *extra = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len, ids_host=ids_np, **requests)
+        if output_attentions:
+            attentions = tuple(extra.pop())
+        if output_hidden_states:
+            hidden = extra.pop()
             # ([N + 1, B, L, H]; with L = 0 the request is packed and empty: the same shape, no data)
             hidden_states = tuple(hidden.reshape(hidden.shape[0], int(input_ids.shape[0]), width, hidden.shape[-1]).unbind(0))
-        else:
-            prune, rank = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len, ids_host=ids_np)
         if on_device:
             pruning_logits = self.encoder.unpack_padded_device(prune, cu, int(input_ids.shape[0]), width)
         else:
@@ -614,7 +631,8 @@ class OpenProvenceModel:
         if return_dict is not None and not return_dict:
             return (rank, pruning_logits)
         return OpenProvenceOutput(
-            loss=None, logits=rank, ranking_logits=rank, pruning_logits=pruning_logits, hidden_states=hidden_states, attentions=None
+            loss=None, logits=rank, ranking_logits=rank, pruning_logits=pruning_logits, hidden_states=hidden_states,
+            attentions=attentions,
         )
 
     def __call__(self, *args: Any, **kwargs: Any):
@@ -2250,9 +2268,10 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
         super().__init__(config, **kwargs)
         self.num_labels = config.num_pruning_labels
 
-    def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, output_hidden_states=None, **kwargs: Any):
+    def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, output_hidden_states=None,
+                output_attentions=None, **kwargs: Any):
         base = OpenProvenceModel.forward(self, input_ids=input_ids, attention_mask=attention_mask, labels=labels, return_dict=True,
-                                         output_hidden_states=output_hidden_states)
+                                         output_hidden_states=output_hidden_states, output_attentions=output_attentions)
         if return_dict is not None and not return_dict:
             return (base["pruning_logits"],)
         return OpenProvenceOutput(
@@ -2261,7 +2280,7 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
             pruning_logits=base["pruning_logits"],
             ranking_logits=base["ranking_logits"],
             hidden_states=base["hidden_states"],
-            attentions=None,
+            attentions=base["attentions"],
         )
 
 
