@@ -7,14 +7,13 @@ profiles/attention_probs.txt is the readable record)."""
 
 from __future__ import annotations
 
-import ctypes
 import json
 
 import numpy as np
 import pytest
 import torch
 
-from attention_utils import fixture_encoder, fixture_errors, packed_batch, selectable_sets, visible_mask
+from attention_utils import c_attention_probs as _c_attention_probs, fixture_encoder, fixture_errors, packed_batch, selectable_sets, visible_mask
 from helpers import GOLDEN_DIR, CharTokenizer, dims_from_meta, load_golden, state_from_fixture
 
 pytestmark = pytest.mark.gpu
@@ -142,24 +141,6 @@ def _hidden_states(enc, rows):
     ids, cu, cu_np, max_len = packed_batch(enc, rows)
     _, _, states = enc.forward_packed(ids, cu, cu_np, max_len, hidden=HiddenRequest())
     return states, cu, cu_np, max_len
-
-
-def _c_attention_probs(enc, hidden, layer, cu, cu_np, max_len, out, ws, host_cu=True):
-    """op_attention_probs with the caller's own output and workspace tensors (host_cu=False: no host copy of cu_seqlens, the call
-    reads it back) -> the return code"""
-
-    from open_provence_amd import _lib
-
-    vp = ctypes.c_void_p
-    req = _lib.OpAttentionRequest()
-    req.struct_bytes = ctypes.sizeof(_lib.OpAttentionRequest)
-    req.layer, req.dtype, req.pad_width = layer, _lib.OP_HIDDEN_F32, int(out.shape[-1])
-    req.hidden_dev, req.out_dev = vp(hidden.data_ptr()), vp(out.data_ptr())
-    base = ws.data_ptr()
-    aligned = (base + 255) // 256 * 256
-    return enc.lib.op_attention_probs(enc._handle, vp(cu.data_ptr()), cu_np.ctypes.data_as(vp) if host_cu else None, len(cu_np) - 1, int(hidden.shape[0]), max_len,
-                                      ctypes.byref(req), vp(aligned), ctypes.c_size_t(ws.numel() - (aligned - base)),
-                                      vp(torch.cuda.current_stream(enc.device).cuda_stream))
 
 
 def test_every_element_is_written():
