@@ -487,6 +487,16 @@ typedef struct op_workspace_region {
 int op_debug_workspace_layout(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen, op_workspace_region* entries,
                               int max_entries);
 
+/* Test hook.  Replaces: nothing.  The RoPE tables as the library builds them, fp32 [max_pos, 32] each (head_dim 64: entry
+ * [p][k] is cos / sin of fp32(p) * inv_freq[k]; the kernels read column k for dimensions k and k + 32), copied to HOST memory.
+ *   h == NULL: the tables op_create builds for `theta` and `max_pos`, by the same function, without touching a device
+ *              (global_table is ignored);
+ *   h != NULL: the handle's own table on its device -- global_table != 0: the full-attention layers' (global_rope_theta),
+ *              else the sliding-window layers' -- `max_pos` must be the handle's max_position_embeddings (theta is ignored).
+ * Synchronous.  OP_ERR_INVALID on a NULL buffer, max_pos <= 0, theta <= 0 or a max_pos that is not the handle's.
+ * Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol). */
+int op_debug_rope_tables(const op_handle* h, int global_table, float theta, int max_pos, float* cos_host, float* sin_host);
+
 /* Measurement hook: when enabled every kernel launch of the forward is bracketed by HIP events
  * on the launch stream; op_profile_read returns accumulated milliseconds and launch counts per
  * kernel kind (names via op_profile_kind_name) and resets nothing; op_profile_reset clears. */

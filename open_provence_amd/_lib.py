@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "op_audit_compare",
     "op_segment_means",
     "op_debug_workspace_layout",
+    "op_debug_rope_tables",
     "op_debug_capture_hidden",
     "op_profile_enable",
     "op_profile_read",
@@ -297,6 +298,9 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "op_debug_workspace_layout"):  # (test hook, additive to ABI 10)
         lib.op_debug_workspace_layout.restype = ci
         lib.op_debug_workspace_layout.argtypes = [vp, ci, ci, ci, ctypes.POINTER(OpWorkspaceRegion), ci]
+    if hasattr(lib, "op_debug_rope_tables"):  # (test hook, additive to ABI 10)
+        lib.op_debug_rope_tables.restype = ci
+        lib.op_debug_rope_tables.argtypes = [vp, ci, ctypes.c_float, ci, vp, vp]
     lib.op_segment_means.restype = ci
     lib.op_segment_means.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     lib.op_debug_capture_hidden.restype = ci

@@ -166,15 +166,20 @@ void erase_missing(op_handle* h, const std::string& name) {
   if (it != h->missing.end()) h->missing.erase(it);
 }
 
-// RoPE tables exactly as HF builds them (modeling_modernbert.py:117-163): inv_freq in fp32,
-// angle = fp32(pos) * inv_freq in fp32, cos/sin of that fp32 angle.
+// RoPE tables by HF's recipe (modeling_modernbert.py:117-163), reproduced to the bit in inv_freq: HF computes
+// 1.0 / (theta ** (arange(0, 64, 2, fp32) / 64)) in fp32, which rounds TWICE -- an fp32 power, then an fp32 reciprocal.  The
+// power is taken in double and rounded to fp32 (torch's fp32 pow agrees with the correctly rounded one on all 32 exponents at
+// theta 10000 and 160000), then divided in fp32.  Rounding once, (float)(1.0 / pow(theta, e)), is one ulp off in 10 / 8 of the
+// 32 entries at those thetas, and the angle's error grows with the position: 1.2e-4 in the table at position 8191.
+// angle = fp32(pos) * inv_freq in fp32; cos / sin of that fp32 angle, correctly rounded (torch's cosf is within 6e-8 of it).
+// tests/test_rope_tables.py holds the tables to torch's within 2^-23 through op_debug_rope_tables.
 void build_rope_host(float theta, int max_pos, std::vector<float>& cs, std::vector<float>& sn) {
   cs.resize((size_t)max_pos * ROPE_HALF);
   sn.resize((size_t)max_pos * ROPE_HALF);
   float inv_freq[ROPE_HALF];
   for (int k = 0; k < ROPE_HALF; ++k) {
     const float expo = (float)(2 * k) / (float)HEAD_DIM;
-    inv_freq[k] = (float)(1.0 / std::pow((double)theta, (double)expo));
+    inv_freq[k] = 1.0f / (float)std::pow((double)theta, (double)expo);
   }
   for (int p = 0; p < max_pos; ++p) {
     for (int k = 0; k < ROPE_HALF; ++k) {
@@ -1924,6 +1929,25 @@ int op_debug_workspace_layout(const op_handle* h, int n_seqs, int total_tokens, 
   carve(h, nullptr, cap_pad, n_seqs, h->set == OP_KS_F32, ws, &layout);
   for (size_t i = 0; i < layout.size() && i < (size_t)max_entries; ++i) entries[i] = layout[i];
   return (int)layout.size();
+}
+
+int op_debug_rope_tables(const op_handle* h, int global_table, float theta, int max_pos, float* cos_host, float* sin_host) {
+  if (max_pos <= 0 || !cos_host || !sin_host) return OP_ERR_INVALID;
+  const size_t count = (size_t)max_pos * ROPE_HALF;
+  if (!h) {  // no handle, no device: the tables op_create would build for this theta
+    if (!(theta > 0.f)) return OP_ERR_INVALID;
+    std::vector<float> cs, sn;
+    build_rope_host(theta, max_pos, cs, sn);
+    std::copy(cs.begin(), cs.end(), cos_host);
+    std::copy(sn.begin(), sn.end(), sin_host);
+    return OP_OK;
+  }
+  const int t = global_table ? 1 : 0;
+  if (max_pos != h->max_pos || !h->rope_cos[t] || !h->rope_sin[t]) return OP_ERR_INVALID;
+  if (hipSetDevice(h->cfg.device_id) != hipSuccess) return OP_ERR_HIP;
+  if (hipMemcpy(cos_host, h->rope_cos[t], count * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return OP_ERR_HIP;
+  if (hipMemcpy(sin_host, h->rope_sin[t], count * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return OP_ERR_HIP;
+  return OP_OK;
 }
 
 int op_debug_capture_hidden(op_handle* h, float* hidden_dev) {

@@ -538,6 +538,19 @@ class HipEncoder:
         return [{"name": e.name.decode(), "offset": int(e.offset), "bytes": int(e.bytes), "kind": _lib.WORKSPACE_KINDS[int(e.kind)]}
                 for e in entries]
 
+    def rope_tables(self, global_table: bool) -> "tuple[torch.Tensor, torch.Tensor]":
+        """Test hook (``op_debug_rope_tables``): this handle's cos / sin tables as they lie on the device, fp32
+        ``[max_position_embeddings, 32]`` each on the CPU; ``global_table``: the full-attention layers' table."""
+
+        if not hasattr(self.lib, "op_debug_rope_tables"):
+            raise _lib.HipLibraryError("this library has no op_debug_rope_tables")
+        n = int(self.dims.max_position_embeddings)
+        cos, sin = torch.empty(n, 32, dtype=torch.float32), torch.empty(n, 32, dtype=torch.float32)
+        code = self.lib.op_debug_rope_tables(self._handle, int(bool(global_table)), 0.0, n, ctypes.c_void_p(cos.data_ptr()),
+                                             ctypes.c_void_p(sin.data_ptr()))
+        _lib.check(self.lib, self._handle, int(code), "op_debug_rope_tables")
+        return cos, sin
+
     def segment_means(self, values: torch.Tensor, segments: torch.Tensor) -> torch.Tensor:
         """``values[T]`` fp32 and ``segments[S, 2]`` int32 (token ranges ``[start, end)``) on this device ->
         ``[S]`` fp32: ``values[start:end].mean()`` in numpy's float32 pairwise order, bit for bit; 1.0 for an empty

@@ -258,7 +258,10 @@ def attention(q, k, v, vis, arith: Arith, layer: int, tile: int):
     p = torch.exp2(s - m).masked_fill(~vis, 0.0)
     fsm = sqk.hi is F16  # the fp16 attention sums the rounded p
     l = (rne(p, F16) if fsm else p).sum(dim=-1, keepdim=True)
-    return contract(p, v, spv) / l
+    o = contract(p, v, spv) / l
+    if bool(vis.any(dim=-1).all()):
+        return o
+    return o.masked_fill(~vis.any(dim=-1)[..., None], 0.0)  # (only a mutated mask hides every key of a query: its output is 0)
 
 
 def rank_logits(state: Mapping[str, torch.Tensor], dims, last_rows: Sequence[torch.Tensor], pool=None) -> torch.Tensor:
@@ -297,7 +300,7 @@ class Backbone:
 
 
 def backbone(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int]], arith: "Arith | str" = "exact", *,
-             path: str = "row", rope_is_global: "Sequence[bool] | None" = None) -> Backbone:
+             path: str = "row", rope_is_global: "Sequence[bool] | None" = None, rope=None, visibility=None) -> Backbone:
     """The layers of :func:`forward` (its arguments)."""
 
     if isinstance(arith, str):
@@ -316,7 +319,7 @@ def backbone(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[in
         offs.append(offs[-1] + n)
     ids = torch.tensor([int(t) for r in rows for t in r], dtype=torch.long)
     T = offs[-1]
-    rope = {g: _rope(hd, dims.global_rope_theta if g else dims.local_rope_theta, max(Lmax, 1)) for g in (True, False)}
+    rope = {g: (rope or _rope)(hd, dims.global_rope_theta if g else dims.local_rope_theta, max(Lmax, 1)) for g in (True, False)}
     qscale = hd**-0.5 * LOG2E
 
     x = _layer_norm(W("model.embeddings.tok_embeddings.weight")[ids], W("model.embeddings.norm.weight"), eps)
@@ -338,7 +341,8 @@ def backbone(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[in
             q, k, v = (qkv[a:e, j].transpose(0, 1) for j in range(3))  # [nh, n, hd]
             q = (q * c + _rot(q) * s) * qscale
             k = k * c + _rot(k) * s
-            ctx[a:e] = attention(q, k, v, visible(n, hw), arith, i, tile).transpose(0, 1).reshape(n, H)
+            vis = visible(n, hw) if visibility is None else visibility(visible(n, hw), glob)
+            ctx[a:e] = attention(q, k, v, vis, arith, i, tile).transpose(0, 1).reshape(n, H)
         x = x + contract(ctx, W(p + "attn.Wo.weight").T, arith.scheme("attn_out", i))
         h = _layer_norm(x, W(p + "mlp_norm.weight"), eps)
         g_in, gate = contract(h, W(p + "mlp.Wi.weight").T, arith.scheme("wi", i)).chunk(2, dim=-1)
@@ -376,14 +380,16 @@ def heads(state: Mapping[str, torch.Tensor], dims, body: Backbone, *, prune_pre_
 
 def forward(state: Mapping[str, torch.Tensor], dims, rows: Sequence[Sequence[int]], arith: "Arith | str" = "exact", *,
             path: str = "row", prune_pre_final_norm: bool = False,
-            rope_is_global: "Sequence[bool] | None" = None) -> ModelOutput:
+            rope_is_global: "Sequence[bool] | None" = None, rope=None, visibility=None) -> ModelOutput:
     """The forward on ragged ``rows`` of token ids (no padding enters any row's arithmetic).  Hidden entry 0 is the
     embedding LayerNorm output, entry i the output of layer i - 1, entry N the final_norm output -- or, under
     ``prune_pre_final_norm``, the un-normalised last layer (the pruning head's input either way, as op_hidden_request).
     ``rope_is_global``: mutation hook, per layer which RoPE table its q / k take (None = the layer's own type; the mask and
-    the key tiles always follow the layer's own type)."""
+    the key tiles always follow the layer's own type); ``rope``: mutation hook, a replacement for :func:`_rope` ((head_dim, theta,
+    n) -> cos, sin [n, head_dim] float64); ``visibility``: mutation hook, (the layer's [n, n] mask, the layer is global) -> the
+    mask the attention applies (a query left without a visible key gets a zero attention output)."""
 
-    body = backbone(state, dims, rows, arith, path=path, rope_is_global=rope_is_global)
+    body = backbone(state, dims, rows, arith, path=path, rope_is_global=rope_is_global, rope=rope, visibility=visibility)
     return heads(state, dims, body, prune_pre_final_norm=prune_pre_final_norm)
 
 

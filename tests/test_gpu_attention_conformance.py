@@ -15,7 +15,8 @@ probability is at most 1.  Each case prints ``err / e_ref`` (profiles/attention_
 2. a zero state gives ``1 / count`` on every visible key, to 1 ulp: every window edge, sequence end and tile edge of every
    query, whatever mass sits there;
 3. nothing but ``out`` and the advertised workspace bytes is written, on both store paths at both alignments of ``out``;
-4. batch composition: a row alone, a chunked handle, empty sequences inside a batch;
+4. batch composition: a row alone, a chunked handle, empty sequences inside a batch; a 4097-token row next to an empty and a
+   5-token sequence (every other row of the module has at most 321 tokens);
 5. end to end on kernel set "fp32" (the forward's rounding included in e_ref)."""
 
 from __future__ import annotations
@@ -189,6 +190,58 @@ def test_empty_sequences_inside_a_batch():
                 empty = [s for s, n in enumerate(lengths) if not n]
                 assert bool((out[empty].view(torch.int32) == 0).all()), f"layer {layer}: an empty sequence's matrix is not all +0.0"
                 assert torch.equal(out[[s for s, n in enumerate(lengths) if n]], want), f"layer {layer}: the empty sequences change the others"
+    finally:
+        enc.close()
+
+
+LONG_LENGTHS = [4097, 0, 5]
+
+
+def test_a_4097_token_row_next_to_an_empty_and_a_short_one():
+    """One token past 4096 (65 key tiles, RoPE table rows beyond 2048, window ranges far from the row's start) on the first
+    full-attention and the first sliding-window layer of the 4-head trained-like model, pad_width 4097: each real row within
+    the module's bound of the fp64 restatement of that row alone, exact +0.0 outside the visible keys and in the whole matrix of
+    the empty sequence, nothing written around ``out`` or behind the advertised workspace bytes."""
+
+    from open_provence_amd.synthetic import pad_rows
+    from oracle.modernbert_oracle import oracle_forward
+
+    torch.set_num_threads(16)
+    dims, state = au.conformance_model("T")
+    assert dims.num_heads == 4 and dims.max_position_embeddings >= max(LONG_LENGTHS)
+    kinds = [bool(g) for g in dims.layer_is_global]
+    layers = [kinds.index(True), kinds.index(False)]
+    real = [n for n in LONG_LENGTHS if n]
+    ids, mask = pad_rows(au.edge_rows(real, vocab=dims.vocab_size))
+    hidden = oracle_forward(state, dims, ids, mask, dtype=torch.float64, return_hidden=True).hidden_states
+    width, B = max(LONG_LENGTHS), len(LONG_LENGTHS)
+    cu_np = np.concatenate(([0], np.cumsum(LONG_LENGTHS))).astype(np.int32)
+    enc = au.conformance_encoder(dims, state)
+    try:
+        cu = torch.from_numpy(cu_np).to(enc.device)
+        need = int(enc.lib.op_attention_workspace_bytes(enc._handle, B, int(cu_np[-1]), width))
+        assert need > 0
+        for layer in layers:
+            h32 = hidden[layer].to(torch.float32)
+            packed = h32[mask.bool()].contiguous().to(enc.device)
+            got = _guarded_call(enc, packed, layer, cu, cu_np, width, (B, dims.num_heads, width, width), 0, need).cpu()
+            err = e_ref = 0.0
+            source = iter(range(len(real)))
+            for s, n in enumerate(LONG_LENGTHS):
+                if not n:
+                    assert bool((got[s].view(torch.int32) == 0).all()), f"layer {layer}: the empty sequence's matrix is not all +0.0"
+                    continue
+                row_mask = torch.zeros((1, width), dtype=torch.int64)
+                row_mask[0, :n] = 1
+                au.check_probs_pattern(f"long row {s} ({n} tokens)", got[s: s + 1], dims, row_mask, layer)
+                alone, ones = h32[next(source)][None, :n], torch.ones((1, n), dtype=torch.int64)
+                want = au.attention_probs(state, dims, alone, ones, layer, torch.float64)
+                e_ref = max(e_ref, float((au.attention_probs(state, dims, alone, ones, layer, torch.float32).double() - want).abs().max()))
+                err = max(err, float((got[s, :, :n, :n].double() - want[0]).abs().max()))
+            bound = au.probs_bound(e_ref)
+            print(f"[attn-conf] {'kernel T rows 4097+0+5':30s} layer {layer}  err {err:.3e}  e_ref {e_ref:.3e}  err/e_ref {err / max(e_ref, 1e-30):6.2f}  "
+                  f"bound {bound:.3e}")
+            assert err <= bound, f"layer {layer}: {err:.3e} from the fp64 restatement, bound {bound:.3e} (e_ref {e_ref:.3e})"
     finally:
         enc.close()
 

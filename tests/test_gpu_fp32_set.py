@@ -42,12 +42,12 @@ F32_REGIONS = ["ln_f", "q_f", "k_f", "v_f", "o_f", "h_f"]
 
 
 # -- models --------------------------------------------------------------------------------------------------------------------
-def _small_dims(hidden, heads, pattern, window, pooling, labels):
+def _small_dims(hidden, heads, pattern, window, pooling, labels, max_positions=2048):
     from open_provence_amd.config import EncoderDims
 
     cfg = dict(model_type="modernbert", vocab_size=512, hidden_size=hidden, intermediate_size=192, num_hidden_layers=3,
                num_attention_heads=heads, local_attention=window, global_attn_every_n_layers=3, global_rope_theta=160000.0,
-               local_rope_theta=10000.0, max_position_embeddings=2048, pad_token_id=0, cls_token_id=1, sep_token_id=2,
+               local_rope_theta=10000.0, max_position_embeddings=max_positions, pad_token_id=0, cls_token_id=1, sep_token_id=2,
                layer_types=["full_attention" if t == "G" else "sliding_attention" for t in pattern], classifier_pooling=pooling)
     return EncoderDims.from_base_model_config(cfg, num_labels=labels)
 
@@ -211,6 +211,25 @@ def test_a_row_alone_equals_the_row_inside_the_ragged_batch(case):
             a, b = int(cu[s]), int(cu[s + 1])
             assert torch.equal(p1, prune[a:b]) and torch.equal(r1, rank[s: s + 1]) and torch.equal(k1, keep[a:b]), f"row {s} ({len(row)} tokens)"
             assert torch.equal(h1, hidden[:, a:b]), f"row {s} ({len(row)} tokens): hidden states"
+    finally:
+        enc.close()
+
+
+LONG_LENGTHS = [4097, 5]  # one token past 4096: 65 key tiles, RoPE table rows beyond 2048, the window far from the row's start
+
+
+def test_a_4097_token_row_matches_the_oracle():
+    """The set at length (no other row of this module exceeds 512 tokens): every entry within the module's bound of the fp64
+    oracle, on a handle whose max_position_embeddings is 8192, one full-attention and two sliding-window layers."""
+
+    case = SMALL[2]
+    dims, state = _small_dims(*case[:6], max_positions=8192), _small_state(case)
+    rows = _rows(LONG_LENGTHS)
+    ref = Reference(state, dims, rows, case[6])
+    enc = _encoder(dims, state, prune_pre_final_norm=case[6])
+    try:
+        got, _ = _forward(enc, rows)
+        _check(f"{case[0]} {case[2]} w{case[3]} rows 4097+5", got, ref)
     finally:
         enc.close()
 

@@ -142,16 +142,17 @@ def _print_table():
 
 
 def _dims(model: str, window: int = 128, *, layer_types: "str | None" = None, pooling: "str | None" = None,
-          labels: "int | None" = None):
+          labels: "int | None" = None, max_position_embeddings: int = 2048):
     """``layer_types``: one letter per layer, "G" (full attention) / "L" (sliding window), None = one global layer, then
-    sliding-window layers; ``pooling``: "cls" (None) / "mean"; ``labels``: ranking labels (None = 1)."""
+    sliding-window layers; ``pooling``: "cls" (None) / "mean"; ``labels``: ranking labels (None = 1);
+    ``max_position_embeddings``: the longest row the handle takes (tests/test_kernel_set_long_rows.py: 8192)."""
 
     from open_provence_amd.config import EncoderDims
 
     H, I, nh, nl = SHAPES[model]
     cfg = dict(model_type="modernbert", vocab_size=512, hidden_size=H, intermediate_size=I, num_hidden_layers=nl,
                num_attention_heads=nh, local_attention=window, global_attn_every_n_layers=nl, global_rope_theta=160000.0,
-               local_rope_theta=10000.0, max_position_embeddings=2048, pad_token_id=0, cls_token_id=1, sep_token_id=2)
+               local_rope_theta=10000.0, max_position_embeddings=max_position_embeddings, pad_token_id=0, cls_token_id=1, sep_token_id=2)
     if layer_types is not None:
         assert len(layer_types) == nl and set(layer_types) <= {"G", "L"}, layer_types
         cfg["layer_types"] = ["full_attention" if t == "G" else "sliding_attention" for t in layer_types]
