@@ -497,6 +497,46 @@ int op_debug_workspace_layout(const op_handle* h, int n_seqs, int total_tokens, 
  * Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol). */
 int op_debug_rope_tables(const op_handle* h, int global_table, float theta, int max_pos, float* cos_host, float* sin_host);
 
+/* Test hook.  Replaces: nothing.  Runs the device functions the forward's kernels are built from (opk_common.hip.h: the
+ * operand conversions, the GELU polynomial, the exponentials, RoPE, the keep-probability, the scaled e4m3 MFMA) over `n`
+ * input elements at in_dev and stores what they return, as raw bits, at out_dev: one launch on `hip_stream`, asynchronous.
+ * `mode` is the wave's conversion mode while the primitive runs: 0 = IEEE overflow (fp16 -> Inf, e4m3 -> NaN), 1 =
+ * saturating (MODE.FP16_OVFL: fp16 clamps to +-65504, e4m3 to +-448), the mode of every kernel that writes e4m3 planes.
+ * Inputs are fp32 unless stated; a record is written per input element unless stated; "word" = uint32.
+ *   kind                 group  record
+ *   OP_PROBE_BF16_SPLIT    4    7 words: (hi, lo) bf16 bits of split2, of split2_pk, of split4; f2bf bits
+ *   OP_PROBE_F16_PAIR      4    3 words: (hi, lo) fp16 bits of split4_f16; f2h bits
+ *   OP_PROBE_F16_F8        4    2 words: hi fp16 bits, lo e4m3 byte of split4_f8 (lo = e4m3((v - hi) x 2^12))
+ *   OP_PROBE_E4M3_F16      4    1 word : e4m3 byte of f16x4_to_e4m3 (input: uint16 fp16 bits)
+ *   OP_PROBE_E4M3_F32      4    3 words: e4m3 byte of f32x4_to_e4m3; of a weight's e4m3 plane e4m3(v x 2^6); of its lo plane
+ *                               e4m3((v - fp16(v)) x 2^18), the last two as the weight pack kernels write them
+ *   OP_PROBE_GELU          1    2 fp32 : gelu_erf(x); the same polynomial issued in stages, as the whole-layer kernels do
+ *   OP_PROBE_EXP2          1    2 fp32 : the attention's exp2 (v_exp_f32); __expf(x)
+ *   OP_PROBE_ROPE          4    2 fp32 per group (x1, x2, cos, sin): rope_lo, rope_hi
+ *   OP_PROBE_KEEP_PROB     2    1 fp32 per group (l0, l1): the keep-probability 1 / (1 + e^(l0 - l1)) of the pruning head
+ *   OP_PROBE_MFMA_SCALE    2    4 x 256 fp32 per group (input: uint8 e4m3 bytes a, b): the 16 x 16 results of the four scaled
+ *                               e4m3 products (K = 128) of the "f16 + fp8" sets with every byte of one operand = a and of
+ *                               the other = b: lo(activation) x e4m3(weight) in both operand orders, then e4m3(activation) x
+ *                               lo(weight) in both; every element is 128 a b 2^-18
+ * OP_ERR_INVALID, before anything is enqueued, on a NULL handle, an unknown kind or mode, an n that is not a multiple of the
+ * kind's group, n > 2^31, or a NULL buffer with n > 0; n == 0 launches nothing.  The kernels index by element number only,
+ * checked against n: no input value is used as an address.  Additive to ABI 10 (op_abi_version() is unchanged: detect the
+ * call by symbol).  tests/test_gpu_primitives.py holds every record to tests/arith_model.py's operand roundings, bit for
+ * bit, and the fp32 functions to float64. */
+enum op_probe_kind {
+  OP_PROBE_BF16_SPLIT = 0,
+  OP_PROBE_F16_PAIR = 1,
+  OP_PROBE_F16_F8 = 2,
+  OP_PROBE_E4M3_F16 = 3,
+  OP_PROBE_E4M3_F32 = 4,
+  OP_PROBE_GELU = 5,
+  OP_PROBE_EXP2 = 6,
+  OP_PROBE_ROPE = 7,
+  OP_PROBE_KEEP_PROB = 8,
+  OP_PROBE_MFMA_SCALE = 9
+};
+int op_debug_primitive(op_handle* h, int kind, int mode, const void* in_dev, size_t n, void* out_dev, void* hip_stream);
+
 /* Measurement hook: when enabled every kernel launch of the forward is bracketed by HIP events
  * on the launch stream; op_profile_read returns accumulated milliseconds and launch counts per
  * kernel kind (names via op_profile_kind_name) and resets nothing; op_profile_reset clears. */

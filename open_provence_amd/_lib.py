@@ -73,6 +73,7 @@ EXPORTED_SYMBOLS = (
     "op_segment_means",
     "op_debug_workspace_layout",
     "op_debug_rope_tables",
+    "op_debug_primitive",
     "op_debug_capture_hidden",
     "op_profile_enable",
     "op_profile_read",
@@ -207,6 +208,20 @@ class OpWorkspaceRegion(ctypes.Structure):
 OP_WS_FLOAT, OP_WS_INDEX, OP_WS_FLAG = 0, 1, 2
 WORKSPACE_KINDS = {OP_WS_FLOAT: "float", OP_WS_INDEX: "index", OP_WS_FLAG: "flag"}
 
+# enum op_probe_kind (op_debug_primitive): name -> (kind, input dtype name, inputs per group, output dtype name, outputs per group)
+PROBE_KINDS = {
+    "BF16_SPLIT": (0, "float32", 4, "int32", 28),
+    "F16_PAIR": (1, "float32", 4, "int32", 12),
+    "F16_F8": (2, "float32", 4, "int32", 8),
+    "E4M3_F16": (3, "int16", 4, "int32", 4),
+    "E4M3_F32": (4, "float32", 4, "int32", 12),
+    "GELU": (5, "float32", 1, "float32", 2),
+    "EXP2": (6, "float32", 1, "float32", 2),
+    "ROPE": (7, "float32", 4, "float32", 2),
+    "KEEP_PROB": (8, "float32", 2, "float32", 1),
+    "MFMA_SCALE": (9, "uint8", 2, "float32", 1024),
+}
+
 OP_CAL_FULL_REPORT = 1
 OP_CAL_WHOLE_DEPTH = 2
 OP_CAL_REFERENCE_F32 = 4  # op_calibrate compares with kernel set "fp32" (a handle created with OP_FLAG_F32_PACKS)
@@ -301,6 +316,9 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "op_debug_rope_tables"):  # (test hook, additive to ABI 10)
         lib.op_debug_rope_tables.restype = ci
         lib.op_debug_rope_tables.argtypes = [vp, ci, ctypes.c_float, ci, vp, vp]
+    if hasattr(lib, "op_debug_primitive"):  # (test hook, additive to ABI 10)
+        lib.op_debug_primitive.restype = ci
+        lib.op_debug_primitive.argtypes = [vp, ci, ci, vp, cs, vp, vp]
     lib.op_segment_means.restype = ci
     lib.op_segment_means.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     lib.op_debug_capture_hidden.restype = ci

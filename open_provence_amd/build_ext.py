@@ -47,6 +47,7 @@ UNITS = [
     ("op_launch_audit", CSRC / "op_launch_audit.hip", [], _INTERNAL + [_AUDIT]),
     ("op_launch_f32", CSRC / "op_launch_f32.hip", [], _INTERNAL),
     ("op_launch_attn_probs", CSRC / "op_launch_attn_probs.hip", [], _INTERNAL),
+    ("op_launch_probe", CSRC / "op_launch_probe.hip", [], _INTERNAL + [CSRC / "opk_probe.hip.h"]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = sorted({h for u in UNITS for h in u[3]})

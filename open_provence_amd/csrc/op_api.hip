@@ -1950,6 +1950,20 @@ int op_debug_rope_tables(const op_handle* h, int global_table, float theta, int 
   return OP_OK;
 }
 
+int op_debug_primitive(op_handle* h, int kind, int mode, const void* in_dev, size_t n, void* out_dev, void* hip_stream) {
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_debug_primitive: NULL handle");
+  const int group = opl::probe_group_size(kind);
+  if (group == 0 || (mode != 0 && mode != 1)) return fail(h, OP_ERR_INVALID, "op_debug_primitive: unknown kind %d or mode %d", kind, mode);
+  if (n % (size_t)group != 0) return fail(h, OP_ERR_INVALID, "op_debug_primitive: n = %zu is not a multiple of kind %d's group of %d", n, kind, group);
+  if (n > ((size_t)1 << 31)) return fail(h, OP_ERR_INVALID, "op_debug_primitive: n = %zu is beyond 2^31 elements", n);
+  if (n == 0) return OP_OK;
+  if (!in_dev || !out_dev) return fail(h, OP_ERR_INVALID, "op_debug_primitive: NULL buffer");
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  opl::launch_probe((hipStream_t)hip_stream, kind, mode, in_dev, n, out_dev);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
 int op_debug_capture_hidden(op_handle* h, float* hidden_dev) {
   if (!h) return fail(nullptr, OP_ERR_INVALID, "op_debug_capture_hidden: NULL handle");
   h->capture = hidden_dev;

@@ -113,6 +113,11 @@ void launch_attn_probs_gather(hipStream_t st, const float* packed, const int32_t
 // grid: (64-query blocks of p.width, heads, the n_seqs sequences from p.s0 on); every element of their matrices is written
 void launch_attn_probs(hipStream_t st, const opk::AttnProbsParams& p, int n_seqs);
 
+// op_debug_primitive (opk_probe.hip.h; op_launch_probe.hip).  probe_group_size: the number of input elements one record of
+// `kind` (enum op_probe_kind) takes, 0 for an unknown kind.  launch_probe: kind, mode and n % group already checked, n > 0.
+int probe_group_size(int kind);
+void launch_probe(hipStream_t st, int kind, int mode, const void* in, size_t n, void* out);
+
 // The padded [B, L] boundary (opk_padded.hip.h; op_pack_padded / op_unpack_padded).  Integer types as enum op_int_dtype.
 constexpr int PAD_INT_I32 = 0, PAD_INT_I64 = 1, PAD_INT_U8 = 2;
 // row lengths + validation, scan and gather of one padded batch: cu[n_rows + 1], ids_packed[<= n_rows * width] and the

@@ -139,6 +139,10 @@ __device__ __forceinline__ f32x4 mfma16(bf16x8 x, bf16x8 y, f32x4 c) {
 __device__ __forceinline__ float rope_lo(float x1, float x2, float c, float s) { return __fmaf_rn(x1, c, -__fmul_rn(x2, s)); }
 __device__ __forceinline__ float rope_hi(float x1, float x2, float c, float s) { return __fmaf_rn(x2, c, __fmul_rn(x1, s)); }
 
+// keep-probability of a token from its two pruning logits: softmax(l0, l1)[1] = 1 / (1 + e^(l0 - l1)).  One spelling for
+// the pruning head of every path (and tests/test_gpu_primitives.py, which holds it to 8 x 2^-24 over the whole range).
+__device__ __forceinline__ float keep_prob_of(float l0, float l1) { return 1.0f / (1.0f + expf(l0 - l1)); }
+
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -507,8 +511,12 @@ __device__ __forceinline__ float4 load_stream_f4(const float* src) {
 // with he(a) = 2^q(a), q a degree-5 polynomial (weighted minimax fit of log2 he on [0, 10], weight a he(a); leading
 // coefficient negative, so q -> -inf and he -> 0 for large |x|).  Eight instructions: five FMAs, one v_exp_f32, one
 // FMA, one med3 -- the VALU work next to the MFMAs is what these epilogues cost, instruction for instruction.  No
-// cancellation on either side of zero.  Max |gelu - exact| = 6.4e-7 over [-12, 12] evaluated in fp32 (offline, against
-// fp64 erf); the library erff costs ~3x the instructions.
+// cancellation on either side of zero.  Max |gelu - exact| = 6.4e-7 (near x = 4; 6.39e-7 over a 4 M-point grid of
+// [-12, 12], 6.13e-7 over every fp16 value, in an fp32 emulation with a correctly rounded exp2), held on the device by
+// tests/test_gpu_primitives.py: against fp64 erfc over that sweep and out to +-3e38, within 1.25 x the emulation's
+// maximum and below 1e-6; gelu(x) == x bit for bit from x = 13 on, zero from -13 down, non-finite in -> non-finite out, and
+// this form bit-identical to the staged one (the measured device maxima: DESIGN.md section 2).  The library erff costs
+// ~3x the instructions.
 // The evaluation in stages (the one-wave-per-SIMD layer kernel runs stage k of ALL values of a chunk in one step of
 // its MFMA stream: a vector instruction that depends on the previous one costs the wave 8 issue cycles, an independent
 // one 4.5 -- microbench/mfma_loop.hip): q after stage 0..4, he after 5, gelu after 6.

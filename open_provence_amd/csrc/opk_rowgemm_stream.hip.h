@@ -277,7 +277,7 @@ __device__ __forceinline__ void rowgemm_final_head(const RowGemmParams& p, const
       l1 += b1;
       p.fin_prune[(size_t)tok * 2 + 0] = l0;
       p.fin_prune[(size_t)tok * 2 + 1] = l1;
-      if (p.fin_keep) p.fin_keep[tok] = 1.0f / (1.0f + expf(l0 - l1));
+      if (p.fin_keep) p.fin_keep[tok] = keep_prob_of(l0, l1);
     }
   }
 }

@@ -269,7 +269,7 @@ __global__ __launch_bounds__(256) void final_ln_prune_kernel(float* __restrict__
     const float l0 = d0 + pb[0] + poison, l1 = d1 + pb[1] + poison;
     prune_out[(size_t)tok * 2 + 0] = l0;
     prune_out[(size_t)tok * 2 + 1] = l1;
-    if (keep_prob) keep_prob[tok] = 1.0f / (1.0f + expf(l0 - l1));
+    if (keep_prob) keep_prob[tok] = keep_prob_of(l0, l1);
   }
   if (keep_all_rows) row_store_f32(rv, x + (size_t)row * H, H, lane);
   if (row_pos[row] == 0) row_store_f32(rv, cls + (size_t)row_seq[row] * H, H, lane);

@@ -551,6 +551,28 @@ class HipEncoder:
         _lib.check(self.lib, self._handle, int(code), "op_debug_rope_tables")
         return cos, sin
 
+    def debug_primitive(self, kind: "str | int", mode: int, inputs: torch.Tensor) -> torch.Tensor:
+        """Test hook (``op_debug_primitive``): the device functions of one ``_lib.PROBE_KINDS`` entry over ``inputs`` (a flat
+        CPU or device tensor of the kind's input dtype) under conversion mode ``mode`` (0 overflowing, 1 saturating);
+        returns the records on the CPU, ``[groups, outputs per group]`` in the kind's output dtype (words as int32)."""
+
+        if not hasattr(self.lib, "op_debug_primitive"):
+            raise _lib.HipLibraryError("this library has no op_debug_primitive")
+        if isinstance(kind, str):
+            number, in_dtype, group, out_dtype, out_per_group = _lib.PROBE_KINDS[kind]
+        else:
+            number, in_dtype, group, out_dtype, out_per_group = next(v for v in _lib.PROBE_KINDS.values() if v[0] == int(kind))
+        if inputs.dtype != getattr(torch, in_dtype) or inputs.ndim != 1:
+            raise TypeError(f"inputs must be a flat {in_dtype} tensor")
+        src = inputs.to(self.device).contiguous()
+        n = int(src.numel())
+        out = torch.empty(n // group, out_per_group, dtype=getattr(torch, out_dtype), device=self.device)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        code = self.lib.op_debug_primitive(self._handle, number, int(mode), ctypes.c_void_p(src.data_ptr() if n else 0), n,
+                                           ctypes.c_void_p(out.data_ptr() if out.numel() else 0), ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, int(code), "op_debug_primitive")
+        return out.cpu()
+
     def segment_means(self, values: torch.Tensor, segments: torch.Tensor) -> torch.Tensor:
         """``values[T]`` fp32 and ``segments[S, 2]`` int32 (token ranges ``[start, end)``) on this device ->
         ``[S]`` fp32: ``values[start:end].mean()`` in numpy's float32 pairwise order, bit for bit; 1.0 for an empty

@@ -34,6 +34,11 @@ What the kernels compute on purpose and the model restates (rather than a bound 
 
 Not modelled (below the 1e-6 floor of the comparison, or outside what a contraction sees): fp32 accumulation order,
 fp32 LayerNorm / GELU / RoPE / softmax exponent, the fp32 residual stream, fp16 subnormal flushing of p below 2^-24.
+The operand roundings above (:func:`rne`, :func:`e4m3`) and the fp32 GELU / exponent / RoPE / keep-probability are held to the
+device's element by element in tests/test_gpu_primitives.py.  Where the device departs from them, on inputs no forward reaches:
+under saturating conversions a finite value beyond bf16's range (|v| >= 0x7f7f8000) becomes +-max bf16 where :func:`rne` gives
+Inf; a weight whose fp32 product with 2^6 (its lo part: with 2^18) is infinite, |w| >= 2^122 (2^110), packs as NaN where
+:func:`e4m3` clamps to 448; NaN payloads are not compared.
 """
 
 from __future__ import annotations
