@@ -404,6 +404,74 @@ int op_pack_padded(op_handle* h, const void* ids_dev, int ids_dtype, const void*
 int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_seqlens_dev, int n_rows, int width, int channels,
                      float* padded_dev, void* hip_stream);
 
+/* Evaluation losses on the device.  Replaces: the losses the reference's inference file computes in its own forward when it
+ * is handed labels -- nn.BCEWithLogitsLoss / nn.CrossEntropyLoss on the ranking logits (standalone.py:1707-1722) and
+ * nn.CrossEntropyLoss over the pruning logits of the attention_mask == 1 positions (standalone.py:3870-3881) -- plus the
+ * ranking term of its training objective, nn.MSELoss (losses.py:56-57), so that a checkpoint can be validated by it.
+ * Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).  A side pass over logits that are already
+ * on the device: it touches none of the forward's kernels or its workspace.
+ *   kind               logits_dev                          labels_dev (labels_dtype)            term                    mean over
+ *   OP_LOSS_TOKEN_CE   prune_logits_dev [total_tokens][2]  [n_rows][width] int32 / int64        2-class cross entropy   tokens whose label != ignore_index
+ *                      as op_forward_packed leaves them    token t of row r reads
+ *                      (packed: no unpacking)              labels[r][t - cu[r]]
+ *   OP_LOSS_RANK_BCE   rank_logits_dev [n_rows][1]         [n_rows] fp32 (OP_LABELS_F32)        max(z,0) - z y          n_rows
+ *                                                                                               + log1p(exp(-|z|))
+ *   OP_LOSS_RANK_CE    rank_logits_dev [n_rows][C >= 2]    [n_rows] int32 / int64               C-class cross entropy   rows whose label != ignore_index
+ *   OP_LOSS_RANK_MSE   rank_logits_dev [n_rows][C]         [n_rows][C] fp32 (OP_LABELS_F32)     (z - y)^2               n_rows * C
+ * channels = 2 / 1 / C / C; width, total_tokens and cu_seqlens_dev [n_rows + 1] belong to the token kind and are ignored
+ * by the others.  Labels under padding (column >= the row's length) are never read.
+ * Arithmetic: every term in fp64 from the fp32 inputs in its stable form -- softplus(z_other - z_label) =
+ * max(d, 0) + log1p(exp(-|d|)) for two classes, log-sum-exp after subtracting the maximum for C (the maximum's own term is
+ * the 1 of a log1p, which for C = 2 is the same softplus) -- so logits of magnitude 1e4 lose nothing and a loss of 1e-35 keeps
+ * its digits.  The sum is fp64 in a FIXED order (per-block partials in a tree, then a single-block launch that adds
+ * them in index order, divides once and rounds once to fp32; no floating-point atomics): the same inputs give the same bits
+ * on every call and on every stream, and the result is within 1 fp32 ulp of the exact mean.  A count of zero (n_rows == 0,
+ * every label ignored) gives 0.0 / 0 = NaN, as torch does; n_rows == 0 launches the finishing step only.
+ *   loss_dev   one fp32, always written
+ *   terms_dev  NULL, or fp32 [total_tokens] (token kind) / [n_rows] / [n_rows][C]: every element is written (the caller
+ *              zeroes nothing), the fp64 term rounded once; exactly +0.0 where the label is ignored
+ * A label outside 0 <= y < C that is not ignore_index is never used as an index and contributes nothing; the first one in
+ * row-major order is reported (status bit 0; bad_row, bad_col, bad_value; bad_col is 0 for OP_LOSS_RANK_CE) and makes the
+ * loss NaN.
+ *   report == NULL  fully asynchronous on hip_stream, nothing is read back (capturable).
+ *   report != NULL  struct_bytes set by the caller; the result block is copied back and hip_stream is SYNCHRONISED ONCE.  A
+ *                   stream that is being captured is refused (OP_ERR_STATE), as in op_pack_padded.  A label out of range
+ *                   returns OP_ERR_INVALID with the report filled and an op_last_error text that names row, column and value.
+ * The 5 KB scratch block of the partials belongs to the handle whatever the batch size (the grid is capped, blocks stride
+ * over the rows): like every call on a handle, serialised by the caller.  Refused with OP_ERR_INVALID before anything is
+ * enqueued (and before the handle is looked at): a NULL request, a wrong struct_bytes (request or report), an unknown kind
+ * or labels_dtype, a labels_dtype that does not fit the kind, a negative size, channels != 2 (token kind) / != 1 (BCE) / < 2
+ * (rank CE), total_tokens beyond n_rows * width, n_rows * width or n_rows * channels >= 2^31, a NULL loss_dev, a NULL
+ * buffer of a non-empty batch. */
+enum op_loss_kind { OP_LOSS_TOKEN_CE = 0, OP_LOSS_RANK_BCE = 1, OP_LOSS_RANK_CE = 2, OP_LOSS_RANK_MSE = 3 };
+enum op_labels_dtype { OP_LABELS_F32 = 3 }; /* beside OP_INT_I32 / OP_INT_I64 of enum op_int_dtype */
+typedef struct op_loss_request {
+  uint32_t struct_bytes; /* sizeof(op_loss_request) */
+  int32_t kind;          /* enum op_loss_kind */
+  const float* logits_dev;
+  const void* labels_dev;
+  int32_t labels_dtype; /* OP_INT_I32 / OP_INT_I64 (the two CE kinds) or OP_LABELS_F32 (BCE, MSE) */
+  int32_t n_rows;
+  int32_t width;        /* token kind: columns of labels_dev */
+  int32_t channels;     /* logits per token / row */
+  int32_t total_tokens; /* token kind: rows of logits_dev */
+  int32_t reserved;
+  const int32_t* cu_seqlens_dev; /* token kind: [n_rows + 1] */
+  int64_t ignore_index;          /* callers pass -100 */
+  float* terms_dev;              /* nullable */
+} op_loss_request;
+typedef struct op_loss_report {
+  uint32_t struct_bytes; /* sizeof(op_loss_report) */
+  int32_t status;        /* bit 0: a label out of range */
+  int32_t bad_row, bad_col; /* the first one in row-major order; -1 when clear */
+  int64_t bad_value;
+  int64_t count; /* terms that entered the mean */
+  double sum;    /* their fp64 sum */
+  float loss;    /* = *loss_dev */
+  int32_t reserved;
+} op_loss_report;
+int op_loss(op_handle* h, const op_loss_request* req, float* loss_dev, op_loss_report* report, void* hip_stream);
+
 /* The running audit of a calibrated kernel set (HipEncoder's audit policy "running").  Replaces: nothing
  * in the reference, which picks its dtype once at load (standalone.py:1631-1642) and never looks again.  Additive to ABI 10
  * (op_abi_version() is unchanged: detect the five calls by symbol).  The handle owns a bitmap of vocab_size bits -- the token

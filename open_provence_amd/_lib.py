@@ -65,6 +65,7 @@ EXPORTED_SYMBOLS = (
     "op_attention_probs",
     "op_pack_padded",
     "op_unpack_padded",
+    "op_loss",
     "op_coverage_scan",
     "op_coverage_commit",
     "op_coverage_reset",
@@ -180,6 +181,49 @@ class OpPaddedReport(ctypes.Structure):
 
 OP_INT_I32, OP_INT_I64, OP_INT_U8 = 0, 1, 2
 OP_PADDED_BAD_MASK, OP_PADDED_BAD_ID = 1, 2  # op_padded_report.status bits
+
+
+class OpLossRequest(ctypes.Structure):
+    """``op_loss_request``: the logits, labels and kind of one ``op_loss`` call."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("kind", ctypes.c_int32),
+        ("logits_dev", ctypes.c_void_p),
+        ("labels_dev", ctypes.c_void_p),
+        ("labels_dtype", ctypes.c_int32),
+        ("n_rows", ctypes.c_int32),
+        ("width", ctypes.c_int32),
+        ("channels", ctypes.c_int32),
+        ("total_tokens", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("cu_seqlens_dev", ctypes.c_void_p),
+        ("ignore_index", ctypes.c_int64),
+        ("terms_dev", ctypes.c_void_p),
+    ]
+
+
+class OpLossReport(ctypes.Structure):
+    """``op_loss_report``: what ``op_loss`` read back -- the first label out of range, the count, the fp64 sum, the loss."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("status", ctypes.c_int32),
+        ("bad_row", ctypes.c_int32),
+        ("bad_col", ctypes.c_int32),
+        ("bad_value", ctypes.c_int64),
+        ("count", ctypes.c_int64),
+        ("sum", ctypes.c_double),
+        ("loss", ctypes.c_float),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
+# enum op_loss_kind, by the names HipEncoder.loss takes
+LOSS_KINDS = {"token_ce": 0, "rank_bce": 1, "rank_ce": 2, "rank_mse": 3}
+OP_LOSS_TOKEN_CE, OP_LOSS_RANK_BCE, OP_LOSS_RANK_CE, OP_LOSS_RANK_MSE = 0, 1, 2, 3
+OP_LABELS_F32 = 3  # op_loss_request.labels_dtype beside OP_INT_I32 / OP_INT_I64
+OP_LOSS_BAD_LABEL = 1  # op_loss_report.status bit
 
 
 class OpCoverageReport(ctypes.Structure):
@@ -299,6 +343,9 @@ def load_library() -> ctypes.CDLL:
         lib.op_pack_padded.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, ctypes.POINTER(OpPaddedReport), vp]
         lib.op_unpack_padded.restype = ci
         lib.op_unpack_padded.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
+    if hasattr(lib, "op_loss"):  # (additive to ABI 10)
+        lib.op_loss.restype = ci
+        lib.op_loss.argtypes = [vp, ctypes.POINTER(OpLossRequest), vp, ctypes.POINTER(OpLossReport), vp]
     if hasattr(lib, "op_coverage_scan"):  # (the running audit's five calls, additive to ABI 10 like the two above)
         lib.op_coverage_scan.restype = ci
         lib.op_coverage_scan.argtypes = [vp, vp, vp, ci, ci, vp, ctypes.POINTER(OpCoverageReport), vp]

@@ -29,10 +29,11 @@ _INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_f32.hip.h", CSRC / "o
 
 _PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
 _AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
+_LOSS = CSRC / "opk_loss.hip.h"  # the evaluation losses: fp64 terms, fixed-order reduction
 
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
-    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_sets.h", CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, INCLUDE]),
+    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_sets.h", CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, INCLUDE]),
     ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"], _INTERNAL),
     ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"], _INTERNAL),
     ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"], _INTERNAL),
@@ -48,6 +49,7 @@ UNITS = [
     ("op_launch_f32", CSRC / "op_launch_f32.hip", [], _INTERNAL),
     ("op_launch_attn_probs", CSRC / "op_launch_attn_probs.hip", [], _INTERNAL),
     ("op_launch_probe", CSRC / "op_launch_probe.hip", [], _INTERNAL + [CSRC / "opk_probe.hip.h"]),
+    ("op_launch_loss", CSRC / "op_launch_loss.hip", [], [_LOSS]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = sorted({h for u in UNITS for h in u[3]})

@@ -18,6 +18,7 @@
 #include "op_internal.h"
 #include "op_sets.h"
 #include "opk_small.hip.h"
+#include "opk_loss.hip.h"
 #include "opk_padded.hip.h"
 #include "opk_tiled.hip.h"
 
@@ -119,6 +120,8 @@ struct op_handle {
   uint32_t* pad_status = nullptr;    // op_pack_padded: the device status block (opk::PAD_ST_WORDS words), allocated on first use
   int32_t* pad_host = nullptr;       // ... and its pinned host staging: cu_seqlens[n_rows + 1] + the status block
   size_t pad_host_words = 0;
+  opk::LossScratch* loss_scratch = nullptr;  // op_loss: the per-block partials and the result block
+  opk::LossResult* loss_host = nullptr;      // ... and the result's pinned host staging, allocated by the first call with a report
   // the running audit's coverage (op_coverage_scan / op_coverage_commit): a bitmap of vocab_size bits + opl::COV_WORDS state words
   uint32_t* cov_bits = nullptr;
   uint32_t* cov_state = nullptr;
@@ -1354,6 +1357,7 @@ int op_create(const op_config* cfg, op_handle** out) {
   }
   OP_CREATE_TRY(dev_alloc(h, &h->cov_bits, ((size_t)h->V + 31) / 32));
   OP_CREATE_TRY(dev_alloc(h, &h->cov_state, (size_t)opl::COV_WORDS));
+  OP_CREATE_TRY(dev_alloc(h, &h->loss_scratch, 1));  // (here, not on first use: op_loss without a report may be captured)
   for (int t = 0; t < 2; ++t) {
     std::vector<float> cs, sn;
     build_rope_host(t == 1 ? cfg->global_rope_theta : cfg->local_rope_theta, h->max_pos, cs, sn);
@@ -1376,6 +1380,7 @@ void op_destroy(op_handle* h) {
   for (void* p : h->allocations) (void)hipFree(p);
   if (h->pad_host) (void)hipHostFree(h->pad_host);
   if (h->cov_host) (void)hipHostFree(h->cov_host);
+  if (h->loss_host) (void)hipHostFree(h->loss_host);
   delete h;
 }
 
@@ -2409,6 +2414,95 @@ int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_se
     return fail(h, OP_ERR_UNSUPPORTED, "op_unpack_padded: no kernel for %d channels", channels);
   OP_HIP(h, hipGetLastError());
   return OP_OK;
+}
+
+int op_loss(op_handle* h, const op_loss_request* req, float* loss_dev, op_loss_report* report, void* hip_stream) {
+  // (the arguments' own fields first: none of them needs the handle)
+  if (!req) return fail(h, OP_ERR_INVALID, "op_loss: request is NULL");
+  if (req->struct_bytes != sizeof(op_loss_request))
+    return fail(h, OP_ERR_INVALID, "op_loss: op_loss_request.struct_bytes is %u, expected %zu", req->struct_bytes, sizeof(op_loss_request));
+  if (report && report->struct_bytes != sizeof(op_loss_report))
+    return fail(h, OP_ERR_INVALID, "op_loss: op_loss_report.struct_bytes is %u, expected %zu", report->struct_bytes, sizeof(op_loss_report));
+  const int kind = req->kind, dtype = req->labels_dtype;
+  if (kind < OP_LOSS_TOKEN_CE || kind > OP_LOSS_RANK_MSE) return fail(h, OP_ERR_INVALID, "op_loss: unknown kind %d", kind);
+  if (dtype != OP_INT_I32 && dtype != OP_INT_I64 && dtype != OP_INT_U8 && dtype != OP_LABELS_F32)
+    return fail(h, OP_ERR_INVALID, "op_loss: unknown labels_dtype %d", dtype);
+  const bool token = kind == OP_LOSS_TOKEN_CE, integer = token || kind == OP_LOSS_RANK_CE;
+  if (integer ? (dtype != OP_INT_I32 && dtype != OP_INT_I64) : dtype != OP_LABELS_F32)
+    return fail(h, OP_ERR_INVALID, "op_loss: labels_dtype %d does not fit kind %d (%s)", dtype, kind,
+                integer ? "OP_INT_I32 or OP_INT_I64" : "OP_LABELS_F32");
+  if (req->n_rows < 0) return fail(h, OP_ERR_INVALID, "op_loss: negative n_rows %d", req->n_rows);
+  if (req->channels < 0) return fail(h, OP_ERR_INVALID, "op_loss: negative channels %d", req->channels);
+  if (token && req->width < 0) return fail(h, OP_ERR_INVALID, "op_loss: negative width %d", req->width);
+  if (token && req->total_tokens < 0) return fail(h, OP_ERR_INVALID, "op_loss: negative total_tokens %d", req->total_tokens);
+  if (token && req->channels != 2) return fail(h, OP_ERR_INVALID, "op_loss: channels is %d, OP_LOSS_TOKEN_CE takes 2", req->channels);
+  if (kind == OP_LOSS_RANK_BCE && req->channels != 1)
+    return fail(h, OP_ERR_INVALID, "op_loss: channels is %d, OP_LOSS_RANK_BCE takes 1", req->channels);
+  if (kind == OP_LOSS_RANK_CE && req->channels < 2)
+    return fail(h, OP_ERR_INVALID, "op_loss: channels is %d, OP_LOSS_RANK_CE takes at least 2", req->channels);
+  const int64_t label_cells = (int64_t)req->n_rows * (int64_t)(token ? req->width : kind == OP_LOSS_RANK_MSE ? req->channels : 1);
+  const int64_t logit_rows = token ? (int64_t)req->total_tokens : (int64_t)req->n_rows;
+  if (token && label_cells > (int64_t)INT32_MAX)  // (the first offender is a 32-bit linear index)
+    return fail(h, OP_ERR_INVALID, "op_loss: n_rows * width = %lld exceeds 2^31 - 1", (long long)label_cells);
+  if (!token && (int64_t)req->n_rows * (int64_t)req->channels > (int64_t)INT32_MAX)
+    return fail(h, OP_ERR_INVALID, "op_loss: n_rows * channels = %lld exceeds 2^31 - 1", (long long)req->n_rows * req->channels);
+  if (token && (int64_t)req->total_tokens > label_cells)
+    return fail(h, OP_ERR_INVALID, "op_loss: total_tokens %d exceeds n_rows * width = %lld", req->total_tokens, (long long)label_cells);
+  if (!loss_dev) return fail(h, OP_ERR_INVALID, "op_loss: loss_dev is NULL");
+  if (logit_rows * req->channels > 0 && !req->logits_dev) return fail(h, OP_ERR_INVALID, "op_loss: logits_dev is NULL");
+  if (label_cells > 0 && !req->labels_dev) return fail(h, OP_ERR_INVALID, "op_loss: labels_dev is NULL");
+  if (token && req->n_rows > 0 && !req->cu_seqlens_dev) return fail(h, OP_ERR_INVALID, "op_loss: cu_seqlens_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_loss: NULL handle");
+  if (report) {
+    report->status = 0;
+    report->bad_row = report->bad_col = -1;
+    report->bad_value = report->count = 0;
+    report->sum = 0.0;
+    report->loss = 0.0f;
+    report->reserved = 0;
+  }
+
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  if (report) {
+    hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+    OP_HIP(h, hipStreamIsCapturing(stream, &capturing));
+    if (capturing != hipStreamCaptureStatusNone)
+      return fail(h, OP_ERR_STATE, "op_loss: the stream is being captured (a call with a report synchronises it to read the result back)");
+    if (!h->loss_host) {
+      void* p = nullptr;
+      hipError_t e = hipHostMalloc(&p, sizeof(opk::LossResult), hipHostMallocDefault);
+      if (e != hipSuccess) return fail(h, OP_ERR_NOMEM, "hipHostMalloc(%zu bytes) failed: %s", sizeof(opk::LossResult), hipGetErrorString(e));
+      h->loss_host = reinterpret_cast<opk::LossResult*>(p);
+    }
+  }
+  opk::LossParams lp;
+  lp.logits = req->logits_dev;
+  lp.labels = req->labels_dev;
+  lp.cu = token ? req->cu_seqlens_dev : nullptr;
+  lp.terms = req->terms_dev;
+  lp.n_rows = req->n_rows;
+  lp.width = token ? req->width : 0;
+  lp.channels = req->channels;
+  lp.total_tokens = token ? req->total_tokens : 0;
+  lp.ignore_index = (long long)req->ignore_index;
+  if (!opl::launch_loss(stream, kind, dtype, lp, h->loss_scratch, loss_dev))
+    return fail(h, OP_ERR_UNSUPPORTED, "op_loss: no kernel for kind %d / labels_dtype %d", kind, dtype);
+  OP_HIP(h, hipGetLastError());
+  if (!report) return OP_OK;
+  OP_HIP(h, hipMemcpyAsync(h->loss_host, &h->loss_scratch->result, sizeof(opk::LossResult), hipMemcpyDeviceToHost, stream));
+  OP_HIP(h, hipStreamSynchronize(stream));  // the one synchronisation: the caller asked for the result on the host
+  const opk::LossResult& res = *h->loss_host;
+  report->count = (int64_t)res.count;
+  report->sum = res.sum;
+  report->loss = res.loss;
+  if (res.status == 0) return OP_OK;
+  report->status = 1;
+  report->bad_value = (int64_t)res.bad_value;
+  report->bad_row = token ? (int32_t)(res.bad_index / (uint32_t)req->width) : (int32_t)res.bad_index;
+  report->bad_col = token ? (int32_t)(res.bad_index % (uint32_t)req->width) : 0;
+  return fail(h, OP_ERR_INVALID, "op_loss: label %lld at row %d, column %d is outside 0 <= label < %d and is not ignore_index (%lld)",
+              (long long)report->bad_value, report->bad_row, report->bad_col, req->channels, (long long)req->ignore_index);
 }
 
 // The coverage belongs to one arithmetic: the kernel set (and the layer mask of sets 8 / 9) it was collected under.  It is

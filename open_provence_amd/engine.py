@@ -282,6 +282,7 @@ class HipEncoder:
         self.fallbacks = 0  # fp16 range-guard fallbacks: reported by process() (timing / performance_trace)
         self._f8_active: bool | None = None  # cache of f8_active(); None = ask the handle
         self._profiling = False
+        self.last_loss_report: dict | None = None  # op_loss_report of the last loss(check=True) call
 
     # -- lifecycle -------------------------------------------------------------------------------
     def close(self) -> None:
@@ -1133,6 +1134,95 @@ class HipEncoder:
             )
         _lib.check(self.lib, self._handle, code, "op_unpack_padded")
         return out
+
+    # -- the evaluation losses on the device (op_loss) -----------------------------------------------------------------
+    def loss(self, kind: str, logits: torch.Tensor, labels: torch.Tensor, *, cu: "torch.Tensor | None" = None,
+             width: "int | None" = None, ignore_index: int = -100, terms: bool = False, check: bool = True
+             ) -> "torch.Tensor | tuple[torch.Tensor, torch.Tensor]":
+        """The losses of the reference's inference file over logits that are already on this device (``op_loss``): a 0-dim fp32
+        device tensor, and with ``terms=True`` also the unreduced fp32 terms (+0.0 where the label is ``ignore_index``).
+
+        ``kind``: ``"token_ce"`` -- packed pruning ``logits[T, 2]`` as :meth:`forward_packed` leaves them, padded integer
+        ``labels[n_rows, width]`` and the batch's ``cu`` (int32 ``[n_rows + 1]``); the mean 2-class cross entropy over the
+        tokens whose label is not ``ignore_index`` (terms ``[T]``).  ``"rank_bce"`` -- ``logits[n_rows]`` or ``[n_rows, 1]``,
+        fp32 ``labels[n_rows]`` (terms ``[n_rows]``).  ``"rank_ce"`` -- ``logits[n_rows, C]``, integer ``labels[n_rows]``
+        (terms ``[n_rows]``).  ``"rank_mse"`` -- ``logits[n_rows, C]`` and fp32 ``labels`` of the same shape (terms too).
+        Terms are evaluated in fp64 and added in a fixed order: the same inputs give the same bits on every call.
+
+        ``check=True`` reads the call's report back (one synchronisation of the current stream) and raises ``IndexError`` for
+        a label outside ``0 <= y < C`` that is not ``ignore_index``, naming its row, column and value, as torch does on the
+        CPU.  ``check=False`` is asynchronous; such a label then makes the loss NaN."""
+
+        if kind not in _lib.LOSS_KINDS:
+            raise ValueError(f"unknown loss kind {kind!r}: one of {sorted(_lib.LOSS_KINDS)}")
+        if logits.dtype != torch.float32:
+            raise TypeError(f"logits must be fp32, got {logits.dtype}")
+        if logits.device != self.device or labels.device != self.device or (cu is not None and cu.device != self.device):
+            raise ValueError(f"logits / labels / cu must live on {self.device}")
+        integer = kind in ("token_ce", "rank_ce")
+        labels = labels.detach()
+        if integer:
+            if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+                raise TypeError(f"{kind} labels must be an integer tensor, got {labels.dtype}")
+            if labels.dtype not in (torch.int32, torch.int64):
+                labels = labels.to(torch.int64)
+        elif labels.dtype != torch.float32:
+            raise TypeError(f"{kind} labels must be fp32, got {labels.dtype}")
+        logits, labels = logits.detach().contiguous(), labels.contiguous()
+        total = 0
+        if kind == "token_ce":
+            if logits.ndim != 2 or logits.shape[1] != 2:
+                raise ValueError("token_ce logits must be packed [T, 2]")
+            if labels.ndim != 2 or (width is not None and int(width) != labels.shape[1]):
+                raise ValueError("token_ce labels must be [n_rows, width]")
+            n_rows, width, channels, total = int(labels.shape[0]), int(labels.shape[1]), 2, int(logits.shape[0])
+            if cu is None or cu.dtype != torch.int32 or cu.ndim != 1 or int(cu.numel()) != n_rows + 1 or not cu.is_contiguous():
+                raise ValueError("token_ce needs cu: contiguous int32 [n_rows + 1]")
+            if total > n_rows * width:
+                raise ValueError(f"{total} packed tokens do not fit labels of shape {tuple(labels.shape)}")
+            terms_shape: tuple = (total,)
+        else:
+            if kind == "rank_bce" and logits.ndim == 1:
+                logits = logits.unsqueeze(1)
+            if logits.ndim != 2:
+                raise ValueError(f"{kind} logits must be [n_rows, C]")
+            n_rows, channels, width = int(logits.shape[0]), int(logits.shape[1]), 0
+            if kind == "rank_bce" and channels != 1:
+                raise ValueError("rank_bce takes one logit per row")
+            if kind == "rank_ce" and channels < 2:
+                raise ValueError("rank_ce takes at least two logits per row")
+            want = (n_rows, channels) if kind == "rank_mse" else (n_rows,)
+            if tuple(labels.shape) != want:
+                raise ValueError(f"{kind} labels must have shape {want}, got {tuple(labels.shape)}")
+            terms_shape = want
+        if n_rows * max(width, channels) >= 2**31:
+            raise ValueError("batch has more than 2^31 positions")
+        out = torch.empty((), dtype=torch.float32, device=self.device)
+        terms_out = torch.empty(terms_shape, dtype=torch.float32, device=self.device) if terms else None
+        ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None and t.numel() else None  # noqa: E731
+        req = _lib.OpLossRequest()
+        req.struct_bytes = ctypes.sizeof(_lib.OpLossRequest)
+        req.kind = _lib.LOSS_KINDS[kind]
+        req.logits_dev, req.labels_dev, req.cu_seqlens_dev, req.terms_dev = ptr(logits), ptr(labels), ptr(cu), ptr(terms_out)
+        req.labels_dtype = {torch.int32: _lib.OP_INT_I32, torch.int64: _lib.OP_INT_I64, torch.float32: _lib.OP_LABELS_F32}[labels.dtype]
+        req.n_rows, req.width, req.channels, req.total_tokens = n_rows, width, channels, total
+        req.ignore_index = int(ignore_index)
+        report = None
+        if check:
+            report = _lib.OpLossReport()
+            report.struct_bytes = ctypes.sizeof(_lib.OpLossReport)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_loss(self._handle, ctypes.byref(req), ctypes.c_void_p(out.data_ptr()),
+                                    ctypes.byref(report) if report is not None else None, ctypes.c_void_p(stream))
+        # what the last checked call read back (None after an unchecked one): the count and fp64 sum behind the mean
+        self.last_loss_report = ({name: getattr(report, name) for name in ("status", "bad_row", "bad_col", "bad_value", "count", "sum", "loss")}
+                                 if report is not None else None)
+        if report is not None and code == _lib.OP_ERR_INVALID and int(report.status) & _lib.OP_LOSS_BAD_LABEL:
+            raise IndexError(f"label {int(report.bad_value)} at row {int(report.bad_row)}, column {int(report.bad_col)} is out of "
+                             f"range for {channels} classes (ignore_index is {int(ignore_index)})")
+        _lib.check(self.lib, self._handle, code, "op_loss")
+        return (out, terms_out) if terms else out
 
     def forward_rows(self, rows: Sequence[Sequence[int]]) -> tuple[torch.Tensor, torch.Tensor, np.ndarray]:
         """Convenience: host id rows -> one H2D copy -> forward.  Returns (prune[T,2], rank[B,nl], cu_host)."""

@@ -587,12 +587,50 @@ class OpenProvenceModel:
         is a tuple of num_layers fp32 tensors ``[B, heads, L, L]`` as the reference returns them under eager attention
         (standalone.py:1689, 1727) -- except that padded QUERY rows are zeros here, where the reference holds a softmax row.
         A side pass over the hidden states (``op_attention_probs``): logits and hidden states are bit-identical to those of
-        the same call without the flag.  Memory: ``num_layers x B x heads x L^2 x 4`` bytes."""
+        the same call without the flag.  Memory: ``num_layers x B x heads x L^2 x 4`` bytes.
+
+        ``labels``: ``loss`` is the reference's evaluation loss of the ranking head (standalone.py:1707-1722) as a 0-dim fp32
+        device tensor -- ``BCEWithLogitsLoss`` on ``labels.float()`` when ``num_labels == 1``, otherwise ``CrossEntropyLoss``
+        on integer ``labels.view(-1)`` -- computed by ``op_loss`` over the ranking logits the forward left on the device (fp64
+        terms, fixed-order sum: within 1 fp32 ulp of the exact mean).  ``labels`` holds one entry per row (``ValueError``
+        otherwise) on the CPU or on the device; a class outside ``0 <= y < num_labels`` that is not -100 raises ``IndexError``.
+        Every other output is bit-identical to the same call without labels; ``return_dict=False`` then returns
+        ``(loss, ranking_logits, pruning_logits)``."""
 
         if input_ids is None:
             raise ValueError("input_ids must be provided")
-        if labels is not None:
-            raise NotImplementedError("training losses are outside the MI355X inference path")
+        rank_labels = self._ranking_labels(labels, int(input_ids.shape[0])) if labels is not None else None
+        rank, pruning_logits, hidden_states, attentions, _ = self._forward_padded(input_ids, attention_mask, output_hidden_states,
+                                                                                  output_attentions)
+        loss = None
+        if rank_labels is not None:
+            loss = self.encoder.loss("rank_bce" if rank.shape[1] == 1 else "rank_ce", rank, rank_labels)
+        if return_dict is not None and not return_dict:
+            return (rank, pruning_logits) if loss is None else (loss, rank, pruning_logits)
+        return OpenProvenceOutput(
+            loss=loss, logits=rank, ranking_logits=rank, pruning_logits=pruning_logits, hidden_states=hidden_states,
+            attentions=attentions,
+        )
+
+    def _ranking_labels(self, labels: torch.Tensor, n_rows: int) -> torch.Tensor:
+        """``labels`` as the ranking loss reads them (standalone.py:1711, 1715), on the model's device: ``[B]`` fp32 for one
+        label, ``[B]`` integer classes otherwise."""
+
+        labels = torch.as_tensor(labels)
+        if labels.numel() != n_rows:
+            raise ValueError(f"labels must hold one entry per row: {labels.numel()} entries for {n_rows} rows")
+        labels = labels.detach().reshape(-1).to(self._runtime_device)
+        if int(self.dims.num_labels) == 1:
+            return labels.float()
+        if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+            raise TypeError(f"class labels must be an integer tensor, got {labels.dtype}")
+        return labels
+
+    def _forward_padded(self, input_ids, attention_mask, output_hidden_states, output_attentions):
+        """The forward of a padded batch without its losses: ``(ranking_logits, pruning_logits, hidden_states, attentions,
+        packed)``; ``packed`` = the pruning logits as the kernels left them, ``[T, 2]`` on the device, with the batch's
+        ``cu_seqlens`` on the device and the token count -- what the token-classification loss reads."""
+
         if output_attentions and not self.encoder.attention_outputs:
             raise ValueError("output_attentions=True needs the fp32 weight packs: create the model with attention_outputs=True")
         dev = self._runtime_device
@@ -628,12 +666,7 @@ class OpenProvenceModel:
             pruning_logits = self.encoder.unpack_padded_device(prune, cu, int(input_ids.shape[0]), width)
         else:
             pruning_logits = unpack_to_padded(prune, cu_np, width)
-        if return_dict is not None and not return_dict:
-            return (rank, pruning_logits)
-        return OpenProvenceOutput(
-            loss=None, logits=rank, ranking_logits=rank, pruning_logits=pruning_logits, hidden_states=hidden_states,
-            attentions=attentions,
-        )
+        return rank, pruning_logits, hidden_states, attentions, (prune, cu, int(cu_np[-1]))
 
     def __call__(self, *args: Any, **kwargs: Any):
         return self.forward(*args, **kwargs)
@@ -2270,17 +2303,41 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
 
     def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, output_hidden_states=None,
                 output_attentions=None, **kwargs: Any):
-        base = OpenProvenceModel.forward(self, input_ids=input_ids, attention_mask=attention_mask, labels=labels, return_dict=True,
-                                         output_hidden_states=output_hidden_states, output_attentions=output_attentions)
+        """The base forward without labels, as the reference runs it (standalone.py:3857-3863); with ``labels[B, L]`` (integer
+        classes 0 / 1, -100 = ignored; CPU or device) ``loss`` is its ``CrossEntropyLoss`` over the pruning logits of the
+        active positions (standalone.py:3870-3881) as a 0-dim fp32 device tensor.  ``op_loss`` reads the PACKED logits the
+        forward left on the device with the forward's own ``cu_seqlens``: the active positions are the packed ones -- the
+        ``attention_mask`` tokens, or every position without a mask.  A mask without any active position gives exactly 0.0
+        (:3878-3879); active positions that are all -100 give NaN, as torch does.  ``return_dict=False`` returns
+        ``(loss, pruning_logits)`` with labels, ``(pruning_logits,)`` without."""
+
+        if input_ids is None:
+            raise ValueError("input_ids must be provided")
+        token_labels = None
+        if labels is not None:
+            token_labels = torch.as_tensor(labels)
+            if token_labels.dtype.is_floating_point or token_labels.dtype.is_complex or token_labels.dtype == torch.bool:
+                raise TypeError(f"token labels must be an integer tensor, got {token_labels.dtype}")
+            if tuple(token_labels.shape) != tuple(input_ids.shape):
+                raise ValueError(f"labels must have the shape of input_ids {tuple(input_ids.shape)}, got {tuple(token_labels.shape)}")
+            token_labels = token_labels.detach().to(self._runtime_device)
+        rank, pruning_logits, hidden_states, attentions, (prune, cu, total) = self._forward_padded(
+            input_ids, attention_mask, output_hidden_states, output_attentions)
+        loss = None
+        if token_labels is not None:
+            if attention_mask is not None and total == 0:
+                loss = torch.zeros((), dtype=torch.float32, device=pruning_logits.device)
+            else:
+                loss = self.encoder.loss("token_ce", prune, token_labels, cu=cu)
         if return_dict is not None and not return_dict:
-            return (base["pruning_logits"],)
+            return (pruning_logits,) if loss is None else (loss, pruning_logits)
         return OpenProvenceOutput(
-            loss=None,
-            logits=base["pruning_logits"],
-            pruning_logits=base["pruning_logits"],
-            ranking_logits=base["ranking_logits"],
-            hidden_states=base["hidden_states"],
-            attentions=base["attentions"],
+            loss=loss,
+            logits=pruning_logits,
+            pruning_logits=pruning_logits,
+            ranking_logits=rank,
+            hidden_states=hidden_states,
+            attentions=attentions,
         )
 
 
