@@ -528,6 +528,59 @@ int op_audit_compare(op_handle* h, const float* prune_dev, const float* rank_dev
 int op_segment_means(op_handle* h, const float* keep_prob_dev, int n_values, const int32_t* seg_dev, int n_seg,
                      float* out_dev, void* hip_stream);
 
+/* Replaces: the host loop that concatenates `[CLS] query [SEP] context [SEP]` rows block by block (standalone.py:2104-2196)
+ * for a PREPARED corpus (OpenProvenceModel.prepare_contexts): the fragments' token ids live on the device, a request brings
+ * its queries' ids and a plan of rows, and the packed input of op_forward_packed is laid out there.  Additive to ABI 10
+ * (op_abi_version() is unchanged: detect the call by symbol).
+ *   corpus_dev   [frag_off[n_frag]] int32   the fragments' ids end to end; frag_off_dev / frag_off_host [n_frag + 1] their
+ *                                           offsets (non-decreasing from 0; the total stays below 2^31)
+ *   query_ids_dev [q_off[n_queries]] int32  the request's queries end to end; q_off_dev / q_off_host [n_queries + 1]
+ *   prefix, middle, suffix                  HOST arrays of n_prefix / n_middle / n_suffix ids, at most OP_ASSEMBLE_MAX_PIECE
+ *                                           each: the specials layout as a template (for BERT: [CLS], [SEP], [SEP])
+ *   plan_dev / plan_host [n_rows][4] int32  per row {query, first_frag, n_frag, clip}: the row is
+ *                                           prefix + query + middle + context + suffix, where context = the fragments
+ *                                           first_frag .. first_frag + n_frag - 1 of the corpus (consecutive, so one
+ *                                           contiguous copy), or with clip > 0 only the first `clip` ids of fragment
+ *                                           first_frag followed by the others whole (two copies).  n_frag = 0: no
+ *                                           context, clip = 0; or clip = -1: no context AND no suffix, the row is
+ *                                           prefix + query + middle (what tokenizers build for an empty second sequence)
+ *   cu_seqlens_dev / cu_seqlens_host [n_rows + 1]  the rows' offsets in ids_dev, from 0 to total_tokens: known on the host
+ *                                           from lengths alone, so nothing is read back
+ *   ids_dev [total_tokens] int32            the output; nothing outside [0, total_tokens) is written, and every element
+ *                                           of it is written when the host and device copies agree
+ * The *_host arrays are the caller's host copies of the *_dev ones; the call checks the request on them and the kernel
+ * reads the device copies, holding every index it finds there inside the buffers all the same.  Asynchronous on hip_stream;
+ * the handle's state is neither read nor changed beyond its device and error text.  OP_ERR_INVALID, before anything is
+ * enqueued: a NULL request or handle, a wrong struct_bytes, a negative count, a template piece longer than
+ * OP_ASSEMBLE_MAX_PIECE (or NULL with a positive count), a NULL buffer while n_rows > 0, a row whose query or fragments lie
+ * outside the request / the corpus or whose clip exceeds its first fragment (or is positive without one), offsets that decrease,
+ * and cu_seqlens_host not equal to the prefix sums of the plan's row lengths from 0 to total_tokens.  n_rows == 0 with
+ * total_tokens == 0 enqueues nothing.  Kernel: a wave per row segment, 16-byte stores where alignment allows, vector
+ * stores only, no atomics (csrc/opk_assemble.hip.h). */
+#define OP_ASSEMBLE_MAX_PIECE 8
+typedef struct op_assemble_request {
+  uint32_t struct_bytes; /* sizeof(op_assemble_request) */
+  int32_t n_frag;
+  int32_t n_queries;
+  int32_t n_rows;
+  int32_t total_tokens;
+  int32_t n_prefix, n_middle, n_suffix;
+  const int32_t* prefix; /* host */
+  const int32_t* middle; /* host */
+  const int32_t* suffix; /* host */
+  const int32_t* corpus_dev;
+  const int32_t* frag_off_dev;
+  const int32_t* frag_off_host;
+  const int32_t* query_ids_dev;
+  const int32_t* q_off_dev;
+  const int32_t* q_off_host;
+  const int32_t* plan_dev;
+  const int32_t* plan_host;
+  const int32_t* cu_seqlens_dev;
+  const int32_t* cu_seqlens_host;
+} op_assemble_request;
+int op_assemble_rows(op_handle* h, const op_assemble_request* req, int32_t* ids_dev, void* hip_stream);
+
 /* Test hook.  Replaces: output_hidden_states=True of the reference forward (standalone.py:1689,
  * 1727).  When `hidden_dev` is non-NULL the next forwards also write the (num_layers+1) hidden
  * states, fp32 [num_layers+1, total_tokens, hidden]; entry num_layers is the post-final_norm

@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = (
     "op_gather_rows",
     "op_audit_compare",
     "op_segment_means",
+    "op_assemble_rows",
     "op_debug_workspace_layout",
     "op_debug_rope_tables",
     "op_debug_primitive",
@@ -238,6 +239,37 @@ class OpCoverageReport(ctypes.Structure):
     ]
 
 
+class OpAssembleRequest(ctypes.Structure):
+    """``op_assemble_request``: the resident corpus, a request's queries, the row template and the plan of one ``op_assemble_rows`` call."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("n_frag", ctypes.c_int32),
+        ("n_queries", ctypes.c_int32),
+        ("n_rows", ctypes.c_int32),
+        ("total_tokens", ctypes.c_int32),
+        ("n_prefix", ctypes.c_int32),
+        ("n_middle", ctypes.c_int32),
+        ("n_suffix", ctypes.c_int32),
+        ("prefix", ctypes.c_void_p),
+        ("middle", ctypes.c_void_p),
+        ("suffix", ctypes.c_void_p),
+        ("corpus_dev", ctypes.c_void_p),
+        ("frag_off_dev", ctypes.c_void_p),
+        ("frag_off_host", ctypes.c_void_p),
+        ("query_ids_dev", ctypes.c_void_p),
+        ("q_off_dev", ctypes.c_void_p),
+        ("q_off_host", ctypes.c_void_p),
+        ("plan_dev", ctypes.c_void_p),
+        ("plan_host", ctypes.c_void_p),
+        ("cu_seqlens_dev", ctypes.c_void_p),
+        ("cu_seqlens_host", ctypes.c_void_p),
+    ]
+
+
+OP_ASSEMBLE_MAX_PIECE = 8
+
+
 class OpWorkspaceRegion(ctypes.Structure):
     """``op_workspace_region``: one region of the forward's workspace (``op_debug_workspace_layout``)."""
 
@@ -366,6 +398,9 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "op_debug_primitive"):  # (test hook, additive to ABI 10)
         lib.op_debug_primitive.restype = ci
         lib.op_debug_primitive.argtypes = [vp, ci, ci, vp, cs, vp, vp]
+    if hasattr(lib, "op_assemble_rows"):  # (prepared contexts, additive to ABI 10)
+        lib.op_assemble_rows.restype = ci
+        lib.op_assemble_rows.argtypes = [vp, ctypes.POINTER(OpAssembleRequest), vp, vp]
     lib.op_segment_means.restype = ci
     lib.op_segment_means.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     lib.op_debug_capture_hidden.restype = ci

@@ -30,6 +30,7 @@ _INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_f32.hip.h", CSRC / "o
 _PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
 _AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
 _LOSS = CSRC / "opk_loss.hip.h"  # the evaluation losses: fp64 terms, fixed-order reduction
+_ASSEMBLE = CSRC / "opk_assemble.hip.h"  # prepared contexts: rows laid out on the device from a resident corpus
 
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
@@ -50,6 +51,7 @@ UNITS = [
     ("op_launch_attn_probs", CSRC / "op_launch_attn_probs.hip", [], _INTERNAL),
     ("op_launch_probe", CSRC / "op_launch_probe.hip", [], _INTERNAL + [CSRC / "opk_probe.hip.h"]),
     ("op_launch_loss", CSRC / "op_launch_loss.hip", [], [_LOSS]),
+    ("op_launch_assemble", CSRC / "op_launch_assemble.hip", [], _INTERNAL + [_ASSEMBLE]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = sorted({h for u in UNITS for h in u[3]})

@@ -2636,4 +2636,79 @@ int op_audit_compare(op_handle* h, const float* prune_dev, const float* rank_dev
   return OP_OK;
 }
 
+int op_assemble_rows(op_handle* h, const op_assemble_request* req, int32_t* ids_dev, void* hip_stream) {
+  // (the request's own fields first, on the host copies: nothing is enqueued before the last check)
+  if (!req) return fail(h, OP_ERR_INVALID, "op_assemble_rows: request is NULL");
+  if (req->struct_bytes != sizeof(op_assemble_request))
+    return fail(h, OP_ERR_INVALID, "op_assemble_rows: op_assemble_request.struct_bytes is %u, expected %zu", req->struct_bytes,
+                sizeof(op_assemble_request));
+  if (req->n_frag < 0 || req->n_queries < 0 || req->n_rows < 0 || req->total_tokens < 0)
+    return fail(h, OP_ERR_INVALID, "op_assemble_rows: negative count (n_frag %d, n_queries %d, n_rows %d, total_tokens %d)", req->n_frag,
+                req->n_queries, req->n_rows, req->total_tokens);
+  const int32_t* const pieces[3] = {req->prefix, req->middle, req->suffix};
+  const int n_pieces[3] = {req->n_prefix, req->n_middle, req->n_suffix};
+  static const char* const piece_names[3] = {"prefix", "middle", "suffix"};
+  for (int i = 0; i < 3; ++i) {
+    if (n_pieces[i] < 0 || n_pieces[i] > OP_ASSEMBLE_MAX_PIECE)
+      return fail(h, OP_ERR_INVALID, "op_assemble_rows: %s holds %d ids, expected 0 .. %d", piece_names[i], n_pieces[i], OP_ASSEMBLE_MAX_PIECE);
+    if (n_pieces[i] > 0 && !pieces[i]) return fail(h, OP_ERR_INVALID, "op_assemble_rows: %s is NULL", piece_names[i]);
+  }
+  if (req->n_rows == 0) {
+    if (req->total_tokens != 0) return fail(h, OP_ERR_INVALID, "op_assemble_rows: no rows but total_tokens is %d", req->total_tokens);
+    if (!h) return fail(nullptr, OP_ERR_INVALID, "op_assemble_rows: NULL handle");
+    return OP_OK;
+  }
+  if (!req->plan_dev || !req->plan_host || !req->cu_seqlens_dev || !req->cu_seqlens_host || !req->q_off_dev || !req->q_off_host ||
+      !req->frag_off_dev || !req->frag_off_host)
+    return fail(h, OP_ERR_INVALID, "op_assemble_rows: a plan, cu_seqlens or offset buffer is NULL");
+  if (req->q_off_host[0] != 0 || req->frag_off_host[0] != 0)
+    return fail(h, OP_ERR_INVALID, "op_assemble_rows: offsets do not start at 0");
+  for (int q = 0; q < req->n_queries; ++q)
+    if (req->q_off_host[q + 1] < req->q_off_host[q]) return fail(h, OP_ERR_INVALID, "op_assemble_rows: q_off decreases at query %d", q);
+  const int n_query_tokens = req->q_off_host[req->n_queries], n_corpus = req->frag_off_host[req->n_frag];
+  if (n_corpus < 0) return fail(h, OP_ERR_INVALID, "op_assemble_rows: frag_off ends at %d", n_corpus);
+  if (req->cu_seqlens_host[0] != 0) return fail(h, OP_ERR_INVALID, "op_assemble_rows: cu_seqlens_host[0] is %d", req->cu_seqlens_host[0]);
+  bool any_query = false, any_ctx = false;
+  int64_t at = 0;
+  for (int r = 0; r < req->n_rows; ++r) {
+    const int32_t* pr = req->plan_host + (size_t)r * 4;
+    const int query = pr[0], first = pr[1], n = pr[2], clip = pr[3];
+    if (query < 0 || query >= req->n_queries) return fail(h, OP_ERR_INVALID, "op_assemble_rows: row %d names query %d of %d", r, query, req->n_queries);
+    if (first < 0 || n < 0 || first > req->n_frag - n)
+      return fail(h, OP_ERR_INVALID, "op_assemble_rows: row %d takes fragments %d .. %d + %d of %d", r, first, first, n, req->n_frag);
+    int64_t ctx = 0;
+    if (n > 0) {
+      const int32_t* fo = req->frag_off_host + first;
+      if (fo[0] < 0 || fo[1] < fo[0] || fo[n] < fo[1] || fo[n] > n_corpus)
+        return fail(h, OP_ERR_INVALID, "op_assemble_rows: frag_off decreases or leaves the corpus at row %d", r);
+      if (clip < 0 || clip > fo[1] - fo[0])
+        return fail(h, OP_ERR_INVALID, "op_assemble_rows: row %d clips its first fragment of %d ids to %d", r, fo[1] - fo[0], clip);
+      ctx = clip > 0 ? (int64_t)clip + (fo[n] - fo[1]) : (int64_t)(fo[n] - fo[0]);
+    } else if (clip != 0 && clip != -1) {
+      return fail(h, OP_ERR_INVALID, "op_assemble_rows: row %d has clip %d and no fragment", r, clip);
+    }
+    const int row_suffix = (n == 0 && clip == -1) ? 0 : n_pieces[2];
+    const int q_len = req->q_off_host[query + 1] - req->q_off_host[query];
+    any_query |= q_len > 0;
+    any_ctx |= ctx > 0;
+    at += (int64_t)n_pieces[0] + q_len + n_pieces[1] + ctx + row_suffix;
+    if (at > (int64_t)INT32_MAX || (int64_t)req->cu_seqlens_host[r + 1] != at)
+      return fail(h, OP_ERR_INVALID, "op_assemble_rows: cu_seqlens_host[%d] is %d, the plan's rows end at %lld", r + 1,
+                  req->cu_seqlens_host[r + 1], (long long)at);
+  }
+  if (at != (int64_t)req->total_tokens)
+    return fail(h, OP_ERR_INVALID, "op_assemble_rows: the plan's rows hold %lld ids, total_tokens is %d", (long long)at, req->total_tokens);
+  if (at > 0 && !ids_dev) return fail(h, OP_ERR_INVALID, "op_assemble_rows: ids_dev is NULL");
+  if (any_query && !req->query_ids_dev) return fail(h, OP_ERR_INVALID, "op_assemble_rows: query_ids_dev is NULL");
+  if (any_ctx && !req->corpus_dev) return fail(h, OP_ERR_INVALID, "op_assemble_rows: corpus_dev is NULL");
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_assemble_rows: NULL handle");
+  if (at == 0) return OP_OK;
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  opl::launch_assemble_rows(reinterpret_cast<hipStream_t>(hip_stream), req->corpus_dev, req->frag_off_dev, req->n_frag, n_corpus,
+                            req->query_ids_dev, req->q_off_dev, req->n_queries, n_query_tokens, pieces, n_pieces, req->plan_dev,
+                            req->cu_seqlens_dev, req->n_rows, req->total_tokens, ids_dev);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
 }  // extern "C"

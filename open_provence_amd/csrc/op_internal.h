@@ -146,4 +146,11 @@ void launch_audit_compare(hipStream_t st, const float* prune, const float* rank,
                           const int32_t* rows, int n_rows, const float* sub_prune, const float* sub_rank, const int32_t* sub_cu,
                           int n_labels, float* err);
 
+// op_assemble_rows (opk_assemble.hip.h; op_launch_assemble.hip): pieces = {prefix, middle, suffix} on the host, each of
+// n_pieces[i] <= ASSEMBLE_PIECE_MAX ids (checked by the caller); plan [n_rows][4] = {query, first_frag, n_frag, clip}; n_rows > 0.
+constexpr int ASSEMBLE_PIECE_MAX = 8;
+void launch_assemble_rows(hipStream_t st, const int32_t* corpus, const int32_t* frag_off, int n_frag, int n_corpus, const int32_t* query_ids,
+                          const int32_t* q_off, int n_queries, int n_query_tokens, const int32_t* const pieces[3], const int n_pieces[3],
+                          const int32_t* plan, const int32_t* cu, int n_rows, int total, int32_t* out);
+
 }  // namespace opl

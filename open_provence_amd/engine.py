@@ -598,6 +598,61 @@ class HipEncoder:
         _lib.check(self.lib, self._handle, code, "op_segment_means")
         return out
 
+    def assemble_rows(self, corpus: torch.Tensor, frag_off: torch.Tensor, frag_off_host: np.ndarray, query_ids: torch.Tensor,
+                      q_off: torch.Tensor, q_off_host: np.ndarray, template: "Sequence[Sequence[int]]", plan: torch.Tensor,
+                      plan_host: np.ndarray, cu_seqlens: torch.Tensor, cu_seqlens_host: np.ndarray,
+                      out: "torch.Tensor | None" = None) -> torch.Tensor:
+        """``op_assemble_rows``: the packed ``ids[T]`` of ``prefix + query + middle + context + suffix`` rows, laid out on
+        this device from a resident corpus (``corpus`` int32: the fragments' ids end to end, ``frag_off`` their offsets),
+        the request's queries (``query_ids`` / ``q_off``) and a plan ``[n_rows, 4]`` int32 of ``{query, first_frag, n_frag,
+        clip}`` per row; ``template`` = the three pieces (at most 8 ids each).  The ``*_host`` numpy arrays are the host
+        copies of the device tensors of the same name: the library checks the request on them (``cu_seqlens_host`` must be
+        the prefix sums of the plan's row lengths) and refuses before it enqueues, so nothing is read back.  Asynchronous on
+        the current stream; ``out`` (int32, at least T elements) or a new tensor."""
+
+        if not hasattr(self.lib, "op_assemble_rows"):
+            raise _lib.HipLibraryError("this library has no op_assemble_rows")
+        device_side = {"corpus": corpus, "frag_off": frag_off, "query_ids": query_ids, "q_off": q_off, "plan": plan, "cu_seqlens": cu_seqlens}
+        for name, tensor in device_side.items():
+            if tensor.dtype != torch.int32 or tensor.device != self.device or not tensor.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous int32 tensor on {self.device}")
+        hosts = []
+        for name, array in (("frag_off_host", frag_off_host), ("q_off_host", q_off_host), ("plan_host", plan_host), ("cu_seqlens_host", cu_seqlens_host)):
+            if not isinstance(array, np.ndarray) or array.dtype != np.int32 or not array.flags.c_contiguous:
+                raise ValueError(f"{name} must be a C-contiguous int32 numpy array")
+            hosts.append(array)
+        n_rows = int(cu_seqlens_host.shape[0]) - 1
+        if (n_rows < 0 or plan_host.size != 4 * n_rows or plan.numel() != 4 * n_rows or cu_seqlens.numel() != n_rows + 1
+                or frag_off.numel() != frag_off_host.size or q_off.numel() != q_off_host.size or frag_off_host.size < 1 or q_off_host.size < 1):
+            raise ValueError("plan / cu_seqlens / offsets: the host and device copies differ in size, or do not describe n_rows rows")
+        if corpus.numel() < int(frag_off_host[-1]) or query_ids.numel() < int(q_off_host[-1]):
+            raise ValueError("corpus / query_ids are shorter than their offsets say")
+        total = int(cu_seqlens_host[-1])
+        pieces = [np.ascontiguousarray(np.asarray(piece, dtype=np.int32).reshape(-1)) for piece in template]
+        if len(pieces) != 3:
+            raise ValueError("template must be (prefix, middle, suffix)")
+        if out is None:
+            out = torch.empty(max(total, 0), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.device != self.device or not out.is_contiguous() or out.numel() < total:
+            raise ValueError(f"out must be a contiguous int32 tensor of at least {total} elements on {self.device}")
+        req = _lib.OpAssembleRequest()
+        req.struct_bytes = ctypes.sizeof(_lib.OpAssembleRequest)
+        req.n_frag, req.n_queries, req.n_rows, req.total_tokens = int(frag_off_host.size) - 1, int(q_off_host.size) - 1, n_rows, total
+        req.n_prefix, req.n_middle, req.n_suffix = (int(p.size) for p in pieces)
+        req.prefix, req.middle, req.suffix = (p.ctypes.data if p.size else None for p in pieces)
+        req.corpus_dev = corpus.data_ptr() if corpus.numel() else None
+        req.frag_off_dev, req.frag_off_host = frag_off.data_ptr(), frag_off_host.ctypes.data
+        req.query_ids_dev = query_ids.data_ptr() if query_ids.numel() else None
+        req.q_off_dev, req.q_off_host = q_off.data_ptr(), q_off_host.ctypes.data
+        req.plan_dev, req.plan_host = (plan.data_ptr(), plan_host.ctypes.data) if n_rows else (None, None)
+        req.cu_seqlens_dev, req.cu_seqlens_host = cu_seqlens.data_ptr(), cu_seqlens_host.ctypes.data
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_assemble_rows(self._handle, ctypes.byref(req), ctypes.c_void_p(out.data_ptr()) if out.numel() else None,
+                                             ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_assemble_rows")
+        return out[:total]
+
     def forward_packed(
         self,
         ids: torch.Tensor,

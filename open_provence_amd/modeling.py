@@ -36,6 +36,7 @@ from .config import DEFAULT_PROCESS_THRESHOLD, EncoderDims, OpenProvenceConfig
 from .engine import AttentionRequest, HiddenRequest, HipEncoder, check_arithmetic_arguments, require_gpu
 from .packing import pack_padded, pack_rows, unpack_to_padded
 from .pipeline import ContextState, FragmentRecord, RawPrediction
+from .prepared import PreparedContexts, PreparedItem, PreparedView, as_request as _as_prepared_request, derive_row_template
 from .splitters import SentenceSplitter, is_builtin_splitter, resolve_sentence_splitter
 
 LOGGER = logging.getLogger(__name__)
@@ -933,13 +934,18 @@ class OpenProvenceModel:
         return self._enqueue_packed(*self._pack_launch(rows, segments))
 
     def _enqueue_packed(self, ids_np: np.ndarray, cu_np: np.ndarray, max_len: int, seg_flat: np.ndarray | None,
-                        seg_counts: list[int] | None, reuse_slot: int | None = None) -> dict[str, Any]:
+                        seg_counts: list[int] | None, reuse_slot: int | None = None, *, assemble: dict[str, Any] | None = None,
+                        ids_dev: torch.Tensor | None = None) -> dict[str, Any]:
         """Enqueue one forward over packed rows (:meth:`_pack_launch`); also what the range guard of the fp16 + e4m3
         kernel sets repeats, see :meth:`_guard_launch`."""
 
         shard = None
         retry = (ids_np, cu_np, max_len, seg_flat, seg_counts)
-        self.encoder.check_ids(ids_np)
+        # Prepared contexts (``ids_np`` is None): the ids are laid out on the device by ``assemble`` (:meth:`_assemble_on_device`
+        # from the request's plan) or, the range guard's repeat, are the launch's own ``ids_dev`` once more.  They were
+        # checked when the corpus and the request's queries were uploaded.
+        if ids_np is not None:
+            self.encoder.check_ids(ids_np)
         total, n_rows, nl = int(cu_np[-1]), len(cu_np) - 1, int(self.dims.num_labels)
         if n_rows == 0:  # (more ranks than rows) nothing to enqueue here; the gather still runs on every rank
             return {"event": None, "pool": None, "total": 0, "rows": 0, "cu": cu_np, "seg_counts": [] if seg_counts is not None else None,
@@ -951,12 +957,19 @@ class OpenProvenceModel:
             slot = reuse_slot
         else:
             slot = self.__dict__["_staging_slot"] = (self.__dict__.get("_staging_slot", -1) + 1) % 2
-        pool = self._staging(slot, total, n_rows)
+        pool = self._staging(slot, max(total, 4 * n_rows) if assemble is not None else total, n_rows)
         dev = self._runtime_device
-        np.copyto(pool["ids_np"][:total], ids_np)
         np.copyto(pool["cu_np"][: n_rows + 1], cu_np)
-        ids_dev = pool["ids"][:total].to(dev, non_blocking=True)
         cu_dev = pool["cu"][: n_rows + 1].to(dev, non_blocking=True)
+        if ids_np is not None:
+            np.copyto(pool["ids_np"][:total], ids_np)
+            ids_dev = pool["ids"][:total].to(dev, non_blocking=True)
+        elif assemble is not None:
+            # the plan travels through the slot's id staging (4 words per row instead of the row's tokens)
+            plan_np = assemble["plan"]
+            np.copyto(pool["ids_np"][: plan_np.size], plan_np.reshape(-1))
+            plan_dev = pool["ids"][: plan_np.size].to(dev, non_blocking=True)
+            ids_dev = self._assemble_on_device(assemble, plan_dev, plan_np, cu_dev, cu_np)
         keep_dev = torch.empty(total, dtype=torch.float32, device=dev)
         seg_dev = means_dev = None
         n_seg = 0
@@ -979,7 +992,7 @@ class OpenProvenceModel:
         event.record(torch.cuda.current_stream(dev))
         return {"event": event, "pool": pool, "total": total, "rows": n_rows, "cu": cu_np, "seg_counts": seg_counts,
                 "alive": (ids_dev, cu_dev, keep_dev, rank_dev, seg_dev, means_dev), "shard": shard, "retry": retry,
-                "f8": self.encoder.f8_active(), "slot": slot}
+                "f8": self.encoder.f8_active(), "slot": slot, "ids_dev": ids_dev if ids_np is None else None}
 
     def _guard_launch(self, handle: dict[str, Any]) -> dict[str, Any]:
         """Range guard of the fp16 + e4m3 kernel sets for a pipelined launch (the launch has completed): when its
@@ -998,7 +1011,8 @@ class OpenProvenceModel:
         if self.encoder.f8_active():
             return handle  # (nothing to fall back to: the caller reports the NaN)
         handle["alive"] = None
-        again = self._enqueue_packed(*handle["retry"], reuse_slot=handle.get("slot"))
+        # (a device-assembled launch is repeated on the ids it laid out: the same device buffer, no second assembly)
+        again = self._enqueue_packed(*handle["retry"], reuse_slot=handle.get("slot"), ids_dev=handle.get("ids_dev"))
         again["shard"] = handle.get("shard")
         again["event"].synchronize()
         return again
@@ -1668,6 +1682,248 @@ class OpenProvenceModel:
             self._store_raw_predictions(chunk, ranges_per_job, queries, states, rank, keeps)
         return waited
 
+    # ------------------------------------------------------------------------------------------
+    # prepared contexts (prepared.py): the query-independent stages once per corpus
+    # ------------------------------------------------------------------------------------------
+    def prepare_contexts(
+        self,
+        contexts: Sequence[str] | Sequence[Sequence[str]],
+        title: None | str | Sequence[str] = "first_sentence",
+        first_line_as_title: bool = False,
+        *,
+        sentence_splitter: SentenceSplitter | Mapping[str, SentenceSplitter] | None = None,
+        language: str | None = None,
+        strip_sentences: bool = False,
+        respect_sentence_boundaries: bool = False,
+        preprocess_workers: int | None = None,
+    ) -> PreparedContexts:
+        """Split, tokenise and fragmentise a corpus ONCE: ``contexts`` is a flat sequence, each entry a string or a list
+        of pre-split sentences, as one question's context list is in :meth:`process`; ``title`` / ``first_line_as_title``
+        as there for one question.  ``process(question, prepared)`` or ``process(question, prepared.select(indices))``
+        then returns what ``process(question, [those contexts], title=...)`` with the same arguments returns, while the
+        host only tokenises the question and plans blocks and forwards from lengths; on the native forward the rows are
+        laid out on the device from the fragments' token ids, which are uploaded on first use (4 bytes per token, below
+        2^31 tokens in all).  The object belongs to this model, its tokenizer and ``max_length``.  Sharded and front-end
+        requests are not supported on prepared contexts."""
+
+        if isinstance(contexts, (str, bytes)) or not pl._is_sequence(contexts):
+            raise ValueError("prepare_contexts takes a flat sequence of contexts (strings or lists of sentences)")
+        splitter = self._resolve_sentence_splitter(sentence_splitter, language)
+        _queries, nested, _structure = pl.normalize_inputs("", list(contexts))
+        nested, titles = self._resolve_titles([""], nested, title, first_line_as_title=first_line_as_title)
+        entries = nested[0]
+        if respect_sentence_boundaries:  # (the rule of _process_impl)
+            max_fragment_tokens = max(16, self.max_length - 2)
+        else:
+            max_fragment_tokens = max(16, self.max_length // 2)
+        timing = {"sentence_collect_seconds": 0.0, "sentence_normalize_seconds": 0.0, "tokenize_seconds": 0.0,
+                  "fragment_split_seconds": 0.0, "fragment_decode_seconds": 0.0}
+        if preprocess_workers is not None:
+            workers = min(max(0, int(preprocess_workers)), 32)
+        else:  # (process()'s own rule for worker threads without a request)
+            workers = 4 if (len(entries) >= 128 and is_builtin_splitter(splitter)
+                            and hasattr(getattr(self.tokenizer, "_tokenizer", None), "encode_batch")) else 0
+        t0 = perf_counter()
+        jobs = self._iter_jobs(
+            [""], [entries], titles, splitter, [], strip_sentences=strip_sentences, timing=timing, workers=workers,
+            fragment_args=dict(max_fragment_tokens=max_fragment_tokens, strip_sentences=strip_sentences,
+                               respect_sentence_boundaries=respect_sentence_boundaries),
+        )
+        items: list[PreparedItem] = []
+        frag_base = 0
+        for job in jobs:
+            items.append(PreparedItem(entries[job["context_idx"]], job, frag_base))
+            frag_base += len(job["fragments"])
+        timing["total_seconds"] = perf_counter() - t0
+        template = derive_row_template(
+            lambda query, ctx: self._prepare_block_inputs(query, [FragmentRecord("", 0, 0, 0, len(ctx), list(ctx))])[0])
+        settings = {
+            "title": title if (title is None or isinstance(title, str)) else [list(t) if pl._is_sequence(t) else str(t) for t in title],
+            "first_line_as_title": bool(first_line_as_title), "sentence_splitter": sentence_splitter, "language": language,
+            "strip_sentences": bool(strip_sentences), "respect_sentence_boundaries": bool(respect_sentence_boundaries),
+            "manual_specials": (getattr(self, "_manual_special_tokens_required", False), getattr(self, "_manual_cls_token_id", None),
+                                getattr(self, "_manual_sep_token_id", None)),
+        }
+        return PreparedContexts(self, items, settings, template, timing)
+
+    def _check_prepared_request(self, corpus: PreparedContexts, given: Mapping[str, Any]) -> None:
+        """The refusals of ``process()`` on prepared contexts (``ValueError``)."""
+
+        if corpus.model is not self:
+            raise ValueError("these contexts were prepared by another model instance: prepare them with this model's prepare_contexts()")
+        manual = (getattr(self, "_manual_special_tokens_required", False), getattr(self, "_manual_cls_token_id", None),
+                  getattr(self, "_manual_sep_token_id", None))
+        if corpus.tokenizer is not self.tokenizer or manual != corpus.settings["manual_specials"]:
+            raise ValueError("the model's tokenizer has changed since these contexts were prepared: prepare them again")
+        if int(self.max_length) != corpus.max_length:
+            raise ValueError(f"max_length is {self.max_length} but these contexts were prepared with max_length {corpus.max_length}: "
+                             "prepare them again")
+        defaults = {"title": "first_sentence", "first_line_as_title": False, "sentence_splitter": None, "language": None,
+                    "strip_sentences": False, "respect_sentence_boundaries": False}
+        for name, default in defaults.items():
+            value, kept = given[name], corpus.settings[name]
+            if name == "title" and not (value is None or isinstance(value, str)):
+                value = [list(t) if pl._is_sequence(t) else str(t) for t in value]
+            same_as_default = value is default or (isinstance(default, str) and value == default)
+            if not same_as_default and not (value is kept or value == kept):
+                raise ValueError(f"process() on prepared contexts got {name}={given[name]!r}, but they were prepared with "
+                                 f"{name}={kept!r}: these arguments belong to prepare_contexts()")
+        if getattr(self, "_dist", None) or self.__dict__.get("_remote_forward") is not None:
+            raise ValueError("prepared contexts do not support a process group or a host front-end: sharded prepared requests "
+                             "are out of scope (detach the group, or pass the raw texts)")
+
+    def _prepared_device_corpus(self, corpus: PreparedContexts) -> dict[str, Any]:
+        """The resident corpus of ``op_assemble_rows``, uploaded on first use: the fragments' token ids as one flat int32
+        buffer in context order then fragment order, their offsets, the template pieces -- ids checked against the
+        embedding table once, here."""
+
+        device = corpus._device
+        if device is None or device["device"] != self._runtime_device:
+            ids_np, frag_off_np = corpus.flat_tokens()
+            pieces = [np.asarray(p, dtype=np.int32) for p in (corpus.template.prefix, corpus.template.middle, corpus.template.suffix)]
+            self.encoder.check_ids(ids_np)
+            for piece in pieces:
+                self.encoder.check_ids(piece)
+            dev = self._runtime_device
+            device = corpus._device = {
+                "device": dev, "ids": torch.from_numpy(ids_np).to(dev), "frag_off": torch.from_numpy(frag_off_np).to(dev),
+                "frag_off_np": frag_off_np, "pieces": pieces,
+            }
+        return device
+
+    def _assemble_on_device(self, assemble: dict[str, Any], plan_dev, plan_np, cu_dev, cu_np) -> torch.Tensor:
+        corpus, queries = assemble["corpus"], assemble["queries"]
+        return self.encoder.assemble_rows(corpus["ids"], corpus["frag_off"], corpus["frag_off_np"], queries["ids"], queries["off"],
+                                          queries["off_np"], corpus["pieces"], plan_dev, plan_np, cu_dev, cu_np)
+
+    def _run_prepared_request(self, views: Sequence[PreparedView], batch_size: int, queries: list[str], query_token_ids: list[list[int]],
+                              sep_len: int, states: dict[tuple[int, int], ContextState], pending: list[Any]) -> tuple[float, float, int]:
+        """The request-time half of ``process()`` on prepared contexts -> (assembly seconds, inference seconds, blocks).
+
+        Blocks come from the cached fragments by length arithmetic (``PreparedItem.blocks_for``); the states are what
+        ``_process_impl`` builds from a job.  A replaced forward, a corpus without a row template, or a library without
+        ``op_assemble_rows``: the rows are built on the host from the cached fragments (:meth:`_run_inference_batches`,
+        at most ``batch_size`` rows per call of a replaced forward).  Native forward: ONE ``plan_forward_chunks`` over all
+        rows of the request within the token budget; per forward the plan (4 words per row), ``cu_seqlens`` and the
+        fragment ranges are uploaded, ``op_assemble_rows`` lays the ids out and the forward runs on them."""
+
+        t_asm = perf_counter()
+        corpus = views[0].corpus
+        tokenizer, max_length = self.tokenizer, self.max_length
+        on_device = (self._forward_is_native() and corpus.template is not None and hasattr(self.encoder.lib, "op_assemble_rows")
+                     and self.__dict__.get("_remote_forward") is None)
+
+        def state_of(q_idx, c_idx, item, blocks):
+            state = states.get((q_idx, c_idx))
+            if state is None:
+                state = states[(q_idx, c_idx)] = ContextState(
+                    sentences=list(item.sentences),
+                    fragments=item.fragments,
+                    blocks=blocks,
+                    prefix_length=len(item.prefix_sentences),
+                    prefix_sentences=item.prefix_sentences,
+                    prefix_token_counts=item.prefix_token_counts,
+                    title_is_first_sentence=item.title_is_first_sentence,
+                    original_text=item.context_text,
+                )
+            return state
+
+        # per row of the request: query, context, block, the context's item and blocks, (first fragment within the context,
+        # fragments, clip, context tokens).  Lengths only: states and jobs are built forward by forward, beside the GPU.
+        rows: list[tuple] = []
+        for q_idx, view in enumerate(views):
+            q_len = len(query_token_ids[q_idx])
+            for c_idx, at in enumerate(view.indices):
+                item = corpus.items[at]
+                blocks, plan = item.blocks_for(tokenizer, q_len, sep_len, max_length)
+                if not blocks:
+                    state_of(q_idx, c_idx, item, blocks)
+                for b_idx, entry in enumerate(plan):
+                    rows.append((q_idx, c_idx, b_idx, item, blocks, entry))
+        if not rows:
+            return perf_counter() - t_asm, 0.0, 0
+        if not on_device:
+            inference_jobs = []
+            for q_idx, c_idx, b_idx, item, blocks, _entry in rows:
+                state_of(q_idx, c_idx, item, blocks)
+                inference_jobs.append({"query_idx": q_idx, "context_idx": c_idx, "block_idx": b_idx, "texts": [f.text for f in blocks[b_idx]]})
+            assembly = perf_counter() - t_asm
+            return assembly, self._run_inference_batches(inference_jobs, batch_size, queries, query_token_ids, states, pending), len(rows)
+
+        template = corpus.template
+        n_fixed = len(template.prefix) + len(template.middle) + len(template.suffix)
+        ctx_at = [len(template.prefix) + len(q) + len(template.middle) for q in query_token_ids]
+        # ids a context must not begin with for its place in the row to follow from lengths alone: the reference looks the
+        # context's tokens up in the row (pipeline.prepare_block_inputs), and an earlier occurrence can only start there
+        heads = [set(template.prefix) | set(q) | set(template.middle) for q in query_token_ids]
+        # a row without context tokens (an empty context's fallback sentence): no fragments in its plan, and no suffix where
+        # the tokenizer builds none for an empty second sequence; a layout that is neither comes from the host (below)
+        drop = len(template.suffix) if template.empty_context == "drop" else 0
+        q_lens = [len(q) for q in query_token_ids]
+        lengths = [n_fixed + q_lens[row[0]] + row[5][3] - (0 if row[5][3] else drop) for row in rows]
+        spans = pl.plan_forward_chunks(lengths, batch_size, self.forward_token_budget)
+        device_corpus = self._prepared_device_corpus(corpus)
+        q_off_np = np.zeros(len(query_token_ids) + 1, dtype=np.int32)
+        q_off_np[1:] = np.cumsum(q_lens)
+        q_ids_np = np.fromiter((t for q in query_token_ids for t in q), dtype=np.int32, count=int(q_off_np[-1]))
+        self.encoder.check_ids(q_ids_np)
+        dev = self._runtime_device
+        request_dev = {"ids": torch.from_numpy(q_ids_np).to(dev), "off": torch.from_numpy(q_off_np).to(dev), "off_np": q_off_np}
+        assembly = perf_counter() - t_asm
+        elapsed = 0.0
+        for start, stop in spans:
+            t_asm = perf_counter()
+            n_rows = stop - start
+            chunk: list[dict[str, Any]] = []
+            plan_np = np.empty((n_rows, 4), dtype=np.int32)
+            ranges_per_job: list[list[tuple[int, int]]] = []
+            segments: list[list[tuple[int, int]]] = []
+            on_host = False
+            for i, (q_idx, c_idx, b_idx, item, blocks, (first, count, clip, ctx_len)) in enumerate(rows[start:stop]):
+                state = state_of(q_idx, c_idx, item, blocks)
+                block = blocks[b_idx]
+                chunk.append({"query_idx": q_idx, "context_idx": c_idx, "block_idx": b_idx, "texts": [f.text for f in block]})
+                if ctx_len == 0:
+                    on_host = on_host or template.empty_context is None
+                    plan_np[i] = (q_idx, item.frag_base + first, 0, -1 if drop else 0)
+                else:
+                    plan_np[i] = (q_idx, item.frag_base + first, count, clip)
+                if ctx_len == 0 or not block[0].token_ids or block[0].token_ids[0] in heads[q_idx]:
+                    ranges = self._prepare_block_inputs(query_token_ids[q_idx], block)[3]
+                else:
+                    ranges, cursor = [], ctx_at[q_idx]
+                    for fragment in block:
+                        ranges.append((cursor, cursor + len(fragment.token_ids)))
+                        cursor += len(fragment.token_ids)
+                ranges_per_job.append(ranges)
+                segments.append(pl.fragment_token_ranges(state, block, ranges, lengths[start + i]))
+            if on_host:  # ... this forward's rows are built on the host
+                host_rows = [self._prepare_block_inputs(query_token_ids[row[0]], row[4][row[2]])[0] for row in rows[start:stop]]
+                assembly += perf_counter() - t_asm
+                t0 = perf_counter()
+                handle = self._launch_rows(host_rows, segments)
+            else:
+                cu_np = np.zeros(n_rows + 1, dtype=np.int32)
+                cu_np[1:] = np.cumsum(lengths[start:stop])
+                seg_counts = [len(s) for s in segments]
+                seg_flat = np.empty(2 * sum(seg_counts), dtype=np.int32)
+                pos = 0
+                for i, segs in enumerate(segments):  # (absolute positions of the packed batch, as _pack_launch writes them)
+                    base = int(cu_np[i])
+                    for seg_start, seg_end in segs:
+                        seg_flat[pos] = base + seg_start
+                        seg_flat[pos + 1] = base + seg_end if seg_end > seg_start else base + seg_start
+                        pos += 2
+                assembly += perf_counter() - t_asm
+                t0 = perf_counter()
+                handle = self._enqueue_packed(None, cu_np, max(lengths[start:stop]), seg_flat, seg_counts,
+                                              assemble={"plan": plan_np, "corpus": device_corpus, "queries": request_dev})
+            elapsed += perf_counter() - t0
+            pending.append((handle, chunk, ranges_per_job, queries, states))
+            if len(pending) > 1:
+                elapsed += self._flush_pending(pending, keep_last=1)
+        return assembly, elapsed, len(rows)
+
     def _gather_job_results(self, result, owned, info, error: BaseException | None = None):
         """Job-sharded ``process()``: every rank sends the post-processed fields of the contexts it owns to rank
         ``dst`` (one ``gather_object``; the payload is the texts and a few floats per context), which writes them into
@@ -1774,7 +2030,17 @@ class OpenProvenceModel:
         # (the reference's auto rule, standalone.py:2588-2596), whenever the tokenizer and the splitter can be sent to a
         # process that does not import the caller's __main__; threads otherwise.  OPEN_PROVENCE_HOST_REPLICAS=0 keeps
         # everything in this process.
-        replicas, implicit = self._front_end_request(context, preprocess_workers, torch_dataloader_kwargs)
+        # Prepared contexts (prepare_contexts): a PreparedContexts / PreparedView, or a list of views with a list of questions.
+        # The request stays in this process -- no front-end, no process group -- and only its query-dependent half runs.
+        prepared = _as_prepared_request(question, context)
+        if prepared is not None:
+            self._check_prepared_request(prepared[1][0].corpus, dict(
+                title=title, first_line_as_title=first_line_as_title, sentence_splitter=sentence_splitter, language=language,
+                strip_sentences=strip_sentences, respect_sentence_boundaries=respect_sentence_boundaries))
+            settings = prepared[1][0].corpus.settings
+            first_line_as_title = settings["first_line_as_title"]
+            strip_sentences, respect_sentence_boundaries = settings["strip_sentences"], settings["respect_sentence_boundaries"]
+        replicas, implicit = ("", True) if prepared is not None else self._front_end_request(context, preprocess_workers, torch_dataloader_kwargs)
         if (replicas and not getattr(self, "_dist", None) and self.__dict__.get("_remote_forward") is None
                 and not isinstance(context, str)):
             routed = self._process_through_front_end(replicas, implicit, dict(
@@ -1805,7 +2071,7 @@ class OpenProvenceModel:
                 strip_sentences=strip_sentences, respect_sentence_boundaries=respect_sentence_boundaries,
                 return_sentence_metrics=return_sentence_metrics, return_sentence_texts=return_sentence_texts,
                 show_inference_progress=show_inference_progress, preprocess_workers=preprocess_workers,
-                preprocess_batch_size=preprocess_batch_size, torch_dataloader_kwargs=torch_dataloader_kwargs,
+                preprocess_batch_size=preprocess_batch_size, torch_dataloader_kwargs=torch_dataloader_kwargs, prepared=prepared,
             )
         finally:
             self.__dict__.pop("_forward_stats", None)  # (the call's counter: later get_raw_predictions* calls count nowhere)
@@ -1932,6 +2198,7 @@ class OpenProvenceModel:
         preprocess_workers,
         preprocess_batch_size,
         torch_dataloader_kwargs,
+        prepared=None,
     ):
         batch_size = max(1, batch_size)
         threshold = self._resolve_process_threshold(threshold)
@@ -1964,11 +2231,18 @@ class OpenProvenceModel:
             # (host-mode front-end: the owner has normalised the request and assigned the jobs once for all replicas; a
             # replica gets the normalised structure with the texts of the contexts it does not own blanked)
             handed = (getattr(self, "_dist", None) or {}).get("prenormalized")
-            if handed is not None:
+            if prepared is not None:
+                # (prepared.as_request: one view per query; `contexts` = the entries post-processing falls back to, as title
+                # resolution left them at preparation.  The job stream below gets no contexts: it tokenises the queries.)
+                queries, views, structure = prepared
+                contexts = [[view.corpus.items[i].entry for i in view.indices] for view in views]
+                titles = [None] * len(queries)
+            elif handed is not None:
                 queries, contexts, structure = handed["queries"], handed["contexts"], handed["structure"]
             else:
                 queries, contexts, structure = self._normalize_inputs(question, context)
-            contexts, titles = self._resolve_titles(queries, contexts, title, first_line_as_title=first_line_as_title)
+            if prepared is None:
+                contexts, titles = self._resolve_titles(queries, contexts, title, first_line_as_title=first_line_as_title)
             if respect_sentence_boundaries:
                 max_fragment_tokens = max(16, self.max_length - 2)
             else:
@@ -1976,7 +2250,7 @@ class OpenProvenceModel:
             sep_token_ids = self.tokenizer.encode(self.tokenizer.sep_token or "", add_special_tokens=False)
 
             query_token_ids: list[list[int]] = []
-            total_jobs = sum(len(per_query) for per_query in contexts)
+            total_jobs = sum(len(per_query) for per_query in contexts) if prepared is None else 0
             # job-level sharding (attach_process_group(shard="jobs")): this rank prepares, runs and post-processes only
             # the contexts it owns; the forward batches below are then purely local
             job_shard = getattr(self, "_dist", None)
@@ -2065,7 +2339,7 @@ class OpenProvenceModel:
                     f"preprocess_batch={preprocess_batch} default_workers={pl.default_preprocess_workers()}"
                 )
             job_stream = self._iter_jobs(
-                queries, contexts, titles, splitter, query_token_ids, strip_sentences=strip_sentences, timing=timing,
+                queries, contexts if prepared is None else [[] for _ in queries], titles, splitter, query_token_ids, strip_sentences=strip_sentences, timing=timing,
                 workers=thread_workers, group_size=min(64, max(1, preprocess_batch)), owned=owned,
                 fragment_args=dict(max_fragment_tokens=max_fragment_tokens, strip_sentences=strip_sentences,
                                    respect_sentence_boundaries=respect_sentence_boundaries) if thread_workers > 0 else None,
@@ -2126,6 +2400,11 @@ class OpenProvenceModel:
                 if inference_jobs:
                     inference_time += self._run_inference_batches(inference_jobs, batch_size, queries, query_token_ids, states, pending)
                     total_blocks += len(inference_jobs)
+            if prepared is not None:
+                t_asm, t_inf, n_blocks = self._run_prepared_request(views, batch_size, queries, query_token_ids, len(sep_token_ids), states, pending)
+                assembly_time += t_asm
+                inference_time += t_inf
+                total_blocks += n_blocks
             inference_time += self._flush_pending(pending)
 
             if show_progress and total_blocks and is_progress_bar_enabled():

@@ -103,7 +103,12 @@ def main():
                     help="synth: O(1) worst-case weights (the default kernel set stays); refinit: reference initialisation (calibrates to 'f16')")
     ap.add_argument("--audit", default=None, choices=["off", "first", "running"],
                     help="audit policy of the calibrated kernel set (HipEncoder(audit=...), here through OPEN_PROVENCE_AUDIT)")
+    ap.add_argument("--prepared", action="store_true",
+                    help="prepare the contexts once, outside the timed region (OpenProvenceModel.prepare_contexts), and time requests on the "
+                    "prepared object; in-process only.  The line gains the one-off preparation time and the forwards of a request")
     args = ap.parse_args()
+    if args.prepared and (args.front_end or args.host_front_end):
+        raise SystemExit("--prepared runs in this process: prepared contexts take no front-end")
     os.environ["E2E_WEIGHTS"] = args.weights
     if args.audit is not None:
         os.environ["OPEN_PROVENCE_AUDIT"] = {"off": "0", "first": "1", "running": "running"}[args.audit]
@@ -139,9 +144,16 @@ def main():
     else:
         target = build_e2e_model()
 
+    prepared, prepare_seconds = None, None
+    if args.prepared:
+        t0 = time.perf_counter()
+        prepared = target.prepare_contexts(contexts, sentence_splitter=period_splitter, preprocess_workers=args.workers)
+        prepare_seconds = time.perf_counter() - t0
+
     def call():
-        return target.process(question, contexts, threshold=0.1, batch_size=args.batch_size, sentence_splitter=period_splitter,
-                              show_progress=False, preprocess_batch_size=args.preprocess_batch, preprocess_workers=args.workers)
+        return target.process(question, contexts if prepared is None else prepared, threshold=0.1, batch_size=args.batch_size,
+                              sentence_splitter=period_splitter, show_progress=False, preprocess_batch_size=args.preprocess_batch,
+                              preprocess_workers=args.workers)
 
     if len(budgets) > 1:
         if front is not None:
@@ -157,6 +169,7 @@ def main():
     audits_warm = audits_so_far()
     best = None
     inference_all = []
+    walls, forwards = [], None
     for _ in range(args.reps):
         r0 = resource.getrusage(resource.RUSAGE_SELF)
         t0 = time.perf_counter()
@@ -170,11 +183,19 @@ def main():
         inference_all.append(round(float(out["timing"]["inference_seconds"]), 5))
         if best is None or dt < best[0]:
             best = (dt, out["timing"], usage)
+        walls.append(round(dt, 5))
+        forwards = getattr(out["performance_trace"], "runtime", {}).get("forwards")
     dt, timing, usage = best
     encoder = getattr(target, "encoder", None)
     audit_info = {} if encoder is None else {"weights": args.weights, "audit": encoder.audit_mode, "kernel_set": encoder.effective_policy()["kernel_set"],
                                              "audits_in_warm_up": audits_warm, "audits_in_timed_calls": audits_so_far() - audits_warm,
                                              "inference_seconds_per_call": inference_all}
+    if args.prepared:
+        audit_info = {**audit_info, "prepared": True, "prepare_seconds": round(prepare_seconds, 4),
+                      "prepare_stage_seconds": {k: round(float(v), 4) for k, v in prepared.timing.items()},
+                      "corpus_tokens": prepared.n_tokens, "corpus_device_bytes": prepared.device_bytes}
+    audit_info = {**audit_info, "batch_size": args.batch_size, "forwards": forwards, "wall_s_per_call": walls,
+                  "wall_s_median": round(float(np.median(walls)), 5)}
     print(json.dumps({**audit_info, "contexts": args.contexts, "chars": args.chars, "tokenizer": args.tokenizer, "workers": args.workers, "front_end_processes": args.front_end, "host_replicas": args.host_front_end, "wall_s": dt, "contexts_per_s": args.contexts / dt, "rusage": usage, "owner_trace": getattr(front, "last_trace", None),
                       "timing": {k: round(float(v), 5) for k, v in timing.items()}}))
     if args.profile:
