@@ -315,6 +315,47 @@ int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t
                              float* prune_logits_dev, float* rank_logits_dev, float* keep_prob_dev,
                              void* workspace_dev, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req);
 
+/* Replaces: what callers of output_hidden_states=True usually compute from it -- one vector per sequence and entry (a CLS
+ * probe, a layer-wise probe, a pooled embedding) -- reduced on the device, so that the (N + 1) x tokens x H states are never
+ * held.  Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).  One forward exactly as
+ * op_forward_packed enqueues it -- the same kernels, bit-identical logits -- whose stores of the entries `pool` selects (numbered
+ * as in op_hidden_request) go to ONE packed fp32 scratch entry [total_tokens][hidden]; a reduction kernel of the call's own
+ * pools the scratch behind each entry and the next entry reuses it (the stream orders this): the extra device memory is one
+ * entry plus the output, not num_layers + 1 entries.
+ *   kind     OP_HIDDEN_POOL_FIRST  the row of token 0 of each sequence (what classifier_pooling = "cls" reads): bit-identical
+ *                                  to that row of the fp32 entry op_forward_packed_hidden writes
+ *            OP_HIDDEN_POOL_MEAN   the mean over the sequence's tokens of the fp32 rows of the entry: fp64 partials over 64
+ *                                  consecutive tokens each, added in token order; the partials added in index order; one fp64
+ *                                  division; one rounding to fp32.  No floating-point atomics: the same bits on every call, on
+ *                                  every stream, under every batch composition and every chunk_rows (the rule of op_loss), within
+ *                                  1 fp32 ulp of the exact mean
+ *   select   host array of num_layers + 1 flags, or NULL = every entry
+ *   out_dev  fp32 [n_sel][n_seqs][hidden], the selected entries in order.  EVERY element is written (the caller zeroes
+ *            nothing); a sequence of length 0 gives a row of exactly +0.0 under both kinds
+ *   scratch_dev / scratch_bytes  caller-allocated, at least total_tokens * hidden * 4 bytes, 16-byte aligned; may hold
+ *            anything on entry, holds the last selected entry afterwards
+ * `req` (may be NULL) is an ordinary op_hidden_request riding on the same call, with its own selection, dtype and layout; an
+ * entry both select is stored once (into the scratch) and copied from there into `req`'s entry: the same values.  The final
+ * entry follows op_config.prune_pre_final_norm as in op_forward_packed_hidden.  No handle state is stored: as stream-safe as
+ * op_forward_packed (a scratch per concurrent call).  OP_ERR_INVALID before anything is enqueued, and -- for the requests' own
+ * fields -- before the handle is looked at: pool == NULL, a wrong struct_bytes of either request, an unknown kind, a misaligned
+ * scratch, everything op_forward_packed_hidden refuses in `req`; once the handle is known: out_dev or scratch_dev NULL, or
+ * scratch_bytes below one entry, with an entry selected of a non-empty batch. */
+enum op_hidden_pool_kind { OP_HIDDEN_POOL_FIRST = 0, OP_HIDDEN_POOL_MEAN = 1 };
+typedef struct op_pool_request {
+  uint32_t struct_bytes; /* sizeof(op_pool_request) */
+  int32_t kind;          /* enum op_hidden_pool_kind */
+  const uint8_t* select; /* host array of num_layers + 1 flags, or NULL = all; entry i = hidden_states[i] */
+  float* out_dev;        /* fp32 [n_sel][n_seqs][hidden] */
+  void* scratch_dev;     /* one packed fp32 entry: total_tokens * hidden * 4 bytes, 16-byte aligned */
+  size_t scratch_bytes;
+} op_pool_request;
+int op_forward_packed_pooled(op_handle* h, const int32_t* ids_dev, const int32_t* cu_seqlens_dev,
+                             const int32_t* cu_seqlens_host, int n_seqs, int total_tokens, int max_seqlen,
+                             float* prune_logits_dev, float* rank_logits_dev, float* keep_prob_dev,
+                             void* workspace_dev, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req,
+                             const op_pool_request* pool);
+
 /* Replaces: output_attentions=True of the reference forward under eager attention (standalone.py:1689, 1727; HF :166-185):
  * the softmax probabilities of ONE layer, as a side pass over that layer's input hidden state.  Additive to ABI 10
  * (op_abi_version() is unchanged: detect the two calls by symbol).  The residual stream is fp32 at every layer boundary on every
@@ -354,6 +395,42 @@ size_t op_attention_workspace_bytes(const op_handle* h, int n_seqs, int total_to
 int op_attention_probs(op_handle* h, const int32_t* cu_seqlens_dev, const int32_t* cu_seqlens_host, int n_seqs, int total_tokens,
                        int max_seqlen, const op_attention_request* req, void* workspace_dev, size_t workspace_bytes,
                        void* hip_stream);
+
+/* Replaces: reading one query row out of output_attentions=True -- "what does the pooled token look at" -- without the
+ * [heads][L][L] matrices: ONE query position per sequence of ONE layer, as a side pass over hidden_states[layer].  Additive to
+ * ABI 10 (op_abi_version() is unchanged: detect the call by symbol).  Inputs, arithmetic, fp32 packs and workspace are those of
+ * op_attention_probs (op_attention_workspace_bytes is sufficient; large batches go through in chunks of sequences): the same
+ * LayerNorm and q | k projection over all tokens, then one kernel of the call's own that walks the visible 64-key tiles of the
+ * selected query's 64-query block in op_attention_probs' order through the same device functions, with the selected query in a
+ * 16-query fragment.
+ *   query_pos_dev   int32 [n_seqs]: the query position of each sequence; NULL = position 0 everywhere
+ *   query_pos_host  NULL, or the caller's host copy of query_pos_dev: a negative position in it is refused (OP_ERR_INVALID)
+ *   reduce_heads 0  out_dev [n_seqs][num_heads][pad_width] fp32; out[s][h][j] is BIT-IDENTICAL to
+ *                   out[s][h][query_pos[s]][j] of op_attention_probs on the same inputs
+ *   reduce_heads 1  out_dev [n_seqs][pad_width] fp32: the mean over heads of those fp32 probabilities, accumulated in fp64 in
+ *                   head order, divided once, rounded to fp32 once (at most 64 heads: OP_ERR_UNSUPPORTED beyond)
+ * EVERY element of out_dev is written: exactly +0.0 at masked keys, at keys >= len[s] and out to pad_width; a whole row of +0.0
+ * when the position is at or beyond len[s] (an empty sequence included) or negative (on the device a position is compared
+ * with the length before it is used as an index).
+ * OP_ERR_UNSUPPORTED on a handle created without OP_FLAG_F32_PACKS (the message names the flag).  Refused with OP_ERR_INVALID
+ * before anything is enqueued and before the handle is looked at: a NULL request, a wrong struct_bytes, a reduce_heads other
+ * than 0 / 1, a pad_width below max_seqlen (or 0 for a non-empty batch), hidden_dev / out_dev NULL for a non-empty batch,
+ * query_pos_host without query_pos_dev, a negative position in query_pos_host.  `layer` is checked once the handle is known.
+ * Asynchronous on hip_stream (cu_seqlens_host == NULL: cu_seqlens_dev is read back, which synchronises the stream once); no
+ * handle state is stored. */
+typedef struct op_attention_rows_request {
+  uint32_t struct_bytes;         /* sizeof(op_attention_rows_request) */
+  int32_t layer;                 /* 0 <= layer < num_layers */
+  int32_t pad_width;             /* >= max_seqlen (and > 0 for a non-empty batch) */
+  int32_t reduce_heads;          /* 0: a row per head; 1: their mean */
+  const float* hidden_dev;       /* packed fp32 [total_tokens][hidden] = hidden_states[layer] */
+  const int32_t* query_pos_dev;  /* [n_seqs], or NULL = position 0 */
+  const int32_t* query_pos_host; /* optional host copy of query_pos_dev */
+  float* out_dev;                /* [n_seqs][num_heads][pad_width] or [n_seqs][pad_width] fp32 */
+} op_attention_rows_request;
+int op_attention_rows(op_handle* h, const int32_t* cu_seqlens_dev, const int32_t* cu_seqlens_host, int n_seqs, int total_tokens,
+                      int max_seqlen, const op_attention_rows_request* req, void* workspace_dev, size_t workspace_bytes,
+                      void* hip_stream);
 
 /* The padded boundary on the device.  Replaces: the reference forward taking `input_ids[B, L]` + `attention_mask[B, L]` as
  * they come from the tokenizer (standalone.py:1666-1690) and returning `pruning_logits[B, L, 2]` (standalone.py:1695-1739);

@@ -61,8 +61,10 @@ EXPORTED_SYMBOLS = (
     "op_workspace_bytes",
     "op_forward_packed",
     "op_forward_packed_hidden",
+    "op_forward_packed_pooled",
     "op_attention_workspace_bytes",
     "op_attention_probs",
+    "op_attention_rows",
     "op_pack_padded",
     "op_unpack_padded",
     "op_loss",
@@ -151,6 +153,24 @@ class OpHiddenRequest(ctypes.Structure):
 OP_HIDDEN_F32, OP_HIDDEN_BF16 = 0, 1
 
 
+class OpPoolRequest(ctypes.Structure):
+    """``op_pool_request``: the entries one ``op_forward_packed_pooled`` call reduces to a row per sequence, and its scratch."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("kind", ctypes.c_int32),
+        ("select", ctypes.POINTER(ctypes.c_uint8)),
+        ("out_dev", ctypes.c_void_p),
+        ("scratch_dev", ctypes.c_void_p),
+        ("scratch_bytes", ctypes.c_size_t),
+    ]
+
+
+# enum op_hidden_pool_kind, by the names HiddenRequest.pool takes
+POOL_KINDS = {"first": 0, "mean": 1}
+OP_HIDDEN_POOL_FIRST, OP_HIDDEN_POOL_MEAN = 0, 1
+
+
 class OpAttentionRequest(ctypes.Structure):
     """``op_attention_request``: the layer whose attention probabilities one ``op_attention_probs`` call writes."""
 
@@ -160,6 +180,21 @@ class OpAttentionRequest(ctypes.Structure):
         ("dtype", ctypes.c_int32),
         ("pad_width", ctypes.c_int32),
         ("hidden_dev", ctypes.c_void_p),
+        ("out_dev", ctypes.c_void_p),
+    ]
+
+
+class OpAttentionRowsRequest(ctypes.Structure):
+    """``op_attention_rows_request``: the layer and the query position per sequence of one ``op_attention_rows`` call."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("layer", ctypes.c_int32),
+        ("pad_width", ctypes.c_int32),
+        ("reduce_heads", ctypes.c_int32),
+        ("hidden_dev", ctypes.c_void_p),
+        ("query_pos_dev", ctypes.c_void_p),
+        ("query_pos_host", ctypes.c_void_p),
         ("out_dev", ctypes.c_void_p),
     ]
 
@@ -350,6 +385,13 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "op_forward_packed_hidden"):
         lib.op_forward_packed_hidden.restype = ci
         lib.op_forward_packed_hidden.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, cs, vp, ctypes.POINTER(OpHiddenRequest)]
+    if hasattr(lib, "op_forward_packed_pooled"):  # (additive to ABI 10)
+        lib.op_forward_packed_pooled.restype = ci
+        lib.op_forward_packed_pooled.argtypes = [vp, vp, vp, vp, ci, ci, ci, vp, vp, vp, vp, cs, vp, ctypes.POINTER(OpHiddenRequest),
+                                                 ctypes.POINTER(OpPoolRequest)]
+    if hasattr(lib, "op_attention_rows"):  # (additive to ABI 10; the workspace is op_attention_workspace_bytes)
+        lib.op_attention_rows.restype = ci
+        lib.op_attention_rows.argtypes = [vp, vp, vp, ci, ci, ci, ctypes.POINTER(OpAttentionRowsRequest), vp, cs, vp]
     if hasattr(lib, "op_attention_probs"):  # (additive to ABI 10: an older library loaded for an A/B has neither)
         lib.op_attention_workspace_bytes.restype = cs
         lib.op_attention_workspace_bytes.argtypes = [vp, ci, ci, ci]

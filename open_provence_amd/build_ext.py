@@ -30,11 +30,12 @@ _INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_f32.hip.h", CSRC / "o
 _PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
 _AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
 _LOSS = CSRC / "opk_loss.hip.h"  # the evaluation losses: fp64 terms, fixed-order reduction
+_POOL = CSRC / "opk_pool.hip.h"  # pooled hidden states: the reduction of the scratch entry, fixed-order fp64 mean
 _ASSEMBLE = CSRC / "opk_assemble.hip.h"  # prepared contexts: rows laid out on the device from a resident corpus
 
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
-    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_sets.h", CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, INCLUDE]),
+    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_sets.h", CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, _POOL, INCLUDE]),
     ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"], _INTERNAL),
     ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"], _INTERNAL),
     ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"], _INTERNAL),

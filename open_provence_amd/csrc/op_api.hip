@@ -18,6 +18,7 @@
 #include "op_internal.h"
 #include "op_sets.h"
 #include "opk_small.hip.h"
+#include "opk_pool.hip.h"
 #include "opk_loss.hip.h"
 #include "opk_padded.hip.h"
 #include "opk_tiled.hip.h"
@@ -333,12 +334,22 @@ int clear_lo(Launcher& L, u16* base, int unit, size_t n_pairs) {
   return L.end();
 }
 
-// A validated per-call hidden-state request (op_forward_packed_hidden): the output slot of every entry (-1: not selected)
+// A validated per-call hidden-state request (op_forward_packed_hidden): the output slot of every entry (-1: not selected);
+// and / or a validated pooled request (op_forward_packed_pooled): an entry it selects is stored into `scratch` (packed fp32
+// [total_tokens][H], one entry, reused by the next: the stream orders it), pooled from there, and copied from there into the
+// ordinary request's entry when that selects it too (the stores have one destination per launch).
 struct HiddenReq {
-  char* out;
-  int bf16, pad;
-  size_t entry_bytes;     // one entry: [total_tokens][H] or [n_seqs][pad][H] elements of the dtype
-  std::vector<int> slot;  // [num_layers + 1]
+  char* out = nullptr;
+  int bf16 = 0, pad = 0;
+  size_t entry_bytes = 0;  // one entry: [total_tokens][H] or [n_seqs][pad][H] elements of the dtype
+  std::vector<int> slot;   // [num_layers + 1]
+  int pool_kind = 0;       // opk::POOL_FIRST / POOL_MEAN
+  float* pool_out = nullptr;  // [n_pool_sel][n_seqs][H]
+  float* scratch = nullptr;
+  int n_seqs = 0, n_pool = 0;  // sequences of the batch, entries the pooled request selects
+  std::vector<int> pool_slot;  // [num_layers + 1], empty: no pooled request
+  bool pooled(int index) const { return !pool_slot.empty() && pool_slot[index] >= 0; }
+  bool full(int index) const { return !slot.empty() && slot[index] >= 0; }
 };
 
 struct AttnPlan {
@@ -516,17 +527,35 @@ struct ChunkPass {
   // first (entry N, post-norm convention).  Two launches store their entry from their own epilogue instead: the wave-pair
   // kernel (layer16p_hout_kernel; between two of its launches x is tiled) and the last whole-layer launch with the head fused,
   // which writes no x (rowgemm_hout_kernel).
+  // A pooled request (op_forward_packed_pooled) redirects the entries it selects to its scratch entry, packed fp32: the same
+  // stores, another destination.  hidden_pooled(index), behind the launch that stored the entry, reduces it to one row per
+  // sequence of this chunk and hands it on to the ordinary request's entry if that wants it too.
   void* hidden_entry(int index) const {
-    if (!hid || hid->slot[index] < 0) return nullptr;
+    if (!hid) return nullptr;
+    if (hid->pooled(index)) return hid->scratch;
+    if (!hid->full(index)) return nullptr;
     return hid->out + (size_t)hid->slot[index] * hid->entry_bytes;
+  }
+  int hidden_bf16(int index) const { return hid->pooled(index) ? 0 : hid->bf16; }
+  int hidden_pad(int index) const { return hid->pooled(index) ? 0 : hid->pad; }
+  int hidden_pooled(int index) {
+    if (!hid || !hid->pooled(index)) return OP_OK;
+    OP_TRY(L.begin(PK_CAPTURE));
+    hipLaunchKernelGGL(pool_hidden_kernel, dim3((unsigned)ns, (unsigned)((H + POOL_COLS - 1) / POOL_COLS)), dim3(256), 0, st, hid->scratch,
+                       cu_dev, s0, total_tokens, H, hid->pool_kind, hid->pool_out + (size_t)hid->pool_slot[index] * (size_t)hid->n_seqs * H);
+    if (hid->full(index))
+      hipLaunchKernelGGL(hidden_repack_kernel, dim3(row_blocks), dim3(256), 0, st, hid->scratch, H, r_pad, ws.row_tok, ws.row_seq,
+                         ws.row_pos, s0, hid->pad, hid->bf16, hid->out + (size_t)hid->slot[index] * hid->entry_bytes);
+    return L.end();
   }
   int hidden(int index, const float* ln = nullptr) {
     void* dst = hidden_entry(index);
     if (!dst) return OP_OK;
     OP_TRY(L.begin(PK_CAPTURE));
     hipLaunchKernelGGL(hidden_rows_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, ln, h->cfg.norm_eps, H, r_pad,
-                       ws.row_tok, ws.row_seq, ws.row_pos, s0, hid->pad, hid->bf16, dst);
-    return L.end();
+                       ws.row_tok, ws.row_seq, ws.row_pos, s0, hidden_pad(index), hidden_bf16(index), dst);
+    OP_TRY(L.end());
+    return hidden_pooled(index);
   }
 
   int attention(bool is_global) {
@@ -690,8 +719,8 @@ struct ChunkPass {
         if (lp.hid_out) {
           lp.row_tok = ws.row_tok;
           lp.row_seq = ws.row_seq;
-          lp.hid_bf16 = hid->bf16;
-          lp.hid_pad = hid->pad;
+          lp.hid_bf16 = hidden_bf16(li + 1);
+          lp.hid_pad = hidden_pad(li + 1);
           lp.hid_s0 = s0;
           hidden_stored = li + 1;
         }
@@ -732,8 +761,8 @@ struct ChunkPass {
         head_done = true;
         rl.hid_out = hidden_entry(h->N);  // (entry N from the head's epilogue: this launch writes no x)
         if (rl.hid_out) {
-          rl.hid_bf16 = hid->bf16;
-          rl.hid_pad = hid->pad;
+          rl.hid_bf16 = hidden_bf16(h->N);
+          rl.hid_pad = hidden_pad(h->N);
           rl.hid_s0 = s0;
         }
       }
@@ -1065,6 +1094,7 @@ struct ChunkPass {
   // final_norm + pruning head (unless the last whole-layer launch did it), ranking head
   int heads() {
     const int mean_pool = h->cfg.pooling == OP_POOL_MEAN ? 1 : 0;
+    if (head_done) OP_TRY(hidden_pooled(h->N));  // (entry N came from the last whole-layer launch's epilogue)
     if (!head_done) {
       // (before final_ln_prune_kernel: under mean pooling it writes the normalised rows over x)
       OP_TRY(hidden(h->N, h->cfg.prune_pre_final_norm ? nullptr : h->final_norm));
@@ -1100,6 +1130,7 @@ struct ChunkPass {
       // output of layer li = entry li + 1 (entry N is the head's input: heads() / the last whole-layer launch), unless the
       // wave-pair launch stored it from its epilogue
       if (li + 1 < h->N && hidden_stored != li + 1) OP_TRY(hidden(li + 1));
+      if (hidden_stored == li + 1) OP_TRY(hidden_pooled(li + 1));
     }
     return heads();
   }
@@ -2080,6 +2111,8 @@ static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32
       hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
       OP_HIP(h, hipMemsetAsync(rank_out, 0, (size_t)n_seqs * h->nl * sizeof(float), st));
     }
+    if (n_seqs > 0 && hid && hid->n_pool > 0)  // only empty sequences: every pooled row is +0.0
+      OP_HIP(h, hipMemsetAsync(hid->pool_out, 0, (size_t)hid->n_pool * n_seqs * h->H * sizeof(float), reinterpret_cast<hipStream_t>(hip_stream)));
     return OP_OK;
   }
   if (!ids_dev || !cu_dev || !prune_out || !rank_out || !workspace)
@@ -2132,6 +2165,8 @@ static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32
     } else {
       // only empty sequences in this chunk
       OP_HIP(h, hipMemsetAsync(rank_out + (size_t)s0 * h->nl, 0, (size_t)(s1 - s0) * h->nl * sizeof(float), stream));
+      for (int e = 0; hid && e < hid->n_pool; ++e)  // (their pooled rows: +0.0)
+        OP_HIP(h, hipMemsetAsync(hid->pool_out + ((size_t)e * n_seqs + s0) * h->H, 0, (size_t)(s1 - s0) * h->H * sizeof(float), stream));
     }
     s0 = s1;
   }
@@ -2145,38 +2180,85 @@ int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_de
                              workspace, workspace_bytes, hip_stream, nullptr);
 }
 
-int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
-                             int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
-                             void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req) {
-  if (req) {  // (the request's own fields first: none of them needs the handle)
+// op_forward_packed_hidden / op_forward_packed_pooled: the two requests checked (their own fields first: none of them needs the
+// handle), then one forward with whatever they select
+static int forward_packed_requests(const char* what, op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in,
+                                   int n_seqs, int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
+                                   void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req,
+                                   const op_pool_request* pool, bool pool_required) {
+  if (req) {
     if (req->struct_bytes != sizeof(op_hidden_request))
-      return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: op_hidden_request.struct_bytes is %u, expected %zu", req->struct_bytes,
+      return fail(h, OP_ERR_INVALID, "%s: op_hidden_request.struct_bytes is %u, expected %zu", what, req->struct_bytes,
                   sizeof(op_hidden_request));
     if (req->dtype != OP_HIDDEN_F32 && req->dtype != OP_HIDDEN_BF16)
-      return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: unknown dtype %d", req->dtype);
+      return fail(h, OP_ERR_INVALID, "%s: unknown dtype %d", what, req->dtype);
     if (req->pad_width < 0 || (req->pad_width > 0 && req->pad_width < max_seqlen))
-      return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: pad_width %d below max_seqlen %d", req->pad_width, max_seqlen);
+      return fail(h, OP_ERR_INVALID, "%s: pad_width %d below max_seqlen %d", what, req->pad_width, max_seqlen);
   }
-  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_forward_packed_hidden: NULL handle");
-  if (!req)
+  if (pool_required && !pool) return fail(h, OP_ERR_INVALID, "%s: the pooled request is NULL", what);
+  if (pool) {
+    if (pool->struct_bytes != sizeof(op_pool_request))
+      return fail(h, OP_ERR_INVALID, "%s: op_pool_request.struct_bytes is %u, expected %zu", what, pool->struct_bytes, sizeof(op_pool_request));
+    if (pool->kind != OP_HIDDEN_POOL_FIRST && pool->kind != OP_HIDDEN_POOL_MEAN)
+      return fail(h, OP_ERR_INVALID, "%s: unknown pooling kind %d", what, pool->kind);
+    if ((reinterpret_cast<uintptr_t>(pool->scratch_dev) & 15) != 0)
+      return fail(h, OP_ERR_INVALID, "%s: scratch_dev must be 16-byte aligned", what);
+  }
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "%s: NULL handle", what);
+  if (!req && !pool)
     return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
                                workspace, workspace_bytes, hip_stream, nullptr);
   HiddenReq hid;
-  hid.out = reinterpret_cast<char*>(req->out_dev);
-  hid.bf16 = req->dtype == OP_HIDDEN_BF16 ? 1 : 0;
-  hid.pad = req->pad_width;
-  hid.slot.assign((size_t)h->N + 1, -1);
   int n_sel = 0;
-  for (int i = 0; i <= h->N; ++i)
-    if (!req->select || req->select[i]) hid.slot[i] = n_sel++;
-  const size_t rows = hid.pad > 0 ? (size_t)std::max(n_seqs, 0) * (size_t)hid.pad : (size_t)std::max(total_tokens, 0);
-  if (rows > (size_t)INT32_MAX)  // (destination rows are 32-bit indices in the kernels' epilogues)
-    return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: %zu destination rows per entry exceed 2^31 - 1", rows);
-  hid.entry_bytes = rows * (size_t)h->H * (hid.bf16 ? 2 : 4);
-  if (n_sel > 0 && hid.entry_bytes > 0 && !hid.out)
-    return fail(h, OP_ERR_INVALID, "op_forward_packed_hidden: out_dev is NULL with %d entries selected", n_sel);
+  if (req) {
+    hid.out = reinterpret_cast<char*>(req->out_dev);
+    hid.bf16 = req->dtype == OP_HIDDEN_BF16 ? 1 : 0;
+    hid.pad = req->pad_width;
+    hid.slot.assign((size_t)h->N + 1, -1);
+    for (int i = 0; i <= h->N; ++i)
+      if (!req->select || req->select[i]) hid.slot[i] = n_sel++;
+    const size_t rows = hid.pad > 0 ? (size_t)std::max(n_seqs, 0) * (size_t)hid.pad : (size_t)std::max(total_tokens, 0);
+    if (rows > (size_t)INT32_MAX)  // (destination rows are 32-bit indices in the kernels' epilogues)
+      return fail(h, OP_ERR_INVALID, "%s: %zu destination rows per entry exceed 2^31 - 1", what, rows);
+    hid.entry_bytes = rows * (size_t)h->H * (hid.bf16 ? 2 : 4);
+    if (n_sel > 0 && hid.entry_bytes > 0 && !hid.out)
+      return fail(h, OP_ERR_INVALID, "%s: out_dev is NULL with %d entries selected", what, n_sel);
+    if (n_sel == 0) hid.slot.clear();
+  }
+  if (pool) {
+    hid.pool_kind = pool->kind == OP_HIDDEN_POOL_MEAN ? POOL_MEAN : POOL_FIRST;
+    hid.pool_out = pool->out_dev;
+    hid.scratch = reinterpret_cast<float*>(pool->scratch_dev);
+    hid.n_seqs = std::max(n_seqs, 0);
+    hid.pool_slot.assign((size_t)h->N + 1, -1);
+    for (int i = 0; i <= h->N; ++i)
+      if (!pool->select || pool->select[i]) hid.pool_slot[i] = hid.n_pool++;
+    const size_t scratch_need = (size_t)std::max(total_tokens, 0) * (size_t)h->H * sizeof(float);
+    if (hid.n_pool > 0 && n_seqs > 0 && !hid.pool_out)
+      return fail(h, OP_ERR_INVALID, "%s: the pooled out_dev is NULL with %d entries selected", what, hid.n_pool);
+    if (hid.n_pool > 0 && n_seqs > 0 && scratch_need > 0 && !hid.scratch)
+      return fail(h, OP_ERR_INVALID, "%s: scratch_dev is NULL", what);
+    if (hid.n_pool > 0 && n_seqs > 0 && pool->scratch_bytes < scratch_need)
+      return fail(h, OP_ERR_INVALID, "%s: scratch has %zu bytes, one packed fp32 entry needs %zu", what, (size_t)pool->scratch_bytes, scratch_need);
+    if (hid.n_pool == 0) hid.pool_slot.clear();
+  }
   return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
-                             workspace, workspace_bytes, hip_stream, n_sel > 0 ? &hid : nullptr);
+                             workspace, workspace_bytes, hip_stream, (n_sel > 0 || hid.n_pool > 0) ? &hid : nullptr);
+}
+
+int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
+                             int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
+                             void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req) {
+  return forward_packed_requests("op_forward_packed_hidden", h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out,
+                                 rank_out, keep_prob, workspace, workspace_bytes, hip_stream, req, nullptr, false);
+}
+
+int op_forward_packed_pooled(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
+                             int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
+                             void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req,
+                             const op_pool_request* pool) {
+  return forward_packed_requests("op_forward_packed_pooled", h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out,
+                                 rank_out, keep_prob, workspace, workspace_bytes, hip_stream, req, pool, true);
 }
 
 // ---- op_attention_probs: the softmax probabilities of one layer, a side pass over that layer's input hidden state ----------
@@ -2214,6 +2296,68 @@ size_t op_attention_workspace_bytes(const op_handle* h, int n_seqs, int total_to
   return ws.bytes;
 }
 
+// The part op_attention_probs and op_attention_rows share, after their own checks: workspace, chunks of sequences as the forward
+// takes them, and per chunk the row map, the state's rows, LayerNorm(attn_norm), q | k with RoPE; `tail(ws, s0, ns, is_global)`
+// then enqueues the call's own kernel over the chunk's q and k.
+extern "C++" {
+template <typename Tail>
+static int attention_side_pass(op_handle* h, const char* what, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs, int total_tokens,
+                               int max_seqlen, int li, const float* hidden_dev, void* workspace, size_t workspace_bytes, hipStream_t stream,
+                               Tail&& tail) {
+  if (!cu_dev || !workspace) return fail(h, OP_ERR_INVALID, "%s: NULL buffer", what);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  const size_t need = op_attention_workspace_bytes(h, n_seqs, total_tokens, max_seqlen);
+  if (workspace_bytes < need) return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, need);
+
+  std::vector<int32_t> cu_copy;
+  const int32_t* cu = nullptr;
+  OP_TRY(host_cu_seqlens(h, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, stream, cu_copy, &cu));
+
+  const int H = h->H;
+  const bool is_global = h->cfg.layer_is_global[li] != 0;
+  const float* attn_norm = li != 0 ? h->layers[li].attn_norm : nullptr;  // layer 0: the identity, as in the forward
+  const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
+  AttnProbsWorkspace ws;
+  carve_attention(h, reinterpret_cast<char*>(workspace), align_up(cap + 64, 256), n_seqs, ws);
+
+  int s0 = 0;
+  while (s0 < n_seqs) {  // chunks of sequences, as the forward takes them
+    int rows = 0, max_len = 0;
+    const int s1 = next_chunk(cu, s0, n_seqs, cap, &rows, &max_len);
+    if (rows > cap) return fail(h, OP_ERR_WORKSPACE, "internal: chunk of %d rows exceeds capacity %d", rows, cap);
+    const int ns = s1 - s0;
+    const int r_pad = align_up(std::max(rows, 1), GEMM_BM);
+    // row map; the state's rows (zero rows where the map holds no token); LayerNorm; q | k with RoPE, q scaled
+    hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, stream, cu_dev, s0, ns, ROW_ALIGN, ROW_ALIGN, ws.roff);
+    hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, stream, cu_dev, s0, ns, ws.roff, r_pad,
+                       ws.row_seq, ws.row_pos, ws.row_tok);
+    opl::launch_attn_probs_gather(stream, hidden_dev, ws.row_tok, H, r_pad, ws.x);
+    if (attn_norm) opl::launch_f32_ln(stream, ws.x, attn_norm, h->cfg.norm_eps, H, r_pad, ws.ln);
+    F32GemmParams gp;
+    memset(&gp, 0, sizeof(gp));
+    gp.a = attn_norm ? ws.ln : ws.x;
+    gp.w = reinterpret_cast<const float*>(h->layers[li].pack[W_QKV][PF_F32]);
+    gp.K = H;
+    gp.n_tiles = 2 * H / GEMM_BN;  // the q and k column tiles only
+    gp.m_tiles = r_pad / GEMM_BM;
+    gp.o0 = ws.q;
+    gp.o1 = ws.k;
+    gp.ld_out = H;
+    gp.hidden = H;
+    gp.inter = h->I;
+    gp.row_pos = ws.row_pos;
+    gp.rope_cos = h->rope_cos[is_global ? 1 : 0];
+    gp.rope_sin = h->rope_sin[is_global ? 1 : 0];
+    gp.max_pos = h->max_pos;
+    if (!opl::launch_f32_gemm(stream, gp, F32_EPI_QKV)) return fail(h, OP_ERR_UNSUPPORTED, "internal: no fp32 GEMM epilogue %d", F32_EPI_QKV);
+    tail(ws, s0, ns, is_global);
+    OP_HIP(h, hipGetLastError());
+    s0 = s1;
+  }
+  return OP_OK;
+}
+}  // extern "C++"
+
 int op_attention_probs(op_handle* h, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs, int total_tokens, int max_seqlen,
                        const op_attention_request* req, void* workspace, size_t workspace_bytes, void* hip_stream) {
   // (the request's own fields first: none of them needs the handle)
@@ -2247,69 +2391,82 @@ int op_attention_probs(op_handle* h, const int32_t* cu_dev, const int32_t* cu_ho
     OP_HIP(h, hipMemsetAsync(out, 0, (size_t)n_seqs * mat_elems * sizeof(float), stream));
     return OP_OK;
   }
-  if (!cu_dev || !workspace) return fail(h, OP_ERR_INVALID, "op_attention_probs: NULL buffer");
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-  const size_t need = op_attention_workspace_bytes(h, n_seqs, total_tokens, max_seqlen);
-  if (workspace_bytes < need) return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, need);
+  return attention_side_pass(h, "op_attention_probs", cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, req->layer, req->hidden_dev,
+                             workspace, workspace_bytes, stream, [&](const AttnProbsWorkspace& ws, int s0, int ns, bool is_global) {
+                               AttnProbsParams ap;
+                               ap.q = ws.q;
+                               ap.k = ws.k;
+                               ap.out = out;
+                               ap.cu = cu_dev;
+                               ap.s0 = s0;
+                               ap.roff = ws.roff;
+                               ap.H = h->H;
+                               ap.num_heads = h->nh;
+                               ap.window = is_global ? -1 : h->cfg.local_attention / 2;
+                               ap.width = width;
+                               ap.wide = (width % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
+                               opl::launch_attn_probs(stream, ap, ns);
+                             });
+}
 
-  std::vector<int32_t> cu_copy;
-  const int32_t* cu = nullptr;
-  OP_TRY(host_cu_seqlens(h, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, stream, cu_copy, &cu));
+// ---- op_attention_rows: one query row per sequence of op_attention_probs' matrices, per head or as the mean over heads --------
+int op_attention_rows(op_handle* h, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs, int total_tokens, int max_seqlen,
+                      const op_attention_rows_request* req, void* workspace, size_t workspace_bytes, void* hip_stream) {
+  // (the request's own fields first: none of them needs the handle)
+  if (!req) return fail(h, OP_ERR_INVALID, "op_attention_rows: the request is NULL");
+  if (req->struct_bytes != sizeof(op_attention_rows_request))
+    return fail(h, OP_ERR_INVALID, "op_attention_rows: op_attention_rows_request.struct_bytes is %u, expected %zu", req->struct_bytes,
+                sizeof(op_attention_rows_request));
+  if (req->reduce_heads != 0 && req->reduce_heads != 1)
+    return fail(h, OP_ERR_INVALID, "op_attention_rows: reduce_heads %d is neither 0 nor 1", req->reduce_heads);
+  if (n_seqs < 0 || total_tokens < 0 || max_seqlen < 0) return fail(h, OP_ERR_INVALID, "op_attention_rows: negative size");
+  const bool empty = n_seqs == 0 || total_tokens == 0;
+  if (req->pad_width < 0 || req->pad_width < max_seqlen || (!empty && req->pad_width == 0))
+    return fail(h, OP_ERR_INVALID, "op_attention_rows: pad_width %d below max_seqlen %d", req->pad_width, max_seqlen);
+  if (!empty && !req->hidden_dev) return fail(h, OP_ERR_INVALID, "op_attention_rows: hidden_dev is NULL");
+  if (!empty && !req->out_dev) return fail(h, OP_ERR_INVALID, "op_attention_rows: out_dev is NULL");
+  if (req->query_pos_host && !req->query_pos_dev)
+    return fail(h, OP_ERR_INVALID, "op_attention_rows: query_pos_host without query_pos_dev");
+  if (req->query_pos_host)
+    for (int s = 0; s < n_seqs; ++s)
+      if (req->query_pos_host[s] < 0)
+        return fail(h, OP_ERR_INVALID, "op_attention_rows: query position %d of sequence %d is negative", req->query_pos_host[s], s);
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_attention_rows: NULL handle");
+  if (req->layer < 0 || req->layer >= h->N)
+    return fail(h, OP_ERR_INVALID, "op_attention_rows: layer %d outside 0 .. %d", req->layer, h->N - 1);
+  if (!h->f32_packs)
+    return fail(h, OP_ERR_UNSUPPORTED, "op_attention_rows: the pass needs the fp32 weight packs: create the handle with OP_FLAG_F32_PACKS");
+  const bool head_mean = req->reduce_heads != 0;
+  if (head_mean && h->nh > AR_MAX_HEADS)
+    return fail(h, OP_ERR_UNSUPPORTED, "op_attention_rows: reduce_heads with %d heads (at most %d)", h->nh, AR_MAX_HEADS);
+  if (op_weights_ready(h) != OP_OK) return OP_ERR_STATE;
 
-  const int li = req->layer, H = h->H;
-  const bool is_global = h->cfg.layer_is_global[li] != 0;
-  const float* attn_norm = li != 0 ? h->layers[li].attn_norm : nullptr;  // layer 0: the identity, as in the forward
-  const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
-  AttnProbsWorkspace ws;
-  carve_attention(h, reinterpret_cast<char*>(workspace), align_up(cap + 64, 256), n_seqs, ws);
-
-  int s0 = 0;
-  while (s0 < n_seqs) {  // chunks of sequences, as the forward takes them
-    int rows = 0, max_len = 0;
-    const int s1 = next_chunk(cu, s0, n_seqs, cap, &rows, &max_len);
-    if (rows > cap) return fail(h, OP_ERR_WORKSPACE, "internal: chunk of %d rows exceeds capacity %d", rows, cap);
-    const int ns = s1 - s0;
-    const int r_pad = align_up(std::max(rows, 1), GEMM_BM);
-    // row map; the state's rows (zero rows where the map holds no token); LayerNorm; q | k with RoPE, q scaled
-    hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, stream, cu_dev, s0, ns, ROW_ALIGN, ROW_ALIGN, ws.roff);
-    hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, stream, cu_dev, s0, ns, ws.roff, r_pad,
-                       ws.row_seq, ws.row_pos, ws.row_tok);
-    opl::launch_attn_probs_gather(stream, req->hidden_dev, ws.row_tok, H, r_pad, ws.x);
-    if (attn_norm) opl::launch_f32_ln(stream, ws.x, attn_norm, h->cfg.norm_eps, H, r_pad, ws.ln);
-    F32GemmParams gp;
-    memset(&gp, 0, sizeof(gp));
-    gp.a = attn_norm ? ws.ln : ws.x;
-    gp.w = reinterpret_cast<const float*>(h->layers[li].pack[W_QKV][PF_F32]);
-    gp.K = H;
-    gp.n_tiles = 2 * H / GEMM_BN;  // the q and k column tiles only
-    gp.m_tiles = r_pad / GEMM_BM;
-    gp.o0 = ws.q;
-    gp.o1 = ws.k;
-    gp.ld_out = H;
-    gp.hidden = H;
-    gp.inter = h->I;
-    gp.row_pos = ws.row_pos;
-    gp.rope_cos = h->rope_cos[is_global ? 1 : 0];
-    gp.rope_sin = h->rope_sin[is_global ? 1 : 0];
-    gp.max_pos = h->max_pos;
-    if (!opl::launch_f32_gemm(stream, gp, F32_EPI_QKV)) return fail(h, OP_ERR_UNSUPPORTED, "internal: no fp32 GEMM epilogue %d", F32_EPI_QKV);
-    AttnProbsParams ap;
-    ap.q = ws.q;
-    ap.k = ws.k;
-    ap.out = out;
-    ap.cu = cu_dev;
-    ap.s0 = s0;
-    ap.roff = ws.roff;
-    ap.H = H;
-    ap.num_heads = h->nh;
-    ap.window = is_global ? -1 : h->cfg.local_attention / 2;
-    ap.width = width;
-    ap.wide = (width % 4 == 0 && (reinterpret_cast<uintptr_t>(out) & 15) == 0) ? 1 : 0;
-    opl::launch_attn_probs(stream, ap, ns);
-    OP_HIP(h, hipGetLastError());
-    s0 = s1;
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  const int width = req->pad_width;
+  const size_t row_elems = (head_mean ? (size_t)1 : (size_t)h->nh) * (size_t)width;  // one sequence
+  float* out = req->out_dev;
+  if (n_seqs == 0 || width == 0) return OP_OK;
+  if (total_tokens == 0) {  // only empty sequences: no position lies inside one
+    OP_HIP(h, hipMemsetAsync(out, 0, (size_t)n_seqs * row_elems * sizeof(float), stream));
+    return OP_OK;
   }
-  return OP_OK;
+  return attention_side_pass(h, "op_attention_rows", cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, req->layer, req->hidden_dev,
+                             workspace, workspace_bytes, stream, [&](const AttnProbsWorkspace& ws, int s0, int ns, bool is_global) {
+                               AttnRowsParams ar;
+                               ar.q = ws.q;
+                               ar.k = ws.k;
+                               ar.out = out;
+                               ar.cu = cu_dev;
+                               ar.qpos = req->query_pos_dev;
+                               ar.s0 = s0;
+                               ar.roff = ws.roff;
+                               ar.H = h->H;
+                               ar.num_heads = h->nh;
+                               ar.window = is_global ? -1 : h->cfg.local_attention / 2;
+                               ar.width = width;
+                               opl::launch_attn_rows(stream, ar, ns, head_mean);
+                             });
 }
 
 int op_pack_padded(op_handle* h, const void* ids_dev, int ids_dtype, const void* mask_dev, int mask_dtype, int n_rows, int width,

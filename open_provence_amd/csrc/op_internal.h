@@ -112,6 +112,9 @@ void launch_f32_rank_head(hipStream_t st, int n_seqs, const float* cls, const fl
 void launch_attn_probs_gather(hipStream_t st, const float* packed, const int32_t* row_tok, int H, int r_pad, float* x);
 // grid: (64-query blocks of p.width, heads, the n_seqs sequences from p.s0 on); every element of their matrices is written
 void launch_attn_probs(hipStream_t st, const opk::AttnProbsParams& p, int n_seqs);
+// op_attention_rows: one query row of the n_seqs sequences from p.s0 on, per head (grid: heads x sequences) or as the mean over
+// heads (grid: sequences; p.num_heads <= opk::AR_MAX_HEADS); every element of their rows is written
+void launch_attn_rows(hipStream_t st, const opk::AttnRowsParams& p, int n_seqs, bool head_mean);
 
 // op_debug_primitive (opk_probe.hip.h; op_launch_probe.hip).  probe_group_size: the number of input elements one record of
 // `kind` (enum op_probe_kind) takes, 0 for an unknown kind.  launch_probe: kind, mode and n % group already checked, n > 0.

@@ -51,11 +51,26 @@ class HiddenRequest:
     num_layers = the pruning head's input: the ``final_norm`` output, or the raw last layer under ``prune_pre_final_norm``);
     None = all of them.  ``dtype``: ``torch.float32`` or ``torch.bfloat16`` (the fp32 state rounded to nearest even).
     ``pad_width``: 0 = packed ``[n_sel, total_tokens, H]``; > 0 = padded ``[n_sel, n_seqs, pad_width, H]`` (zeros beyond each
-    sequence's length; at least ``max_seqlen``)."""
+    sequence's length; at least ``max_seqlen``).
+
+    ``pool`` (``op_forward_packed_pooled``): None = the states themselves; ``"first"`` = the row of token 0 of each sequence (what
+    ``classifier_pooling="cls"`` reads, bit-identical to that row of the full entry); ``"mean"`` = the mean over the sequence's
+    tokens (fp64 in a fixed order, rounded once: the same bits whatever the batch around the sequence).  The result is then fp32
+    ``[n_sel, n_seqs, H]`` -- a row of zeros for an empty sequence -- reduced on the device from ONE scratch entry, so ``dtype``
+    must stay ``torch.float32`` and ``pad_width`` 0."""
 
     layers: "Sequence[int] | None" = None
     dtype: torch.dtype = torch.float32
     pad_width: int = 0
+    pool: "str | None" = None
+
+    def __post_init__(self) -> None:
+        if self.pool is None:
+            return
+        if self.pool not in _lib.POOL_KINDS:
+            raise ValueError(f"HiddenRequest.pool must be None, 'first' or 'mean', got {self.pool!r}")
+        if self.dtype != torch.float32 or int(self.pad_width) != 0:
+            raise ValueError("a pooled HiddenRequest is fp32 [n_sel, n_seqs, H]: dtype must be torch.float32 and pad_width 0")
 
 
 @dataclass(frozen=True)
@@ -65,10 +80,33 @@ class AttentionRequest:
 
     ``layers``: the layers 0 .. num_layers - 1 to return; None = all of them.  ``pad_width``: rows and columns of every
     ``[B, heads, pad_width, pad_width]`` fp32 tensor (zeros at masked keys, beyond each sequence's length and on padded query
-    rows); 0 = ``max_seqlen``, otherwise at least that."""
+    rows); 0 = ``max_seqlen``, otherwise at least that.
+
+    ``query`` (``op_attention_rows``): None = the whole matrices; ``"first"`` = the row of query position 0 of each sequence; an
+    integer tensor ``[n_seqs]`` = one query position per sequence (on the host or on the encoder's device; a position at or
+    beyond a sequence's length gives a row of zeros, a negative one is refused where it is visible on the host).  Every tensor is
+    then ``[B, heads, pad_width]``, bit-identical to that row of the whole matrix, or with ``reduce_heads=True`` ``[B, pad_width]``,
+    the mean over heads (fp64 in head order, rounded once).  ``reduce_heads`` needs a ``query``."""
 
     layers: "Sequence[int] | None" = None
     pad_width: int = 0
+    query: "str | torch.Tensor | None" = None
+    reduce_heads: bool = False
+
+    def __post_init__(self) -> None:
+        query = self.query
+        if isinstance(query, str):
+            if query != "first":
+                raise ValueError(f"AttentionRequest.query must be None, 'first' or an integer tensor [n_seqs], got {query!r}")
+        elif query is not None:
+            if not isinstance(query, torch.Tensor) or query.ndim != 1 or query.dtype not in (torch.int32, torch.int64):
+                raise ValueError("AttentionRequest.query must be None, 'first' or an int32 / int64 tensor [n_seqs]")
+            if query.device.type == "cpu" and query.numel() and int(query.min()) < 0:
+                raise ValueError("AttentionRequest.query holds a negative position")
+        if not isinstance(self.reduce_heads, (bool, int)) or int(self.reduce_heads) not in (0, 1):
+            raise ValueError("AttentionRequest.reduce_heads must be a bool")
+        if self.reduce_heads and query is None:
+            raise ValueError("AttentionRequest.reduce_heads needs a query (the head mean of whole matrices is not offered)")
 
 
 class PackedCall(NamedTuple):
@@ -91,6 +129,7 @@ class PackedCall(NamedTuple):
     # an audit's reference call: `ws` is checked against the kernel set selected WHEN THE CALL IS LAUNCHED and replaced if that set
     # needs more (op_workspace_bytes depends on the selection: kernel set "fp32" has fp32 planes of its own)
     size_ws_at_launch: bool = False
+    pool_req: "_lib.OpPoolRequest | None" = None  # a pooled hidden request: op_forward_packed_pooled
 
 
 def parse_precision(precision: "str | Mapping[str, int]") -> tuple[int, list[int]]:
@@ -498,7 +537,7 @@ class HipEncoder:
         return bool(changed.value)
 
     def forward_packed_checked(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None, ids_host=None,
-                               attentions=None):
+                               attentions=None, pooled=None):
         """``forward_packed`` + the range guard: on kernel sets 3 / 4 the outputs are tested for NaN / Inf (one device
         reduction, one synchronisation) and a non-finite batch is repeated on the (hi, lo) bf16 sets.  On those sets
         nothing is tested: whatever comes out is what the reference's arithmetic gives.  With a ``hidden`` request the
@@ -506,6 +545,8 @@ class HipEncoder:
         ``attentions`` request its last element is the list of that forward's attention probabilities."""
 
         extra = {} if attentions is None else {"attentions": attentions}
+        if pooled is not None:  # (a repeated batch repeats its pooled request as it repeats a full one)
+            extra["pooled"] = pooled
         out = self.forward_packed(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=keep_prob, hidden=hidden, ids_host=ids_host, **extra)
         if self.f8_active():
             prune, rank = out[0], out[1]
@@ -663,6 +704,7 @@ class HipEncoder:
         hidden: "HiddenRequest | None" = None,
         ids_host: "np.ndarray | None" = None,
         attentions: "AttentionRequest | None" = None,
+        pooled: "HiddenRequest | None" = None,
     ) -> tuple[torch.Tensor, ...]:
         """``ids[T]`` / ``cu_seqlens[B+1]`` int32 on this device -> (prune_logits[T, 2], rank_logits[B, nl]) fp32.
         ``keep_prob`` (optional, fp32 ``[T]`` on this device) additionally receives
@@ -676,7 +718,12 @@ class HipEncoder:
         probabilities ``[B, heads, W, W]`` fp32.  The forward then runs with a packed fp32 hidden request for those layers'
         inputs (merged with the caller's ``hidden`` request, whose states are laid out from the merged ones) and
         ``op_attention_probs`` runs once per layer behind it on the same stream; logits and hidden states are bit-identical to
-        those of the same call without the request.
+        those of the same call without the request.  With ``AttentionRequest(query=...)`` the list holds one query row per
+        sequence, ``[B, heads, W]`` or ``[B, W]`` (``op_attention_rows``).
+
+        A ``hidden`` request with ``pool`` set returns ``[n_sel, B, H]`` in the place of the states.  ``pooled`` (a
+        :class:`HiddenRequest` with ``pool`` set) is a pooled request that rides on the same call BESIDE an ordinary ``hidden``
+        request: the result is then ``(prune, rank, hidden_states, pooled_states[, attentions])``.
 
         Asynchronous on the current torch stream of ``self.device`` (a forward that is audited synchronises it once)."""
 
@@ -686,10 +733,17 @@ class HipEncoder:
             )
             capture_ptr = ctypes.c_void_p(self._capture.data_ptr())
             _lib.check(self.lib, self._handle, self.lib.op_debug_capture_hidden(self._handle, capture_ptr), "capture")
+        if hidden is not None and isinstance(hidden, HiddenRequest) and hidden.pool is not None:
+            if pooled is not None:
+                raise ValueError("two pooled requests: pass the ordinary request as hidden= and the pooled one as pooled=")
+            hidden, pooled = None, hidden
+        if pooled is not None and (not isinstance(pooled, HiddenRequest) or pooled.pool is None):
+            raise ValueError("pooled must be a HiddenRequest with pool='first' or pool='mean'")
         if attentions is not None:
-            return self._forward_with_attentions(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host, attentions)
-        call, states = self._forward(None, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host)
-        return (call.prune, call.rank) if states is None else (call.prune, call.rank, states)
+            return self._forward_with_attentions(ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host, attentions, pooled)
+        call, states, pooled_states = self._forward(None, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host,
+                                                    pooled=pooled)
+        return (call.prune, call.rank) + tuple(t for t in (states, pooled_states) if t is not None)
 
     # -- attention probabilities: a side pass over the hidden states the forward hands out ---------------------------------------
     def _require_attention_outputs(self) -> None:
@@ -698,8 +752,9 @@ class HipEncoder:
         if not hasattr(self.lib, "op_attention_probs"):
             raise _lib.HipLibraryError("this library has no op_attention_probs")
 
-    def _forward_with_attentions(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host, attentions):
-        """One forward with the merged hidden request, then ``op_attention_probs`` per requested layer."""
+    def _forward_with_attentions(self, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, hidden, ids_host, attentions, pooled=None):
+        """One forward with the merged hidden request, then ``op_attention_probs`` (``attentions.query``: ``op_attention_rows``) per
+        requested layer."""
 
         if not isinstance(attentions, AttentionRequest):
             raise TypeError("attentions must be an AttentionRequest")
@@ -719,19 +774,25 @@ class HipEncoder:
             self._hidden_request(hidden, 0, 0, max_seqlen)
         # hidden_states[i] is the input of layer i: one packed fp32 request for every entry either side needs
         merged = sorted(set(layers) | set(own or ()))
-        call, states = self._forward(None, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob,
-                                     HiddenRequest(layers=merged, dtype=torch.float32, pad_width=0), ids_host)
+        call, states, pooled_states = self._forward(None, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob,
+                                                    HiddenRequest(layers=merged, dtype=torch.float32, pad_width=0), ids_host, pooled=pooled)
         slot = {entry: k for k, entry in enumerate(merged)}
-        probs = [self.attention_probs(states[slot[i]], i, cu_seqlens, call.cu_host, max_seqlen, width) for i in layers]
+        if attentions.query is None:
+            probs = [self.attention_probs(states[slot[i]], i, cu_seqlens, call.cu_host, max_seqlen, width) for i in layers]
+        else:
+            query = None if isinstance(attentions.query, str) else attentions.query
+            probs = [self.attention_rows(states[slot[i]], i, cu_seqlens, call.cu_host, max_seqlen, width, query=query,
+                                         reduce_heads=bool(attentions.reduce_heads)) for i in layers]
+        tail = (probs,) if pooled_states is None else (pooled_states, probs)
         if own is None:
-            return call.prune, call.rank, probs
+            return (call.prune, call.rank) + tail
         mine = states if own == merged else states[[slot[i] for i in own]]
         if hidden.pad_width > 0:  # (the layout the kernels give a padded request: zeros beyond each sequence's length)
             from .packing import unpack_to_padded
 
             mine = torch.stack([unpack_to_padded(entry, call.cu_host, int(hidden.pad_width)) for entry in mine]) if len(own) else \
                 mine.new_zeros((0, call.n_seqs, int(hidden.pad_width), self.dims.hidden_size))
-        return call.prune, call.rank, mine.to(hidden.dtype), probs
+        return (call.prune, call.rank, mine.to(hidden.dtype)) + tail
 
     def attention_probs(self, hidden_packed: torch.Tensor, layer: int, cu_seqlens: torch.Tensor, cu_seqlens_host: np.ndarray,
                         max_seqlen: int, pad_width: int = 0) -> torch.Tensor:
@@ -782,12 +843,81 @@ class HipEncoder:
         _lib.check(self.lib, self._handle, code, "op_attention_probs")
         return out
 
+    def attention_rows(self, hidden_packed: torch.Tensor, layer: int, cu_seqlens: torch.Tensor, cu_seqlens_host: np.ndarray,
+                       max_seqlen: int, pad_width: int = 0, query: "torch.Tensor | None" = None, reduce_heads: bool = False) -> torch.Tensor:
+        """One query row per sequence of :meth:`attention_probs`' matrices, without the matrices (``op_attention_rows``; the same
+        inputs, arithmetic and workspace).  ``query``: an int32 / int64 tensor ``[B]`` of query positions, on the host (negative
+        positions are refused) or on this device; None = position 0.  -> ``[B, heads, W]`` fp32, ``out[s, h, j]`` bit-identical to
+        ``attention_probs(...)[s, h, query[s], j]``, or with ``reduce_heads`` ``[B, W]``: the mean over heads (fp64 in head order,
+        rounded once).  Every element is written: a position at or beyond a sequence's length gives a row of zeros.
+        Asynchronous on the current torch stream."""
+
+        self._require_attention_outputs()
+        if not hasattr(self.lib, "op_attention_rows"):
+            raise _lib.HipLibraryError("this library has no op_attention_rows")
+        H, max_seqlen = self.dims.hidden_size, int(max_seqlen)
+        if (hidden_packed.dtype != torch.float32 or hidden_packed.device != self.device or hidden_packed.ndim != 2
+                or hidden_packed.shape[1] != H or not hidden_packed.is_contiguous()):
+            raise ValueError(f"hidden_packed must be a contiguous fp32 [total_tokens, {H}] tensor on {self.device}")
+        if cu_seqlens.dtype != torch.int32 or cu_seqlens.device != self.device:
+            raise ValueError(f"cu_seqlens must be int32 on {self.device}")
+        if not 0 <= int(layer) < self.dims.num_layers:
+            raise ValueError(f"layer must lie in 0 .. {self.dims.num_layers - 1}")
+        total, n_seqs = int(hidden_packed.shape[0]), int(cu_seqlens.numel()) - 1
+        width = int(pad_width) or max_seqlen
+        if width < max_seqlen:
+            raise ValueError(f"pad_width must be 0 (= max_seqlen) or at least max_seqlen ({max_seqlen}), got {width}")
+        cu_host = np.ascontiguousarray(cu_seqlens_host, dtype=np.int32)
+        if cu_host.shape[0] != n_seqs + 1:
+            raise ValueError("cu_seqlens_host length mismatch")
+        query_dev, query_host = None, None
+        if query is not None:
+            if not isinstance(query, torch.Tensor) or query.ndim != 1 or query.dtype not in (torch.int32, torch.int64) or query.numel() != n_seqs:
+                raise ValueError(f"query must be an int32 / int64 tensor of {n_seqs} positions")
+            if query.device.type == "cpu":
+                if n_seqs and int(query.min()) < 0:
+                    raise ValueError("query holds a negative position")
+                if n_seqs and int(query.max()) > np.iinfo(np.int32).max:
+                    raise ValueError("query holds a position beyond int32")
+                query_host = np.ascontiguousarray(query.numpy(), dtype=np.int32)
+            elif query.device != self.device:
+                raise ValueError(f"query must live on the host or on {self.device}")
+            # (int64 on the device: clamped into int32 first, so that a huge position stays "beyond the length" and a negative one negative)
+            query_dev = query.to(self.device).clamp(-1, np.iinfo(np.int32).max).to(torch.int32).contiguous()
+        vp = ctypes.c_void_p
+        with torch.cuda.device(self.device):
+            shape = (n_seqs, width) if reduce_heads else (n_seqs, self.dims.num_heads, width)
+            out = torch.empty(shape, dtype=torch.float32, device=self.device)
+            if out.numel() == 0:
+                return out
+            need = int(self.lib.op_attention_workspace_bytes(self._handle, n_seqs, total, max_seqlen)) + 256
+            ws = self._attention_workspace
+            if ws is None or ws.numel() < need:
+                ws = self._attention_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            base = ws.data_ptr()
+            aligned = (base + 255) // 256 * 256
+            req = _lib.OpAttentionRowsRequest()
+            req.struct_bytes = ctypes.sizeof(_lib.OpAttentionRowsRequest)
+            req.layer = int(layer)
+            req.pad_width = width
+            req.reduce_heads = 1 if reduce_heads else 0
+            req.hidden_dev = vp(hidden_packed.data_ptr()) if total else None
+            req.query_pos_dev = vp(query_dev.data_ptr()) if query_dev is not None else None
+            req.query_pos_host = query_host.ctypes.data_as(vp) if query_host is not None else None
+            req.out_dev = vp(out.data_ptr())
+            code = self.lib.op_attention_rows(
+                self._handle, vp(cu_seqlens.data_ptr()), cu_host.ctypes.data_as(vp), n_seqs, total, max_seqlen, ctypes.byref(req),
+                vp(aligned), ctypes.c_size_t(ws.numel() - (aligned - base)), vp(torch.cuda.current_stream(self.device).cuda_stream),
+            )
+        _lib.check(self.lib, self._handle, code, "op_attention_rows")
+        return out
+
     def _forward(self, part: "int | None", ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob=None, hidden=None, ids_host=None,
-                 running: "bool | None" = True) -> "tuple[PackedCall, torch.Tensor | None]":
+                 running: "bool | None" = True, pooled=None) -> "tuple[PackedCall, torch.Tensor | None, torch.Tensor | None]":
         """The one body of :meth:`forward_packed` (``part`` None: the current stream, the encoder's workspace) and
         :meth:`forward_packed_on` (pipeline ``part``: its stream and workspace): checks, outputs, workspace, the launch and the
         audits (``running``: whether the running audit may look at this forward; None: no audit at all) -> (the call with its
-        outputs, the hidden states of a ``hidden`` request)."""
+        outputs, the hidden states of a ``hidden`` request, the rows of a ``pooled`` request)."""
 
         if ids.dtype != torch.int32 or cu_seqlens.dtype != torch.int32:
             raise TypeError("ids and cu_seqlens must be int32")
@@ -803,6 +933,7 @@ class HipEncoder:
         if cu_host.shape[0] != n_seqs + 1:
             raise ValueError("cu_seqlens_host length mismatch")
         states, req = self._hidden_request(hidden, n_seqs, total, max_seqlen) if hidden is not None else (None, None)
+        pooled_states, pool_req = self._pool_request(pooled, n_seqs, total) if pooled is not None else (None, None)
         slots = self._split_streams() if part is not None else None
         # The outputs of a pipeline come from the SIDE stream's pool of the caching allocator (allocated under that stream): a
         # block of that pool is only ever recycled in side-stream order, so the kernels that write them can never land on memory
@@ -821,15 +952,39 @@ class HipEncoder:
             else:
                 ws = slots["ws"][part] = self._grown_workspace(slots["ws"][part], n_seqs, total, max_seqlen)
             call = PackedCall(ids, cu_seqlens, cu_host, n_seqs, total, max_seqlen, prune, rank, keep_prob, ws,
-                              torch.cuda.current_stream(self.device).cuda_stream, req, ids_host)
+                              torch.cuda.current_stream(self.device).cuda_stream, req, ids_host, pool_req=pool_req)
             if n_seqs:
                 self._forward_native(call)
                 # (an audit synchronises the call's stream once; on a pipeline, the other one must not be mid-forward on another
                 # host thread while it runs -- the pipelines of one encoder are driven from ONE thread everywhere in this package)
                 if running is not None:
                     maybe_audit(self, call, running)
-        return call, states
+        return call, states, pooled_states
 
+    def _pool_request(self, pooled: "HiddenRequest", n_seqs: int, total: int):
+        """-> (output tensor ``[n_sel, n_seqs, H]``, ``_lib.OpPoolRequest``) of one forward; the struct keeps its select array and
+        its scratch entry (one packed fp32 entry, reused by every selected entry) alive."""
+
+        if not isinstance(pooled, HiddenRequest) or pooled.pool is None:
+            raise TypeError("a pooled request is a HiddenRequest with pool='first' or pool='mean'")
+        n_entries = self.dims.num_layers + 1
+        layers = range(n_entries) if pooled.layers is None else [int(i) for i in pooled.layers]
+        if any(i < 0 or i >= n_entries for i in layers):
+            raise ValueError(f"hidden.layers must lie in 0 .. {n_entries - 1} (entry {n_entries - 1} = the pruning head's input)")
+        selected = sorted(set(layers))
+        H = self.dims.hidden_size
+        out = torch.empty((len(selected), n_seqs, H), dtype=torch.float32, device=self.device)
+        scratch = torch.empty((total, H), dtype=torch.float32, device=self.device)
+        flags = (ctypes.c_uint8 * n_entries)(*[1 if i in selected else 0 for i in range(n_entries)])
+        req = _lib.OpPoolRequest()
+        req.struct_bytes = ctypes.sizeof(_lib.OpPoolRequest)
+        req.kind = _lib.POOL_KINDS[pooled.pool]
+        req.select = ctypes.cast(flags, ctypes.POINTER(ctypes.c_uint8))
+        req.out_dev = ctypes.c_void_p(out.data_ptr()) if out.numel() else None
+        req.scratch_dev = ctypes.c_void_p(scratch.data_ptr()) if scratch.numel() else None
+        req.scratch_bytes = scratch.numel() * 4
+        req._keep = (flags, scratch)  # (alive as long as the struct)
+        return out, req
     def _hidden_request(self, hidden: "HiddenRequest", n_seqs: int, total: int, max_seqlen: int):
         """-> (output tensor, ``_lib.OpHiddenRequest``) of one forward; the struct keeps its select array alive."""
 
@@ -882,7 +1037,7 @@ class HipEncoder:
         self.check_ids(ids_np)
         ids = torch.from_numpy(ids_np).to(self.device)
         cu = torch.from_numpy(cu_np).to(self.device)
-        call, _ = self._forward(None, ids, cu, cu_np, max_len, running=None)  # (what is pinned now: the calibrated set, its layer mask included)
+        call, _, _ = self._forward(None, ids, cu, cu_np, max_len, running=None)  # (what is pinned now: the calibrated set, its layer mask included)
         return first_batch_audit(self, call, collective=True)
 
     def revert_to_default(self, reason: str, *, warning: "str | None" = None, stacklevel: int = 3,
@@ -952,7 +1107,7 @@ class HipEncoder:
 
         if rows is None:
             return call._replace(prune=torch.empty_like(call.prune), rank=torch.empty_like(call.rank), keep_prob=None, hidden_req=None,
-                                 size_ws_at_launch=True)
+                                 pool_req=None, size_ws_at_launch=True)
         sub_lengths = np.diff(call.cu_host)[list(rows)]
         sub_cu_host = np.concatenate(([0], np.cumsum(sub_lengths))).astype(np.int32)
         sub_ids_host = None if call.ids_host is None else np.concatenate([call.ids_host[call.cu_host[r]: call.cu_host[r + 1]] for r in rows])
@@ -1003,13 +1158,19 @@ class HipEncoder:
         aligned = (base + 255) // 256 * 256
         extra = () if call.hidden_req is None else (ctypes.byref(call.hidden_req),)
         entry = self.lib.op_forward_packed if call.hidden_req is None else self.lib.op_forward_packed_hidden
+        if call.pool_req is not None:
+            if not hasattr(self.lib, "op_forward_packed_pooled"):
+                raise _lib.HipLibraryError("this library has no op_forward_packed_pooled")
+            entry = self.lib.op_forward_packed_pooled
+            extra = (ctypes.byref(call.hidden_req) if call.hidden_req is not None else None, ctypes.byref(call.pool_req))
         code = entry(
             self._handle, vp(call.ids.data_ptr()), vp(call.cu_seqlens.data_ptr()), call.cu_host.ctypes.data_as(vp),
             call.n_seqs, call.total, call.max_seqlen, vp(call.prune.data_ptr()), vp(call.rank.data_ptr()),
             vp(call.keep_prob.data_ptr()) if call.keep_prob is not None else None,
             vp(aligned), ctypes.c_size_t(ws.numel() - (aligned - base)), vp(call.stream), *extra,
         )
-        _lib.check(self.lib, self._handle, code, "op_forward_packed" if call.hidden_req is None else "op_forward_packed_hidden")
+        _lib.check(self.lib, self._handle, code, "op_forward_packed_pooled" if call.pool_req is not None else
+                   "op_forward_packed" if call.hidden_req is None else "op_forward_packed_hidden")
 
     def _split_streams(self) -> dict:
         """Two HIP streams of their own (hipExtStreamCreateWithCUMask with the full mask: own hardware queues, no CU partition since
@@ -1078,7 +1239,7 @@ class HipEncoder:
             raise NotImplementedError("hidden-state requests are not available on the pipelined path (use forward_packed(hidden=...))")
         if attentions is not None:
             raise NotImplementedError("attention requests are not available on the pipelined path (use forward_packed(attentions=...))")
-        call, _ = self._forward(part, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, running=False)
+        call, _, _ = self._forward(part, ids, cu_seqlens, cu_seqlens_host, max_seqlen, keep_prob, running=False)
         return call.prune, call.rank
 
     def pipeline_stream(self, part: int) -> torch.cuda.Stream:

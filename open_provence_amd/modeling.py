@@ -99,7 +99,8 @@ _NO_PROBS = np.zeros(0, dtype=np.float32)
 
 class OpenProvenceOutput(dict):
     """Forward result usable both as a Mapping and through attributes, exposing the reference's fields:
-    ``logits`` (= ``ranking_logits``), ``ranking_logits``, ``pruning_logits``, ``loss``, ``hidden_states``."""
+    ``logits`` (= ``ranking_logits``), ``ranking_logits``, ``pruning_logits``, ``loss``, ``hidden_states``; and this package's
+    own reduced outputs ``pooled_hidden_states`` / ``attention_rows`` (None unless requested)."""
 
     def __getattr__(self, name: str) -> Any:
         try:
@@ -572,6 +573,9 @@ class OpenProvenceModel:
         return_dict: bool | None = None,
         output_hidden_states: bool | None = None,
         output_attentions: bool | None = None,
+        pooled_hidden_states: str | None = None,
+        attention_rows: "str | torch.Tensor | None" = None,
+        attention_rows_reduce_heads: bool = False,
         **kwargs: Any,
     ) -> OpenProvenceOutput | tuple[torch.Tensor, ...]:
         """``input_ids[B, L]`` (+ right-padded ``attention_mask``) -> ``ranking_logits[B, nl]`` and
@@ -590,6 +594,16 @@ class OpenProvenceModel:
         A side pass over the hidden states (``op_attention_probs``): logits and hidden states are bit-identical to those of
         the same call without the flag.  Memory: ``num_layers x B x heads x L^2 x 4`` bytes.
 
+        ``pooled_hidden_states="first" | "mean"`` (no counterpart in the reference): ``pooled_hidden_states`` is one fp32 tensor
+        ``[num_layers + 1, B, H]`` -- per entry of ``hidden_states`` the row of token 0 of each sequence (bit-identical to it) or
+        the mean over the sequence's tokens (fp64 in a fixed order, rounded once; a row of zeros for an empty sequence) --
+        reduced on the device from one scratch entry (``op_forward_packed_pooled``): ``(N + 1) x B x H x 4`` bytes instead of
+        ``(N + 1) x B x L x H x 4``.  ``attention_rows="first"`` or an integer tensor ``[B]`` of query positions (a model created
+        with ``attention_outputs=True``; ``ValueError`` otherwise): ``attention_rows`` is a tuple of num_layers fp32 tensors
+        ``[B, heads, L]``, the selected query's row of ``attentions`` bit for bit, or with ``attention_rows_reduce_heads=True``
+        ``[B, L]``, its mean over heads (``op_attention_rows``).  Both may be combined with the two flags above; logits are
+        bit-identical with or without them.
+
         ``labels``: ``loss`` is the reference's evaluation loss of the ranking head (standalone.py:1707-1722) as a 0-dim fp32
         device tensor -- ``BCEWithLogitsLoss`` on ``labels.float()`` when ``num_labels == 1``, otherwise ``CrossEntropyLoss``
         on integer ``labels.view(-1)`` -- computed by ``op_loss`` over the ranking logits the forward left on the device (fp64
@@ -601,8 +615,10 @@ class OpenProvenceModel:
         if input_ids is None:
             raise ValueError("input_ids must be provided")
         rank_labels = self._ranking_labels(labels, int(input_ids.shape[0])) if labels is not None else None
-        rank, pruning_logits, hidden_states, attentions, _ = self._forward_padded(input_ids, attention_mask, output_hidden_states,
-                                                                                  output_attentions)
+        reduced: dict[str, Any] = {}
+        rank, pruning_logits, hidden_states, attentions, _ = self._forward_padded(
+            input_ids, attention_mask, output_hidden_states, output_attentions,
+            reduced=self._reduced_requests(pooled_hidden_states, attention_rows, attention_rows_reduce_heads, reduced))
         loss = None
         if rank_labels is not None:
             loss = self.encoder.loss("rank_bce" if rank.shape[1] == 1 else "rank_ce", rank, rank_labels)
@@ -610,8 +626,20 @@ class OpenProvenceModel:
             return (rank, pruning_logits) if loss is None else (loss, rank, pruning_logits)
         return OpenProvenceOutput(
             loss=loss, logits=rank, ranking_logits=rank, pruning_logits=pruning_logits, hidden_states=hidden_states,
-            attentions=attentions,
+            attentions=attentions, pooled_hidden_states=reduced.get("pooled_hidden_states"), attention_rows=reduced.get("attention_rows"),
         )
+
+    def _reduced_requests(self, pooled_hidden_states, attention_rows, reduce_heads, results: "dict[str, Any]") -> "dict[str, Any] | None":
+        """The ``reduced`` argument of :meth:`_forward_padded` for forward()'s three keywords (None: none of them is set);
+        ``results`` receives ``pooled_hidden_states`` / ``attention_rows``."""
+
+        if pooled_hidden_states is None and attention_rows is None:
+            if reduce_heads:
+                raise ValueError("attention_rows_reduce_heads=True needs attention_rows")
+            return None
+        if attention_rows is not None and not self.encoder.attention_outputs:
+            raise ValueError("attention_rows needs the fp32 weight packs: create the model with attention_outputs=True")
+        return {"pool": pooled_hidden_states, "query": attention_rows, "reduce_heads": bool(reduce_heads), "results": results}
 
     def _ranking_labels(self, labels: torch.Tensor, n_rows: int) -> torch.Tensor:
         """``labels`` as the ranking loss reads them (standalone.py:1711, 1715), on the model's device: ``[B]`` fp32 for one
@@ -627,10 +655,11 @@ class OpenProvenceModel:
             raise TypeError(f"class labels must be an integer tensor, got {labels.dtype}")
         return labels
 
-    def _forward_padded(self, input_ids, attention_mask, output_hidden_states, output_attentions):
+    def _forward_padded(self, input_ids, attention_mask, output_hidden_states, output_attentions, reduced=None):
         """The forward of a padded batch without its losses: ``(ranking_logits, pruning_logits, hidden_states, attentions,
         packed)``; ``packed`` = the pruning logits as the kernels left them, ``[T, 2]`` on the device, with the batch's
-        ``cu_seqlens`` on the device and the token count -- what the token-classification loss reads."""
+        ``cu_seqlens`` on the device and the token count -- what the token-classification loss reads.  ``reduced``
+        (:meth:`_reduced_requests`): the pooled hidden states and / or attention rows go into its ``results``."""
 
         if output_attentions and not self.encoder.attention_outputs:
             raise ValueError("output_attentions=True needs the fp32 weight packs: create the model with attention_outputs=True")
@@ -654,11 +683,23 @@ class OpenProvenceModel:
         requests: dict[str, Any] = {}
         if output_hidden_states:
             requests["hidden"] = HiddenRequest(dtype=torch.float32, pad_width=width)
+        rows_request = self._attention_rows_request(reduced, width, int(cu_np.shape[0]) - 1)
         if output_attentions:
             requests["attentions"] = AttentionRequest(pad_width=width)
+        elif rows_request is not None:  # (beside the whole matrices: a pass of its own, below)
+            requests["attentions"] = rows_request
+        if reduced is not None and reduced["pool"] is not None:
+            requests["pooled"] = HiddenRequest(pool=reduced["pool"])
         prune, rank, *extra = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len, ids_host=ids_np, **requests)
         if output_attentions:
             attentions = tuple(extra.pop())
+            if rows_request is not None:
+                *_, rows = self.encoder.forward_packed_checked(ids, cu, cu_np, max_len, ids_host=ids_np, attentions=rows_request)
+                reduced["results"]["attention_rows"] = tuple(rows)
+        elif rows_request is not None:
+            reduced["results"]["attention_rows"] = tuple(extra.pop())
+        if "pooled" in requests:
+            reduced["results"]["pooled_hidden_states"] = extra.pop()
         if output_hidden_states:
             hidden = extra.pop()
             # ([N + 1, B, L, H]; with L = 0 the request is packed and empty: the same shape, no data)
@@ -668,6 +709,19 @@ class OpenProvenceModel:
         else:
             pruning_logits = unpack_to_padded(prune, cu_np, width)
         return rank, pruning_logits, hidden_states, attentions, (prune, cu, int(cu_np[-1]))
+
+    @staticmethod
+    def _attention_rows_request(reduced, width: int, n_rows: int) -> "AttentionRequest | None":
+        """forward(attention_rows=...) as the encoder's request: every layer, one query row per sequence."""
+
+        if reduced is None or reduced["query"] is None:
+            return None
+        query = reduced["query"]
+        if not isinstance(query, str):
+            query = torch.as_tensor(query)
+            if query.ndim != 1 or query.numel() != n_rows:
+                raise ValueError(f"attention_rows must be 'first' or hold one query position per row ({n_rows})")
+        return AttentionRequest(pad_width=width, query=query, reduce_heads=reduced["reduce_heads"])
 
     def __call__(self, *args: Any, **kwargs: Any):
         return self.forward(*args, **kwargs)
@@ -2581,14 +2635,16 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
         self.num_labels = config.num_pruning_labels
 
     def forward(self, input_ids=None, attention_mask=None, labels=None, return_dict=None, output_hidden_states=None,
-                output_attentions=None, **kwargs: Any):
+                output_attentions=None, pooled_hidden_states=None, attention_rows=None, attention_rows_reduce_heads=False,
+                **kwargs: Any):
         """The base forward without labels, as the reference runs it (standalone.py:3857-3863); with ``labels[B, L]`` (integer
         classes 0 / 1, -100 = ignored; CPU or device) ``loss`` is its ``CrossEntropyLoss`` over the pruning logits of the
         active positions (standalone.py:3870-3881) as a 0-dim fp32 device tensor.  ``op_loss`` reads the PACKED logits the
         forward left on the device with the forward's own ``cu_seqlens``: the active positions are the packed ones -- the
         ``attention_mask`` tokens, or every position without a mask.  A mask without any active position gives exactly 0.0
         (:3878-3879); active positions that are all -100 give NaN, as torch does.  ``return_dict=False`` returns
-        ``(loss, pruning_logits)`` with labels, ``(pruning_logits,)`` without."""
+        ``(loss, pruning_logits)`` with labels, ``(pruning_logits,)`` without.  ``pooled_hidden_states`` / ``attention_rows`` /
+        ``attention_rows_reduce_heads``: as in :meth:`OpenProvenceModel.forward`."""
 
         if input_ids is None:
             raise ValueError("input_ids must be provided")
@@ -2600,8 +2656,10 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
             if tuple(token_labels.shape) != tuple(input_ids.shape):
                 raise ValueError(f"labels must have the shape of input_ids {tuple(input_ids.shape)}, got {tuple(token_labels.shape)}")
             token_labels = token_labels.detach().to(self._runtime_device)
+        reduced: dict[str, Any] = {}
         rank, pruning_logits, hidden_states, attentions, (prune, cu, total) = self._forward_padded(
-            input_ids, attention_mask, output_hidden_states, output_attentions)
+            input_ids, attention_mask, output_hidden_states, output_attentions,
+            reduced=self._reduced_requests(pooled_hidden_states, attention_rows, attention_rows_reduce_heads, reduced))
         loss = None
         if token_labels is not None:
             if attention_mask is not None and total == 0:
@@ -2617,6 +2675,8 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
             ranking_logits=rank,
             hidden_states=hidden_states,
             attentions=attentions,
+            pooled_hidden_states=reduced.get("pooled_hidden_states"),
+            attention_rows=reduced.get("attention_rows"),
         )
 
 
