@@ -160,7 +160,8 @@ class _ReplicaLink:
         self.stamps: dict[str, float] = {}
 
     # -- forward ---------------------------------------------------------------------------------------------------
-    def submit(self, rows: list[list[int]], segments: list[list[tuple[int, int]]] | None) -> dict[str, Any]:
+    def submit(self, rows: list[list[int]], segments: list[list[tuple[int, int]]] | None) -> "RemoteLaunch":
+        from .launches import RemoteLaunch
         from .modeling import OpenProvenceModel
 
         ids_np, cu_np, max_len, seg_flat, seg_counts = OpenProvenceModel._pack_launch(rows, segments)
@@ -169,26 +170,23 @@ class _ReplicaLink:
                              f"vocab_size is {self.vocab_size}")  # (what HipEncoder.check_ids raises in the plain call)
         self.conn.send(("rows", self.request, (ids_np, cu_np, int(max_len), seg_flat, seg_counts)))
         self.stamps.setdefault("first_submit", perf_counter())
-        return {"remote": self, "rows": len(rows), "cu": cu_np, "seg_counts": seg_counts}
+        return RemoteLaunch(remote=self, rows=len(rows), cu=cu_np, seg_counts=seg_counts)
 
-    def result(self, handle: dict[str, Any]):
+    def result(self, launch: "RemoteLaunch"):
         import torch
+
+        from .launches import split_by_counts
 
         kind, request, payload = self.conn.recv()  # replies come back in the order of the submissions
         self.stamps["last_result"] = perf_counter()
         if kind == "error" or request != self.request:
             raise RuntimeError(f"the GPU owner could not run a forward batch: {payload}")
         rank_np, values, reduced = payload
-        n_rows = handle["rows"]
-        rank = torch.from_numpy(rank_np).reshape(n_rows, self.num_labels)
+        rank = torch.from_numpy(rank_np).reshape(launch.rows, self.num_labels)
         if reduced:
-            means, out, pos = values.tolist(), [], 0  # float32 -> Python float, exact (as OpenProvenceModel._collect_rows)
-            for c in handle["seg_counts"]:
-                out.append(means[pos : pos + c])
-                pos += c
-            return rank, out
-        cu = handle["cu"]
-        return rank, [values[cu[i] : cu[i + 1]] for i in range(n_rows)]
+            return rank, split_by_counts(values.tolist(), launch.seg_counts)  # float32 -> Python float, exact
+        cu = launch.cu
+        return rank, [values[cu[i] : cu[i + 1]] for i in range(launch.rows)]
 
     # -- this replica's part of the result (OpenProvenceModel._gather_job_results) --------------------------------------
     def exchange(self, _model: Any, mine: dict) -> list:
@@ -409,9 +407,9 @@ class _OwnerHub:
 
     @staticmethod
     def _finished(launched: tuple) -> bool:
-        if launched[0] != "handle":
+        if launched[0] != "launch":
             return True  # (replaced forward: computed synchronously)
-        event = launched[2].get("event")
+        event = launched[2].event
         return event is None or bool(event.query())
 
     def _launch(self, model: Any, batch: list) -> tuple:
@@ -441,9 +439,9 @@ class _OwnerHub:
         cu = np.concatenate(cu_parts)
         max_len = max(int(payload[2]) for _conn, payload in batch)
         if native:
-            handle = model._enqueue_packed(ids, cu, max_len, np.concatenate(seg_parts) if with_ranges else None,
-                                           seg_counts if with_ranges else None)
-            return ("handle", requests, handle)
+            launch = model._enqueue_packed(ids, cu, max_len, np.concatenate(seg_parts) if with_ranges else None,
+                                          seg_counts if with_ranges else None)
+            return ("launch", requests, launch)
         # a model whose forward was replaced (tests): the padded protocol, per-token keep-probabilities
         rows = [ids[cu[i] : cu[i + 1]].tolist() for i in range(len(cu) - 1)]
         rank, keeps = model._predict_rows_local(rows, None)
@@ -458,7 +456,7 @@ class _OwnerHub:
             return
         kind, requests, what = launched
         try:
-            rank, values, reduced = model._collect_packed(what) if kind == "handle" else what
+            rank, values, reduced = model._collect_packed(what) if kind == "launch" else what
         except Exception as exc:  # noqa: BLE001
             for conn, _rows, _vals, _tok in requests:
                 conn.send(("error", self.request, f"{type(exc).__name__}: {exc}"))

@@ -17,6 +17,7 @@ library or without a GPU, construction raises -- there is no fallback.
 from __future__ import annotations
 
 import contextlib
+import functools
 import itertools
 import json
 import logging
@@ -31,13 +32,13 @@ from typing import Any
 import numpy as np
 import torch
 
-from . import pipeline as pl
+from . import launches, pipeline as pl, request as rq
 from .config import DEFAULT_PROCESS_THRESHOLD, EncoderDims, OpenProvenceConfig
 from .engine import AttentionRequest, HiddenRequest, HipEncoder, check_arithmetic_arguments, require_gpu
 from .packing import pack_padded, pack_rows, unpack_to_padded
 from .pipeline import ContextState, FragmentRecord, RawPrediction
-from .prepared import PreparedContexts, PreparedItem, PreparedView, as_request as _as_prepared_request, derive_row_template
-from .splitters import SentenceSplitter, is_builtin_splitter, resolve_sentence_splitter
+from .prepared import PreparedContexts, PreparedItem, as_request as _as_prepared_request, derive_row_template
+from .splitters import SentenceSplitter, resolve_sentence_splitter
 
 LOGGER = logging.getLogger(__name__)
 # As the reference (standalone.py:160), the Rust tokenizer's own thread pool is off unless the environment says otherwise.
@@ -885,270 +886,30 @@ class OpenProvenceModel:
         cu = plan.cu
         return rank_all.cpu(), [keep_np[cu[i] : cu[i + 1]] for i in range(len(rows))]
 
-    # -- asynchronous forward: launch now, collect later (host stages of the neighbouring batches overlap the GPU) -----
+    # -- asynchronous forward: launch now, collect later (launches.py; host stages of the neighbouring batches overlap the GPU) --
     def _can_pipeline(self) -> bool:
         # (also with a process group attached: _launch_rows enqueues this rank's share, _collect_rows gathers)
         return self._forward_is_native()
 
-    def _dist_info(self) -> dict[str, Any] | None:
-        info = getattr(self, "_dist", None)
-        if info and info.get("local_only"):  # inside a job-sharded process(): this rank's forward batches are its own
-            return None
-        return info if info and (info["world"] > 1 or info.get("force")) else None
+    @functools.cached_property
+    def _staging(self) -> launches.Staging:
+        """The pinned staging pools of this model's launches and their rotation, made on first use."""
 
-    def _staging(self, slot: int, n_tokens: int, n_rows: int) -> dict[str, torch.Tensor]:
-        """Pinned host staging buffers (two slots, grown on demand, reused across calls: pinning memory costs ms).
+        return launches.Staging()
 
-        The host side fills and drains them through numpy views: an ATen CPU ``copy_`` of a batch this size starts the
-        intra-op thread pool, whose workers then spin on every core for a while -- measured on the 256-thread host of
-        the GPU box as 3 s of user time inside a 0.17 s ``process()`` call and 2-3x slower Python stages around it."""
+    _pack_launch = staticmethod(launches.pack_launch)
+    _dist_info = launches.dist_info
+    _count_forward = launches.count_forward
+    _launch_rows = launches.launch_rows
+    _enqueue_packed = launches.enqueue_packed
+    _guard_launch = launches.guard_launch
+    _collect_rows = launches.collect_rows
+    _collect_packed = launches.collect_packed
 
-        pools = self.__dict__.setdefault("_staging_pools", [None, None])
-        nl = int(self.dims.num_labels)
-        pool = pools[slot]
-        if pool is None or pool["ids"].numel() < n_tokens or pool["cu"].numel() < n_rows + 1:
-            cap_t, cap_r = max(n_tokens, 1) * 5 // 4 + 64, max(n_rows + 1, 2) * 5 // 4 + 8
-            pool = {
-                "ids": torch.empty(cap_t, dtype=torch.int32).pin_memory(),
-                "cu": torch.empty(cap_r, dtype=torch.int32).pin_memory(),
-                "keep": torch.empty(cap_t, dtype=torch.float32).pin_memory(),
-                "rank": torch.empty(cap_r * nl, dtype=torch.float32).pin_memory(),
-                "seg": torch.empty(2 * cap_t, dtype=torch.int32).pin_memory(),  # a fragment has at least one token
-            }
-            for name in ("ids", "cu", "keep", "rank", "seg"):
-                pool[name + "_np"] = pool[name].numpy()
-            pools[slot] = pool
-        return pool
-
-    def _launch_rows(self, rows: list[list[int]], segments: list[list[tuple[int, int]]] | None = None) -> dict[str, Any]:
-        """Enqueue one forward on the current stream: pinned H2D of the packed ids, the forward (keep-probability from
-        the head kernel), pinned D2H of keep-probabilities + ranking logits, one event.  Nothing here waits for the GPU.
-
-        With ``segments`` (per row, token ranges within the row) the keep-probabilities stay on the device: their mean
-        over every range is taken there (``op_segment_means``: numpy's float32 pairwise order, bit for bit) and only
-        4 bytes per range come back."""
-
-        remote = self.__dict__.get("_remote_forward")
-        if remote is not None:  # host-stage replica (frontend.py, mode="host"): the GPU owner's process runs the forward
-            self._count_forward(len(rows), sum(len(r) for r in rows))
-            return remote.submit(rows, segments)
-        info = self._dist_info()
-        shard = None
-        if info is not None:
-            # Data parallelism over the rows (SURVEY.md section 8e): the token-balanced plan every rank derives from the
-            # row lengths alone; this rank enqueues only its share -- same pinned staging, same asynchronous copies, same
-            # on-device fragment means as the single-GPU path -- and _collect_rows gathers 4 bytes per FRAGMENT (or per
-            # token, without segments) + the ranking logits on the post-processing rank.
-            from .sharding import ShardPlan
-
-            lengths = [len(r) for r in rows]
-            token_plan = ShardPlan(lengths, info["world"], width=1, num_labels=int(self.dims.num_labels))
-            mine = token_plan.local_rows(info["rank"])
-            shard = {"mine": mine, "n_rows_all": len(rows), "lengths": lengths, "shards": token_plan.shards,
-                     "counts_all": [len(sg) for sg in segments] if segments is not None else None}
-            rows = [rows[i] for i in mine]
-            if segments is not None:
-                segments = [segments[i] for i in mine]
-        handle = self._enqueue_local(rows, segments)
-        handle["shard"] = shard
-        return handle
-
-    def _count_forward(self, n_rows: int, n_tokens: int) -> None:
-        """One forward this process enqueued (or, a host-stage replica, submitted): ``performance_trace.runtime["forwards"]``."""
-
-        stats = self.__dict__.get("_forward_stats")
-        if stats is not None:
-            stats["launches"] += 1
-            stats["rows"] += int(n_rows)
-            stats["tokens"] += int(n_tokens)
-
-    @staticmethod
-    def _pack_launch(rows: list[list[int]], segments: list[list[tuple[int, int]]] | None):
-        """Rows (+ per-row token ranges) -> the arrays a launch consumes: packed ids, row offsets, the longest row, the
-        ranges as absolute (start, end) token positions of the packed batch, ranges per row.  This is also what a
-        host-stage replica sends to the GPU owner (frontend.py) -- a few numpy buffers instead of lists of Python ints."""
-
-        ids_np, cu_np, max_len = pack_rows(rows)
-        if segments is None:
-            return ids_np, cu_np, max_len, None, None
-        seg_counts = [len(s) for s in segments]
-        flat = np.empty(2 * sum(seg_counts), dtype=np.int32)
-        pos = 0
-        for i, segs in enumerate(segments):
-            base = int(cu_np[i])
-            for start, end in segs:
-                flat[pos] = base + start
-                flat[pos + 1] = base + end if end > start else base + start
-                pos += 2
-        return ids_np, cu_np, max_len, flat, seg_counts
-
-    def _enqueue_local(self, rows: list[list[int]], segments: list[list[tuple[int, int]]] | None) -> dict[str, Any]:
-        """The launch of :meth:`_launch_rows` for THIS process's rows."""
+    def _enqueue_local(self, rows: list[list[int]], segments: list[list[tuple[int, int]]] | None) -> launches.Launch:
+        """The launch of ``_launch_rows`` for THIS process's rows."""
 
         return self._enqueue_packed(*self._pack_launch(rows, segments))
-
-    def _enqueue_packed(self, ids_np: np.ndarray, cu_np: np.ndarray, max_len: int, seg_flat: np.ndarray | None,
-                        seg_counts: list[int] | None, reuse_slot: int | None = None, *, assemble: dict[str, Any] | None = None,
-                        ids_dev: torch.Tensor | None = None) -> dict[str, Any]:
-        """Enqueue one forward over packed rows (:meth:`_pack_launch`); also what the range guard of the fp16 + e4m3
-        kernel sets repeats, see :meth:`_guard_launch`."""
-
-        shard = None
-        retry = (ids_np, cu_np, max_len, seg_flat, seg_counts)
-        # Prepared contexts (``ids_np`` is None): the ids are laid out on the device by ``assemble`` (:meth:`_assemble_on_device`
-        # from the request's plan) or, the range guard's repeat, are the launch's own ``ids_dev`` once more.  They were
-        # checked when the corpus and the request's queries were uploaded.
-        if ids_np is not None:
-            self.encoder.check_ids(ids_np)
-        total, n_rows, nl = int(cu_np[-1]), len(cu_np) - 1, int(self.dims.num_labels)
-        if n_rows == 0:  # (more ranks than rows) nothing to enqueue here; the gather still runs on every rank
-            return {"event": None, "pool": None, "total": 0, "rows": 0, "cu": cu_np, "seg_counts": [] if seg_counts is not None else None,
-                    "alive": None, "shard": shard, "retry": None}
-        if reuse_slot is not None:
-            # the synchronous repeat of a guarded launch re-uses THAT launch's staging slot (its values have been read) and
-            # leaves the rotation alone: with A on slot 0 and B still in flight on slot 1, a repeat of A that advanced the
-            # rotation would hand slot 1 to the next launch while B's results are uncollected there
-            slot = reuse_slot
-        else:
-            slot = self.__dict__["_staging_slot"] = (self.__dict__.get("_staging_slot", -1) + 1) % 2
-        pool = self._staging(slot, max(total, 4 * n_rows) if assemble is not None else total, n_rows)
-        dev = self._runtime_device
-        np.copyto(pool["cu_np"][: n_rows + 1], cu_np)
-        cu_dev = pool["cu"][: n_rows + 1].to(dev, non_blocking=True)
-        if ids_np is not None:
-            np.copyto(pool["ids_np"][:total], ids_np)
-            ids_dev = pool["ids"][:total].to(dev, non_blocking=True)
-        elif assemble is not None:
-            # the plan travels through the slot's id staging (4 words per row instead of the row's tokens)
-            plan_np = assemble["plan"]
-            np.copyto(pool["ids_np"][: plan_np.size], plan_np.reshape(-1))
-            plan_dev = pool["ids"][: plan_np.size].to(dev, non_blocking=True)
-            ids_dev = self._assemble_on_device(assemble, plan_dev, plan_np, cu_dev, cu_np)
-        keep_dev = torch.empty(total, dtype=torch.float32, device=dev)
-        seg_dev = means_dev = None
-        n_seg = 0
-        if seg_counts is not None:
-            n_seg = sum(seg_counts)
-            if 2 * n_seg > pool["seg"].numel():
-                seg_flat = seg_counts = None  # (cannot happen for non-empty fragments; fall back to the token payload)
-        if seg_counts is not None:
-            np.copyto(pool["seg_np"][: 2 * n_seg], seg_flat)
-            seg_dev = pool["seg"][: 2 * n_seg].to(dev, non_blocking=True).view(n_seg, 2)
-        _, rank_dev = self.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev, ids_host=ids_np)
-        self._count_forward(n_rows, total)
-        if seg_counts is not None:
-            means_dev = self.encoder.segment_means(keep_dev, seg_dev)
-            pool["keep"][:n_seg].copy_(means_dev, non_blocking=True)
-        else:
-            pool["keep"][:total].copy_(keep_dev, non_blocking=True)
-        pool["rank"][: n_rows * nl].copy_(rank_dev.reshape(-1), non_blocking=True)
-        event = torch.cuda.Event()
-        event.record(torch.cuda.current_stream(dev))
-        return {"event": event, "pool": pool, "total": total, "rows": n_rows, "cu": cu_np, "seg_counts": seg_counts,
-                "alive": (ids_dev, cu_dev, keep_dev, rank_dev, seg_dev, means_dev), "shard": shard, "retry": retry,
-                "f8": self.encoder.f8_active(), "slot": slot, "ids_dev": ids_dev if ids_np is None else None}
-
-    def _guard_launch(self, handle: dict[str, Any]) -> dict[str, Any]:
-        """Range guard of the fp16 + e4m3 kernel sets for a pipelined launch (the launch has completed): when its
-        results -- fragment means or keep-probabilities, ranking logits -- are not finite and it ran on those sets, the
-        model falls back to the (hi, lo) bf16 sets (``HipEncoder.fall_back_from_f8``: warn once, stay there) and THIS
-        launch is repeated synchronously; the handle of the repeat is returned.  Launches already in flight are guarded
-        the same way when they are collected.  On the bf16 sets nothing is tested (reference arithmetic, fp32 range)."""
-
-        if not handle.get("f8") or handle.get("retry") is None or handle["rows"] == 0:
-            return handle
-        pool, nl = handle["pool"], int(self.dims.num_labels)
-        n_val = sum(handle["seg_counts"]) if handle["seg_counts"] is not None else handle["total"]
-        if np.isfinite(pool["keep_np"][:n_val]).all() and np.isfinite(pool["rank_np"][: handle["rows"] * nl]).all():
-            return handle
-        self.encoder.fall_back_from_f8("process")
-        if self.encoder.f8_active():
-            return handle  # (nothing to fall back to: the caller reports the NaN)
-        handle["alive"] = None
-        # (a device-assembled launch is repeated on the ids it laid out: the same device buffer, no second assembly)
-        again = self._enqueue_packed(*handle["retry"], reuse_slot=handle.get("slot"), ids_dev=handle.get("ids_dev"))
-        again["shard"] = handle.get("shard")
-        again["event"].synchronize()
-        return again
-
-    def _collect_rows(self, handle: dict[str, Any]) -> tuple[torch.Tensor, list[Any]]:
-        """-> (ranking logits, per row: its keep-probabilities, or -- launched with ``segments`` -- the list of its
-        range means as Python floats)."""
-
-        if handle.get("remote") is not None:
-            return handle["remote"].result(handle)
-        if handle.get("shard") is not None:
-            return self._collect_rows_sharded(handle)
-        handle["event"].synchronize()
-        handle = self._guard_launch(handle)
-        total, n_rows, nl, cu = handle["total"], handle["rows"], int(self.dims.num_labels), handle["cu"]
-        rank = torch.from_numpy(handle["pool"]["rank_np"][: n_rows * nl].copy()).reshape(n_rows, nl)
-        counts = handle.get("seg_counts")
-        handle["alive"] = None
-        if counts is not None:
-            means = handle["pool"]["keep_np"][: sum(counts)].tolist()  # float32 -> Python float, exact
-            out, pos = [], 0
-            for c in counts:
-                out.append(means[pos : pos + c])
-                pos += c
-            return rank, out
-        keep = handle["pool"]["keep_np"][:total].copy()  # the slot is reused two launches later
-        return rank, [keep[cu[i] : cu[i + 1]] for i in range(n_rows)]
-
-    def _collect_packed(self, handle: dict[str, Any]) -> tuple[np.ndarray, np.ndarray, bool]:
-        """:meth:`_collect_rows` without the per-row Python objects: (ranking logits [rows, nl], the launch's values as one
-        float32 array, reduced?) -- values = per-range means when the launch had ranges (reduced), else per-token
-        keep-probabilities.  What the GPU owner of a host-mode front-end sends back to its replicas (frontend.py)."""
-
-        handle["event"].synchronize()
-        handle = self._guard_launch(handle)
-        n_rows, nl = handle["rows"], int(self.dims.num_labels)
-        counts = handle.get("seg_counts")
-        n_val = sum(counts) if counts is not None else handle["total"]
-        rank = handle["pool"]["rank_np"][: n_rows * nl].copy().reshape(n_rows, nl)
-        values = handle["pool"]["keep_np"][:n_val].copy()  # the slot is reused two launches later
-        handle["alive"] = None
-        return rank, values, counts is not None
-
-    def _collect_rows_sharded(self, handle: dict[str, Any]) -> tuple[torch.Tensor, list[Any]]:
-        """The group form of :meth:`_collect_rows`: wait for this rank's launch, then ONE gather of fixed-size payloads
-        (per-fragment means -- or, launched without segments, per-token keep-probabilities -- + ranking logits) to
-        rank ``dst`` (RCCL over xGMI with backend "nccl"; the payload is KBs).  Every rank calls this for the same
-        handles in the same order; ranks other than ``dst`` get zero placeholders (their ``process()`` result is
-        discarded)."""
-
-        import torch.distributed as dist
-
-        from .sharding import ShardPlan
-
-        info, shard = self._dist_info(), handle["shard"]
-        nl = int(self.dims.num_labels)
-        n_all, lengths, counts_all = shard["n_rows_all"], shard["lengths"], shard["counts_all"]
-        per_row = counts_all if counts_all is not None else lengths  # values per row in the payload
-        if handle["event"] is not None:
-            handle["event"].synchronize()
-            handle = self._guard_launch(handle)  # a rank repeats ITS rows before the gather: the payload is finite
-        n_rows, n_val = handle["rows"], (sum(handle["seg_counts"]) if counts_all is not None else handle["total"])
-        if n_rows:
-            values = torch.from_numpy(handle["pool"]["keep_np"][:n_val].copy())
-            rank_local = torch.from_numpy(handle["pool"]["rank_np"][: n_rows * nl].copy()).reshape(n_rows, nl)
-        else:
-            values, rank_local = torch.zeros(0, dtype=torch.float32), torch.zeros((0, nl), dtype=torch.float32)
-        handle["alive"] = None
-        plan = ShardPlan(per_row, info["world"], width=1, num_labels=nl, shards=shard["shards"])  # the launch's row assignment
-        comm = self._runtime_device if dist.get_backend(info["group"]) == "nccl" else torch.device("cpu")
-        gathered = plan.gather(values.to(comm), rank_local.to(comm), dst=info["dst"], group=info["group"])
-        if gathered is None:
-            if counts_all is not None:
-                return torch.zeros((n_all, nl), dtype=torch.float32), [[0.0] * c for c in counts_all]
-            return torch.zeros((n_all, nl), dtype=torch.float32), [np.zeros(n, dtype=np.float32) for n in lengths]
-        vals, rank_all = gathered
-        flat = vals.reshape(-1).cpu().numpy()
-        cu = plan.cu
-        if counts_all is not None:
-            as_list = flat.tolist()  # float32 -> Python float, exact
-            return rank_all.cpu(), [as_list[cu[i] : cu[i + 1]] for i in range(n_all)]
-        return rank_all.cpu(), [flat[cu[i] : cu[i + 1]] for i in range(n_all)]
 
     def _predict_rows_local(self, rows: list[list[int]], type_rows: list[list[int]] | None) -> tuple[torch.Tensor, list[np.ndarray]]:
         """This process's rows -> (ranking_logits[B, nl] fp32 CPU, per-row keep probabilities fp32).
@@ -1382,83 +1143,27 @@ class OpenProvenceModel:
             raw_blocks=list(info.get("raw_blocks", [])),
         )
 
-    def _postprocess_contexts(
-        self,
-        queries,
-        contexts,
-        contexts_info,
-        *,
-        threshold: float,
-        always_select_title: bool,
-        use_best_reranker_score: bool,
-        sentence_probability_groups_requested: bool,
-        collect_sentence_texts: bool,
-        first_line_as_title: bool,
-        zero_score_when_empty: bool,
-    ):
+    def _postprocess_contexts(self, queries, contexts, contexts_info, *, threshold: float, always_select_title: bool,
+                              use_best_reranker_score: bool, sentence_probability_groups_requested: bool,
+                              collect_sentence_texts: bool, first_line_as_title: bool, zero_score_when_empty: bool):
         """Reference-shaped entry point (ref: _postprocess_contexts :2962-3202): returns the 8-tuple
         (pruned, scores, compression, kept, removed, titles, sentence_probabilities, seconds)."""
 
         t0 = perf_counter()
         states = {key: self._as_state(value) for key, value in contexts_info.items()}
         res = pl.postprocess_contexts(
-            queries,
-            contexts,
-            states,
-            threshold=threshold,
-            always_select_title=always_select_title,
-            use_best_reranker_score=use_best_reranker_score,
-            want_sentence_probabilities=sentence_probability_groups_requested,
-            want_sentence_texts=collect_sentence_texts,
-            first_line_as_title=first_line_as_title,
-            zero_score_when_empty=zero_score_when_empty,
-        )
-        return (
-            res.pruned_contexts,
-            res.reranking_scores,
-            res.compression_rates,
-            res.kept_sentences,
-            res.removed_sentences,
-            res.titles,
-            res.sentence_probabilities,
-            perf_counter() - t0,
-        )
+            queries, contexts, states, threshold=threshold, always_select_title=always_select_title,
+            use_best_reranker_score=use_best_reranker_score, want_sentence_probabilities=sentence_probability_groups_requested,
+            want_sentence_texts=collect_sentence_texts, first_line_as_title=first_line_as_title, zero_score_when_empty=zero_score_when_empty)
+        return (*res.as_tuple(), perf_counter() - t0)
 
-    def _apply_reordering(
-        self,
-        pruned_contexts,
-        reranking_scores,
-        compression_rates,
-        kept_sentences,
-        removed_sentences,
-        title_values,
-        sentence_probability_groups,
-        *,
-        top_k: int | None,
-    ):
+    def _apply_reordering(self, pruned_contexts, reranking_scores, compression_rates, kept_sentences, removed_sentences, title_values,
+                          sentence_probability_groups, *, top_k: int | None):
         """Reference-shaped entry point (ref: _apply_reordering :3204-3312)."""
 
-        res = pl.apply_reordering(
-            pl.PostprocessResult(
-                pruned_contexts,
-                reranking_scores,
-                compression_rates,
-                kept_sentences,
-                removed_sentences,
-                title_values,
-                sentence_probability_groups,
-            ),
-            top_k,
-        )
-        return (
-            res.pruned_contexts,
-            res.reranking_scores,
-            res.compression_rates,
-            res.kept_sentences,
-            res.removed_sentences,
-            res.titles,
-            res.sentence_probabilities,
-        )
+        result = pl.PostprocessResult(pruned_contexts, reranking_scores, compression_rates, kept_sentences, removed_sentences,
+                                      title_values, sentence_probability_groups)
+        return pl.apply_reordering(result, top_k).as_tuple()
 
     def _estimate_device_memory_bytes(self) -> int | None:
         override = os.getenv("OPEN_PROVENCE_DEVICE_MEMORY_GB")
@@ -1473,19 +1178,6 @@ class OpenProvenceModel:
             return int(torch.cuda.get_device_properties(self._runtime_device).total_memory)
         except Exception:
             return None
-
-    def _resolve_preprocess_workers(self, override: int | None) -> int:
-        if override is not None:
-            return max(0, int(override))
-        env_value = os.getenv("OPEN_PROVENCE_PREPROCESS_WORKERS")
-        if env_value:
-            try:
-                parsed = int(env_value)
-            except ValueError:
-                parsed = 0
-            if parsed > 0:
-                return parsed
-        return pl.default_preprocess_workers()
 
     def _auto_tune_preprocess_loader(self, **kwargs: Any) -> tuple[int, int, int | None]:
         return pl.auto_tune_preprocess_loader(device_memory_bytes=self._estimate_device_memory_bytes(), **kwargs)
@@ -1509,7 +1201,7 @@ class OpenProvenceModel:
 
         def specs():
             for q_idx, query in enumerate(queries):
-                query_token_ids.append([int(t) for t in self.tokenizer.encode(query, add_special_tokens=False)])
+                query_token_ids.append(pl.tokenize_query(self.tokenizer, query))
                 for c_idx, entry in enumerate(contexts[q_idx]):
                     if owned is None or owned[q_idx][c_idx]:  # job-sharded call: the other ranks' contexts are skipped
                         yield q_idx, c_idx, entry
@@ -1766,22 +1458,16 @@ class OpenProvenceModel:
         _queries, nested, _structure = pl.normalize_inputs("", list(contexts))
         nested, titles = self._resolve_titles([""], nested, title, first_line_as_title=first_line_as_title)
         entries = nested[0]
-        if respect_sentence_boundaries:  # (the rule of _process_impl)
-            max_fragment_tokens = max(16, self.max_length - 2)
-        else:
-            max_fragment_tokens = max(16, self.max_length // 2)
-        timing = {"sentence_collect_seconds": 0.0, "sentence_normalize_seconds": 0.0, "tokenize_seconds": 0.0,
-                  "fragment_split_seconds": 0.0, "fragment_decode_seconds": 0.0}
+        timing = pl.empty_stage_timing()
         if preprocess_workers is not None:
             workers = min(max(0, int(preprocess_workers)), 32)
-        else:  # (process()'s own rule for worker threads without a request)
-            workers = 4 if (len(entries) >= 128 and is_builtin_splitter(splitter)
-                            and hasattr(getattr(self.tokenizer, "_tokenizer", None), "encode_batch")) else 0
+        else:
+            workers = rq.default_thread_workers(self, len(entries), splitter)
         t0 = perf_counter()
         jobs = self._iter_jobs(
             [""], [entries], titles, splitter, [], strip_sentences=strip_sentences, timing=timing, workers=workers,
-            fragment_args=dict(max_fragment_tokens=max_fragment_tokens, strip_sentences=strip_sentences,
-                               respect_sentence_boundaries=respect_sentence_boundaries),
+            fragment_args=dict(max_fragment_tokens=pl.max_fragment_tokens(self.max_length, respect_sentence_boundaries),
+                               strip_sentences=strip_sentences, respect_sentence_boundaries=respect_sentence_boundaries),
         )
         items: list[PreparedItem] = []
         frag_base = 0
@@ -1850,134 +1536,6 @@ class OpenProvenceModel:
         return self.encoder.assemble_rows(corpus["ids"], corpus["frag_off"], corpus["frag_off_np"], queries["ids"], queries["off"],
                                           queries["off_np"], corpus["pieces"], plan_dev, plan_np, cu_dev, cu_np)
 
-    def _run_prepared_request(self, views: Sequence[PreparedView], batch_size: int, queries: list[str], query_token_ids: list[list[int]],
-                              sep_len: int, states: dict[tuple[int, int], ContextState], pending: list[Any]) -> tuple[float, float, int]:
-        """The request-time half of ``process()`` on prepared contexts -> (assembly seconds, inference seconds, blocks).
-
-        Blocks come from the cached fragments by length arithmetic (``PreparedItem.blocks_for``); the states are what
-        ``_process_impl`` builds from a job.  A replaced forward, a corpus without a row template, or a library without
-        ``op_assemble_rows``: the rows are built on the host from the cached fragments (:meth:`_run_inference_batches`,
-        at most ``batch_size`` rows per call of a replaced forward).  Native forward: ONE ``plan_forward_chunks`` over all
-        rows of the request within the token budget; per forward the plan (4 words per row), ``cu_seqlens`` and the
-        fragment ranges are uploaded, ``op_assemble_rows`` lays the ids out and the forward runs on them."""
-
-        t_asm = perf_counter()
-        corpus = views[0].corpus
-        tokenizer, max_length = self.tokenizer, self.max_length
-        on_device = (self._forward_is_native() and corpus.template is not None and hasattr(self.encoder.lib, "op_assemble_rows")
-                     and self.__dict__.get("_remote_forward") is None)
-
-        def state_of(q_idx, c_idx, item, blocks):
-            state = states.get((q_idx, c_idx))
-            if state is None:
-                state = states[(q_idx, c_idx)] = ContextState(
-                    sentences=list(item.sentences),
-                    fragments=item.fragments,
-                    blocks=blocks,
-                    prefix_length=len(item.prefix_sentences),
-                    prefix_sentences=item.prefix_sentences,
-                    prefix_token_counts=item.prefix_token_counts,
-                    title_is_first_sentence=item.title_is_first_sentence,
-                    original_text=item.context_text,
-                )
-            return state
-
-        # per row of the request: query, context, block, the context's item and blocks, (first fragment within the context,
-        # fragments, clip, context tokens).  Lengths only: states and jobs are built forward by forward, beside the GPU.
-        rows: list[tuple] = []
-        for q_idx, view in enumerate(views):
-            q_len = len(query_token_ids[q_idx])
-            for c_idx, at in enumerate(view.indices):
-                item = corpus.items[at]
-                blocks, plan = item.blocks_for(tokenizer, q_len, sep_len, max_length)
-                if not blocks:
-                    state_of(q_idx, c_idx, item, blocks)
-                for b_idx, entry in enumerate(plan):
-                    rows.append((q_idx, c_idx, b_idx, item, blocks, entry))
-        if not rows:
-            return perf_counter() - t_asm, 0.0, 0
-        if not on_device:
-            inference_jobs = []
-            for q_idx, c_idx, b_idx, item, blocks, _entry in rows:
-                state_of(q_idx, c_idx, item, blocks)
-                inference_jobs.append({"query_idx": q_idx, "context_idx": c_idx, "block_idx": b_idx, "texts": [f.text for f in blocks[b_idx]]})
-            assembly = perf_counter() - t_asm
-            return assembly, self._run_inference_batches(inference_jobs, batch_size, queries, query_token_ids, states, pending), len(rows)
-
-        template = corpus.template
-        n_fixed = len(template.prefix) + len(template.middle) + len(template.suffix)
-        ctx_at = [len(template.prefix) + len(q) + len(template.middle) for q in query_token_ids]
-        # ids a context must not begin with for its place in the row to follow from lengths alone: the reference looks the
-        # context's tokens up in the row (pipeline.prepare_block_inputs), and an earlier occurrence can only start there
-        heads = [set(template.prefix) | set(q) | set(template.middle) for q in query_token_ids]
-        # a row without context tokens (an empty context's fallback sentence): no fragments in its plan, and no suffix where
-        # the tokenizer builds none for an empty second sequence; a layout that is neither comes from the host (below)
-        drop = len(template.suffix) if template.empty_context == "drop" else 0
-        q_lens = [len(q) for q in query_token_ids]
-        lengths = [n_fixed + q_lens[row[0]] + row[5][3] - (0 if row[5][3] else drop) for row in rows]
-        spans = pl.plan_forward_chunks(lengths, batch_size, self.forward_token_budget)
-        device_corpus = self._prepared_device_corpus(corpus)
-        q_off_np = np.zeros(len(query_token_ids) + 1, dtype=np.int32)
-        q_off_np[1:] = np.cumsum(q_lens)
-        q_ids_np = np.fromiter((t for q in query_token_ids for t in q), dtype=np.int32, count=int(q_off_np[-1]))
-        self.encoder.check_ids(q_ids_np)
-        dev = self._runtime_device
-        request_dev = {"ids": torch.from_numpy(q_ids_np).to(dev), "off": torch.from_numpy(q_off_np).to(dev), "off_np": q_off_np}
-        assembly = perf_counter() - t_asm
-        elapsed = 0.0
-        for start, stop in spans:
-            t_asm = perf_counter()
-            n_rows = stop - start
-            chunk: list[dict[str, Any]] = []
-            plan_np = np.empty((n_rows, 4), dtype=np.int32)
-            ranges_per_job: list[list[tuple[int, int]]] = []
-            segments: list[list[tuple[int, int]]] = []
-            on_host = False
-            for i, (q_idx, c_idx, b_idx, item, blocks, (first, count, clip, ctx_len)) in enumerate(rows[start:stop]):
-                state = state_of(q_idx, c_idx, item, blocks)
-                block = blocks[b_idx]
-                chunk.append({"query_idx": q_idx, "context_idx": c_idx, "block_idx": b_idx, "texts": [f.text for f in block]})
-                if ctx_len == 0:
-                    on_host = on_host or template.empty_context is None
-                    plan_np[i] = (q_idx, item.frag_base + first, 0, -1 if drop else 0)
-                else:
-                    plan_np[i] = (q_idx, item.frag_base + first, count, clip)
-                if ctx_len == 0 or not block[0].token_ids or block[0].token_ids[0] in heads[q_idx]:
-                    ranges = self._prepare_block_inputs(query_token_ids[q_idx], block)[3]
-                else:
-                    ranges, cursor = [], ctx_at[q_idx]
-                    for fragment in block:
-                        ranges.append((cursor, cursor + len(fragment.token_ids)))
-                        cursor += len(fragment.token_ids)
-                ranges_per_job.append(ranges)
-                segments.append(pl.fragment_token_ranges(state, block, ranges, lengths[start + i]))
-            if on_host:  # ... this forward's rows are built on the host
-                host_rows = [self._prepare_block_inputs(query_token_ids[row[0]], row[4][row[2]])[0] for row in rows[start:stop]]
-                assembly += perf_counter() - t_asm
-                t0 = perf_counter()
-                handle = self._launch_rows(host_rows, segments)
-            else:
-                cu_np = np.zeros(n_rows + 1, dtype=np.int32)
-                cu_np[1:] = np.cumsum(lengths[start:stop])
-                seg_counts = [len(s) for s in segments]
-                seg_flat = np.empty(2 * sum(seg_counts), dtype=np.int32)
-                pos = 0
-                for i, segs in enumerate(segments):  # (absolute positions of the packed batch, as _pack_launch writes them)
-                    base = int(cu_np[i])
-                    for seg_start, seg_end in segs:
-                        seg_flat[pos] = base + seg_start
-                        seg_flat[pos + 1] = base + seg_end if seg_end > seg_start else base + seg_start
-                        pos += 2
-                assembly += perf_counter() - t_asm
-                t0 = perf_counter()
-                handle = self._enqueue_packed(None, cu_np, max(lengths[start:stop]), seg_flat, seg_counts,
-                                              assemble={"plan": plan_np, "corpus": device_corpus, "queries": request_dev})
-            elapsed += perf_counter() - t0
-            pending.append((handle, chunk, ranges_per_job, queries, states))
-            if len(pending) > 1:
-                elapsed += self._flush_pending(pending, keep_last=1)
-        return assembly, elapsed, len(rows)
-
     def _gather_job_results(self, result, owned, info, error: BaseException | None = None):
         """Job-sharded ``process()``: every rank sends the post-processed fields of the contexts it owns to rank
         ``dst`` (one ``gather_object``; the payload is the texts and a few floats per context), which writes them into
@@ -1993,8 +1551,7 @@ class OpenProvenceModel:
             return result
         fields = []
         if error is None:
-            fields = [f for f in (result.pruned_contexts, result.reranking_scores, result.compression_rates, result.kept_sentences,
-                                  result.removed_sentences, result.titles, result.sentence_probabilities)]
+            fields = list(result.as_tuple())
             mine = {
                 (q, c): tuple(None if f is None else f[q][c] for f in fields)
                 for q, per_query in enumerate(owned) for c, own in enumerate(per_query) if own
@@ -2095,18 +1652,19 @@ class OpenProvenceModel:
             first_line_as_title = settings["first_line_as_title"]
             strip_sentences, respect_sentence_boundaries = settings["strip_sentences"], settings["respect_sentence_boundaries"]
         replicas, implicit = ("", True) if prepared is not None else self._front_end_request(context, preprocess_workers, torch_dataloader_kwargs)
+        call = dict(
+            question=question, context=context, title=title, first_line_as_title=first_line_as_title, batch_size=batch_size,
+            threshold=threshold, always_select_title=always_select_title, reorder=reorder, top_k=top_k,
+            sentence_splitter=sentence_splitter, language=language, use_best_reranker_score=use_best_reranker_score,
+            zero_score_when_empty=zero_score_when_empty, show_progress=show_progress, debug_messages=debug_messages,
+            enable_warnings=enable_warnings, strip_sentences=strip_sentences,
+            respect_sentence_boundaries=respect_sentence_boundaries, return_sentence_metrics=return_sentence_metrics,
+            return_sentence_texts=return_sentence_texts, show_inference_progress=show_inference_progress,
+            preprocess_workers=preprocess_workers, preprocess_batch_size=preprocess_batch_size,
+            torch_dataloader_kwargs=torch_dataloader_kwargs)
         if (replicas and not getattr(self, "_dist", None) and self.__dict__.get("_remote_forward") is None
                 and not isinstance(context, str)):
-            routed = self._process_through_front_end(replicas, implicit, dict(
-                question=question, context=context, title=title, first_line_as_title=first_line_as_title, batch_size=batch_size,
-                threshold=threshold, always_select_title=always_select_title, reorder=reorder, top_k=top_k,
-                sentence_splitter=sentence_splitter, language=language, use_best_reranker_score=use_best_reranker_score,
-                zero_score_when_empty=zero_score_when_empty, show_progress=show_progress, debug_messages=debug_messages,
-                enable_warnings=enable_warnings, strip_sentences=strip_sentences,
-                respect_sentence_boundaries=respect_sentence_boundaries, return_sentence_metrics=return_sentence_metrics,
-                return_sentence_texts=return_sentence_texts, show_inference_progress=show_inference_progress,
-                preprocess_workers=preprocess_workers, preprocess_batch_size=preprocess_batch_size,
-                torch_dataloader_kwargs=torch_dataloader_kwargs))
+            routed = self._process_through_front_end(replicas, implicit, call)
             if routed is not None:
                 return routed
 
@@ -2117,16 +1675,7 @@ class OpenProvenceModel:
         gc_was_enabled = gc.isenabled()
         gc.disable()
         try:
-            return self._process_impl(
-                question, context, title, first_line_as_title, batch_size=batch_size, threshold=threshold,
-                always_select_title=always_select_title, reorder=reorder, top_k=top_k, sentence_splitter=sentence_splitter,
-                language=language, use_best_reranker_score=use_best_reranker_score, zero_score_when_empty=zero_score_when_empty,
-                show_progress=show_progress, debug_messages=debug_messages, enable_warnings=enable_warnings,
-                strip_sentences=strip_sentences, respect_sentence_boundaries=respect_sentence_boundaries,
-                return_sentence_metrics=return_sentence_metrics, return_sentence_texts=return_sentence_texts,
-                show_inference_progress=show_inference_progress, preprocess_workers=preprocess_workers,
-                preprocess_batch_size=preprocess_batch_size, torch_dataloader_kwargs=torch_dataloader_kwargs, prepared=prepared,
-            )
+            return self._process_impl(prepared=prepared, **call)
         finally:
             self.__dict__.pop("_forward_stats", None)  # (the call's counter: later get_raw_predictions* calls count nowhere)
             if gc_was_enabled:
@@ -2226,385 +1775,68 @@ class OpenProvenceModel:
             return None
 
     def _process_impl(
-        self,
-        question,
-        context,
-        title,
-        first_line_as_title,
-        *,
-        batch_size,
-        threshold,
-        always_select_title,
-        reorder,
-        top_k,
-        sentence_splitter,
-        language,
-        use_best_reranker_score,
-        zero_score_when_empty,
-        show_progress,
-        debug_messages,
-        enable_warnings,
-        strip_sentences,
-        respect_sentence_boundaries,
-        return_sentence_metrics,
-        return_sentence_texts,
-        show_inference_progress,
-        preprocess_workers,
-        preprocess_batch_size,
-        torch_dataloader_kwargs,
-        prepared=None,
+        self, question, context, title, first_line_as_title, *, batch_size, threshold, always_select_title, reorder, top_k,
+        sentence_splitter, language, use_best_reranker_score, zero_score_when_empty, show_progress, debug_messages,
+        enable_warnings, strip_sentences, respect_sentence_boundaries, return_sentence_metrics, return_sentence_texts,
+        show_inference_progress, preprocess_workers, preprocess_batch_size, torch_dataloader_kwargs, prepared=None,
     ):
+        """One request through its stages (request.py); the forwards go through the launch layer (launches.py)."""
+
         batch_size = max(1, batch_size)
         threshold = self._resolve_process_threshold(threshold)
         start_total = perf_counter()
         forward_stats = self.__dict__["_forward_stats"] = {"launches": 0, "rows": 0, "tokens": 0}
         splitter = self._resolve_sentence_splitter(sentence_splitter, language)
-
-        if isinstance(debug_messages, bool):
-            debug_callback = LOGGER.info if debug_messages else None
-        elif callable(debug_messages):
-            debug_callback = debug_messages
-        else:
-            raise TypeError("debug_messages must be a bool or a callable that accepts a string")
-
-        timing = {
-            "sentence_collect_seconds": 0.0,
-            "sentence_normalize_seconds": 0.0,
-            "tokenize_seconds": 0.0,
-            "fragment_split_seconds": 0.0,
-            "fragment_decode_seconds": 0.0,
-        }
-        assembly_time = 0.0
-        inference_time = 0.0
+        debug_callback = rq.debug_callback_of(debug_messages, LOGGER)
+        timing = pl.empty_stage_timing()
+        run = rq.Run()
 
         with contextlib.ExitStack() as stack:
             if not enable_warnings:
                 stack.enter_context(warnings.catch_warnings())
                 warnings.simplefilter("ignore")
-
-            # (host-mode front-end: the owner has normalised the request and assigned the jobs once for all replicas; a
-            # replica gets the normalised structure with the texts of the contexts it does not own blanked)
-            handed = (getattr(self, "_dist", None) or {}).get("prenormalized")
+            request = rq.resolve_request(self, question, context, title, first_line_as_title, respect_sentence_boundaries, prepared)
+            sharding = rq.enter_job_sharding(self, request, stack)
+            total_jobs = sharding.total_jobs if sharding is not None else request.total_jobs
+            thread_workers, preprocess_batch = rq.plan_host_stages(
+                self, total_jobs, batch_size, splitter, preprocess_workers, preprocess_batch_size, torch_dataloader_kwargs, debug_callback)
             if prepared is not None:
-                # (prepared.as_request: one view per query; `contexts` = the entries post-processing falls back to, as title
-                # resolution left them at preparation.  The job stream below gets no contexts: it tokenises the queries.)
-                queries, views, structure = prepared
-                contexts = [[view.corpus.items[i].entry for i in view.indices] for view in views]
-                titles = [None] * len(queries)
-            elif handed is not None:
-                queries, contexts, structure = handed["queries"], handed["contexts"], handed["structure"]
+                rq.run_prepared_request(self, request, run, batch_size)
             else:
-                queries, contexts, structure = self._normalize_inputs(question, context)
-            if prepared is None:
-                contexts, titles = self._resolve_titles(queries, contexts, title, first_line_as_title=first_line_as_title)
-            if respect_sentence_boundaries:
-                max_fragment_tokens = max(16, self.max_length - 2)
-            else:
-                max_fragment_tokens = max(16, self.max_length // 2)
-            sep_token_ids = self.tokenizer.encode(self.tokenizer.sep_token or "", add_special_tokens=False)
-
-            query_token_ids: list[list[int]] = []
-            total_jobs = sum(len(per_query) for per_query in contexts) if prepared is None else 0
-            # job-level sharding (attach_process_group(shard="jobs")): this rank prepares, runs and post-processes only
-            # the contexts it owns; the forward batches below are then purely local
-            job_shard = getattr(self, "_dist", None)
-            if not (job_shard and job_shard.get("shard") == "jobs" and (job_shard["world"] > 1 or job_shard.get("force"))):
-                job_shard = None
-            owned = None
-            if job_shard is not None:
-                owner = handed["owner"] if handed is not None else pl.assign_jobs(contexts, job_shard["world"])
-                owned = [[r == job_shard["rank"] for r in per_query] for per_query in owner]
-                total_jobs = sum(sum(per_query) for per_query in owned)
-                job_shard["local_only"] = True
-                stack.callback(job_shard.__setitem__, "local_only", False)
-                if job_shard["world"] > 1 and handed is None and self._forward_is_native() and self.encoder.audit_pending:
-                    # every rank has the whole request: the audit rows are its head (first query, up to eight contexts), the
-                    # same on every rank, whatever jobs a rank owns
-                    from .sharding import collective_audit
-
-                    collective_audit(self.encoder, self._audit_rows_of_request(queries, contexts), job_shard["group"])
-                gather_state = {"entered": False}
-
-                def _leave_with_error(_exc_type, exc, _tb, _info=job_shard, _state=gather_state):
-                    # an exception on this rank before its gather: enter the collective with an error marker, so that
-                    # the peers are told instead of blocking in gather_object forever; then let the exception go on
-                    if exc is not None and not _state["entered"]:
-                        _state["entered"] = True
-                        try:
-                            self._gather_job_results(None, None, _info, error=exc)
-                        except Exception:  # (a broken group must not mask the original error)
-                            pass
-                    return False
-
-                stack.push(_leave_with_error)
-
-            # effective preprocess batch (= cap of blocks per inference pass), as the reference computes it
-            workers = self._resolve_preprocess_workers(preprocess_workers)
-            preprocess_batch = max(1, int(preprocess_batch_size or batch_size))
-            workers_explicit = preprocess_workers is not None
-            batch_explicit = preprocess_batch_size is not None
-            prefetch_explicit = False
-            prefetch: int | None = None
-            if not workers_explicit:
-                env_workers = os.getenv("OPEN_PROVENCE_PREPROCESS_WORKERS")
-                if env_workers:
-                    try:
-                        workers_explicit = int(env_workers) > 0
-                    except ValueError:
-                        workers_explicit = False
-            if torch_dataloader_kwargs:
-                custom = dict(torch_dataloader_kwargs)
-                if "num_workers" in custom:
-                    workers_explicit = True
-                    workers = int(custom["num_workers"])
-                if "batch_size" in custom:
-                    batch_explicit = True
-                    preprocess_batch = int(custom["batch_size"])
-                if "prefetch_factor" in custom:
-                    prefetch_explicit = True
-                    raw_prefetch = custom["prefetch_factor"]
-                    if isinstance(raw_prefetch, (int, float)) or (isinstance(raw_prefetch, str) and raw_prefetch.isdigit()):
-                        prefetch = int(raw_prefetch)
-            workers, preprocess_batch, _prefetch = self._auto_tune_preprocess_loader(
-                total_jobs=total_jobs,
-                inference_batch_size=batch_size,
-                current_workers=workers,
-                current_preprocess_batch=preprocess_batch,
-                current_prefetch=prefetch,
-                workers_explicit=workers_explicit,
-                batch_explicit=batch_explicit,
-                prefetch_explicit=prefetch_explicit,
-            )
-            # Worker threads for the split / tokenize stage: as many as explicitly requested (preprocess_workers=, the
-            # OPEN_PROVENCE_PREPROCESS_WORKERS variable or torch_dataloader_kwargs["num_workers"]); WITHOUT a request, four
-            # of them from 128 jobs on when BOTH hold: the tokenizer is a Hugging Face fast one (its Rust batch calls run
-            # outside the GIL) and the sentence splitter is one of this package's own (thread-safe: stateless regex /
-            # lazily initialised under a lock).  A caller-supplied splitter is never called from several threads unless
-            # workers were asked for -- the reference only ever ran splitters in separate processes (standalone.py:3589).
-            # Pure-Python tokenizers are served best by the lazy single-thread pipeline below (the reference's own default
-            # is 0 workers under 2000 jobs, standalone.py:2591-2592).
-            thread_workers = min(int(workers), 32) if (workers_explicit and workers > 0) else 0
-            if (not workers_explicit and total_jobs >= 128 and is_builtin_splitter(splitter)
-                    and hasattr(getattr(self.tokenizer, "_tokenizer", None), "encode_batch")):
-                thread_workers = 4
-            if debug_callback is not None:
-                debug_callback(
-                    f"[OpenProvenceModel] preprocess_workers={workers} preprocess_threads={thread_workers} "
-                    f"preprocess_batch={preprocess_batch} default_workers={pl.default_preprocess_workers()}"
-                )
-            job_stream = self._iter_jobs(
-                queries, contexts if prepared is None else [[] for _ in queries], titles, splitter, query_token_ids, strip_sentences=strip_sentences, timing=timing,
-                workers=thread_workers, group_size=min(64, max(1, preprocess_batch)), owned=owned,
-                fragment_args=dict(max_fragment_tokens=max_fragment_tokens, strip_sentences=strip_sentences,
-                                   respect_sentence_boundaries=respect_sentence_boundaries) if thread_workers > 0 else None,
-            )
-            states: dict[tuple[int, int], ContextState] = {}
-            total_blocks = 0
-            pending: list[Any] = []  # forwards in flight (pipelined native path)
-            # Native pipelined path: the forward of one granule of contexts runs on the GPU while the host splits,
-            # tokenizes and assembles the next one (rows are independent, so the granule does not change results).
-            # A call costs about (launch overhead) x N / g for its launches plus (GPU time per context) x g for the
-            # last granule, which nothing overlaps: with ~0.3 ms and ~29 us measured on xsmall at seq_len 512 the
-            # optimum is g ~ 3.2 sqrt(N) (51 / 103 / 205 contexts at N = 256 / 1024 / 4096; a sweep over 64 / 128 / 256
-            # agrees).  An explicit preprocess batch is honoured as given.
-            if self._can_pipeline() and not batch_explicit:
-                granule = -(-int(3.2 * total_jobs**0.5) // 16) * 16
-                preprocess_batch = min(preprocess_batch, max(32, granule))
-                if preprocess_batch < total_jobs <= preprocess_batch * 3 // 2:
-                    preprocess_batch = total_jobs  # (no separate launch for a remainder of less than half a granule)
-                # (a host-stage replica keeps this granule: with many replicas the GPU owner already sees a stream of
-                # batches, and every extra batch costs a replica ~1 ms of fixed work -- measured at 1024 contexts and 31
-                # replicas: one batch per replica 27.2 k contexts/s, four 23.8 k, six 22.8 k)
-            while True:
-                batch_jobs = list(itertools.islice(job_stream, preprocess_batch))
-                if not batch_jobs:
-                    break
-                inference_jobs: list[dict[str, Any]] = []
-                t_asm = perf_counter()
-                if batch_jobs and "fragments" in batch_jobs[0]:  # the worker threads decoded them with their group
-                    fragments_per_job = [job["fragments"] for job in batch_jobs]
-                else:
-                    t0 = perf_counter()
-                    fragments_per_job = pl.fragmentize_many(  # one batch_decode over the fragments of the whole batch
-                        self.tokenizer,
-                        [(job["token_lists"], job["context_text"]) for job in batch_jobs],
-                        max_fragment_tokens,
-                        strip_sentences=strip_sentences,
-                        respect_sentence_boundaries=respect_sentence_boundaries,
-                    )
-                    timing["fragment_decode_seconds"] += perf_counter() - t0
-                for job, fragments in zip(batch_jobs, fragments_per_job):
-                    q_idx, c_idx = job["query_idx"], job["context_idx"]
-                    blocks = self._assemble_blocks_from_fragments(len(query_token_ids[q_idx]), len(sep_token_ids), fragments)
-                    states[(q_idx, c_idx)] = ContextState(
-                        sentences=job["sentences"],
-                        fragments=fragments,
-                        blocks=blocks,
-                        prefix_length=len(job["prefix_sentences"]),
-                        prefix_sentences=job["prefix_sentences"],
-                        prefix_token_counts=job["prefix_token_counts"],
-                        title_is_first_sentence=job["title_is_first_sentence"],
-                        original_text=job["context_text"],
-                    )
-                    for b_idx, block in enumerate(blocks):
-                        inference_jobs.append(
-                            {"query_idx": q_idx, "context_idx": c_idx, "block_idx": b_idx, "texts": [f.text for f in block]}
-                        )
-                assembly_time += perf_counter() - t_asm
-                if inference_jobs:
-                    inference_time += self._run_inference_batches(inference_jobs, batch_size, queries, query_token_ids, states, pending)
-                    total_blocks += len(inference_jobs)
-            if prepared is not None:
-                t_asm, t_inf, n_blocks = self._run_prepared_request(views, batch_size, queries, query_token_ids, len(sep_token_ids), states, pending)
-                assembly_time += t_asm
-                inference_time += t_inf
-                total_blocks += n_blocks
-            inference_time += self._flush_pending(pending)
-
-            if show_progress and total_blocks and is_progress_bar_enabled():
-                message = f"[OpenProvenceModel] Model inference time: {inference_time:.2f}s ({total_blocks} blocks)"
+                rq.run_raw_jobs(self, request, run, splitter, sharding.owned if sharding is not None else None, thread_workers,
+                                preprocess_batch, batch_size, timing, strip_sentences=strip_sentences,
+                                respect_sentence_boundaries=respect_sentence_boundaries)
+            run.inference_seconds += self._flush_pending(run.pending)
+            if show_progress and run.blocks and is_progress_bar_enabled():
+                message = f"[OpenProvenceModel] Model inference time: {run.inference_seconds:.2f}s ({run.blocks} blocks)"
                 if debug_callback is None:
                     print(message, flush=True)
                 else:
                     debug_callback(message)
+            result, post_time = rq.postprocess_and_gather(
+                self, request, run, sharding, threshold=threshold, always_select_title=always_select_title,
+                use_best_reranker_score=use_best_reranker_score, sentence_probability_groups_requested=return_sentence_metrics,
+                collect_sentence_texts=return_sentence_texts, first_line_as_title=first_line_as_title,
+                zero_score_when_empty=zero_score_when_empty)
 
-            (
-                pruned_l,
-                scores_l,
-                rates_l,
-                kept_l,
-                removed_l,
-                titles_l,
-                probs_l,
-                post_time,
-            ) = self._postprocess_contexts(
-                queries,
-                contexts,
-                states,
-                threshold=threshold,
-                always_select_title=always_select_title,
-                use_best_reranker_score=use_best_reranker_score,
-                sentence_probability_groups_requested=return_sentence_metrics,
-                collect_sentence_texts=return_sentence_texts,
-                first_line_as_title=first_line_as_title,
-                zero_score_when_empty=zero_score_when_empty,
-            )
-            result = pl.PostprocessResult(pruned_l, scores_l, rates_l, kept_l, removed_l, titles_l, probs_l)
-            if job_shard is not None:
-                t_gather = perf_counter()
-                gather_state["entered"] = True
-                result = self._gather_job_results(result, owned, job_shard)
-                post_time += perf_counter() - t_gather
-
-        preprocess_time = sum(timing.values())
-        hub = (getattr(self, "_dist", None) or {}).get("transport")
-        if hub is not None and hasattr(hub, "conns") and isinstance(getattr(hub, "trace", None), dict):
-            # The owner of a host-mode front-end prepares, runs and post-processes NO job of its own: its stage timers are
-            # zero and the whole call used to land under postprocess_seconds -- the field the reference's harness reads for
-            # its published timings (scripts/eval_datasets.py:225, 359-365).  From the owner's time line of the request:
-            #   preprocess  = request start -> the first forward batch of a replica is launched (the replicas' host stages
-            #                 up to their first submit; later batches overlap the forward),
-            #   inference   = that launch -> the last reply (every launch is collected synchronised before it is answered),
-            #   postprocess = the rest: the replicas' post-processing of their last blocks, their results coming back.
-            first = hub.trace.get("first_batch_seconds")
-            replies = hub.trace.get("reply_at") or []
-            if first is not None and replies:
-                total_now = perf_counter() - start_total
-                preprocess_time = float(min(first, total_now))
-                inference_time = float(min(max(replies[-1] / 1e3 - first, 0.0), total_now - preprocess_time))
-                post_time = float(max(total_now - preprocess_time - inference_time - assembly_time, 0.0))
+        preprocess_time, inference_time, post_time = rq.owner_stage_seconds(
+            self, start_total, run.assembly_seconds, (sum(timing.values()), run.inference_seconds, post_time))
         trace = ProcessPerformanceTrace(
-            preprocess_seconds=preprocess_time,
-            assembly_seconds=assembly_time,
-            inference_seconds=inference_time,
-            postprocess_seconds=post_time,
-            total_seconds=perf_counter() - start_total,
-            **timing,
-        )
-        runtime: dict[str, Any] = {}
-        if self._forward_is_native() and getattr(self, "encoder", None) is not None:
-            runtime["kernel_set"] = self.encoder.effective_policy()["kernel_set"]
-            runtime["calibration"] = self.encoder.calibration
-            runtime["fallback_from_f8"] = int(getattr(self.encoder, "fallbacks", 0))
-        if self._forward_is_native():
-            # the forwards this process enqueued (the owner of a host front-end: its replicas' merged batches) or, a
-            # host-stage replica, submitted.  A dict on purpose: as_dict() / "timing" keep numbers only
-            runtime["forwards"] = dict(forward_stats, token_budget=int(self.forward_token_budget))
-        transport = (getattr(self, "_dist", None) or {}).get("transport")
-        if transport is not None and hasattr(transport, "conns"):  # the owner of a host-mode front-end
-            runtime["host_replicas"] = len(transport.conns)
+            preprocess_seconds=preprocess_time, assembly_seconds=run.assembly_seconds, inference_seconds=inference_time,
+            postprocess_seconds=post_time, total_seconds=perf_counter() - start_total, **timing)
+        runtime = rq.runtime_facts(self, forward_stats)
         if runtime:
             object.__setattr__(trace, "runtime", runtime)  # (frozen dataclass: an attribute beside its ten fields)
         if debug_callback is not None:
-            debug_callback(
-                "[OpenProvenceModel] Timing: "
-                f"preprocess={trace.preprocess_seconds:.2f}s assembly={trace.assembly_seconds:.2f}s "
-                f"inference={trace.inference_seconds:.2f}s postprocess={trace.postprocess_seconds:.2f}s "
-                f"total={trace.total_seconds:.2f}s"
-            )
+            debug_callback(f"[OpenProvenceModel] Timing: preprocess={trace.preprocess_seconds:.2f}s assembly={trace.assembly_seconds:.2f}s "
+                           f"inference={trace.inference_seconds:.2f}s postprocess={trace.postprocess_seconds:.2f}s "
+                           f"total={trace.total_seconds:.2f}s")
 
         if reorder:
-            result = pl.PostprocessResult(
-                *self._apply_reordering(
-                    result.pruned_contexts,
-                    result.reranking_scores,
-                    result.compression_rates,
-                    result.kept_sentences,
-                    result.removed_sentences,
-                    result.titles,
-                    result.sentence_probabilities,
-                    top_k=top_k,
-                )
-            )
-
-        pruned: Any = result.pruned_contexts
-        scores: Any = result.reranking_scores
-        rates: Any = result.compression_rates
-        kept: Any = result.kept_sentences
-        removed: Any = result.removed_sentences
-        title_out: Any = result.titles
-        probs: Any = result.sentence_probabilities
-
-        if structure == "str" and result.pruned_contexts:
-            pruned = result.pruned_contexts[0][0] if result.pruned_contexts[0] else ""
-            scores = result.reranking_scores[0][0] if result.reranking_scores[0] else None
-            rates = result.compression_rates[0][0] if result.compression_rates[0] else 0.0
-            if kept is not None:
-                kept = result.kept_sentences[0][0] if result.kept_sentences[0] else []
-            if removed is not None:
-                removed = result.removed_sentences[0][0] if result.removed_sentences[0] else []
-            title_out = result.titles[0][0] if result.titles[0] else None
-            if probs is not None and probs and probs[0]:
-                probs = probs[0][0]
-        elif structure == "list" and result.pruned_contexts:
-            pruned, scores, rates = result.pruned_contexts[0], result.reranking_scores[0], result.compression_rates[0]
-            if kept is not None:
-                kept = result.kept_sentences[0]
-            if removed is not None:
-                removed = result.removed_sentences[0]
-            title_out = result.titles[0]
-            if probs is not None:
-                probs = probs[0] if probs else []
-        elif structure == "aligned" and result.pruned_contexts:
-            pruned = [e[0] if e else "" for e in result.pruned_contexts]
-            scores = [s[0] if s else None for s in result.reranking_scores]
-            rates = [r[0] if r else 0.0 for r in result.compression_rates]
-            if kept is not None:
-                kept = [v[0] if v else [] for v in result.kept_sentences]
-            if removed is not None:
-                removed = [v[0] if v else [] for v in result.removed_sentences]
-            title_out = [v[0] if v else None for v in result.titles]
-            if probs is not None:
-                probs = [v[0] if v else [] for v in probs]
-
-        payload: dict[str, Any] = {
-            "pruned_context": pruned,
-            "reranking_score": scores,
-            "compression_rate": rates,
-            "title": title_out,
-            "timing": trace.as_dict(),
-            "performance_trace": trace,
-        }
+            result = pl.apply_reordering(result, top_k)
+        pruned, scores, rates, kept, removed, title_out, probs = pl.shape_outputs(result, request.structure)
+        payload: dict[str, Any] = {"pruned_context": pruned, "reranking_score": scores, "compression_rate": rates, "title": title_out,
+                                   "timing": trace.as_dict(), "performance_trace": trace}
         if kept is not None:
             payload["kept_sentences"] = kept
         if removed is not None:

@@ -10,11 +10,12 @@ from __future__ import annotations
 
 import functools
 import math
+import operator
 import os
 import heapq
 from collections import defaultdict
 from dataclasses import dataclass, field
-from typing import Any, Callable, Mapping, Sequence
+from typing import Any, Callable, Mapping, NamedTuple, Sequence
 
 import numpy as np
 
@@ -65,6 +66,42 @@ class ContextState:
     title_is_first_sentence: bool
     original_text: str
     raw_blocks: list[tuple[int, RawPrediction]] = field(default_factory=list)
+
+
+def context_state(job: Any, fragments: list[FragmentRecord], blocks: list[list[FragmentRecord]]) -> ContextState:
+    """The state of one (query, context) pair from ``job``: a job of the job stream (a dict) or a prepared item (the same
+    fields as attributes)."""
+
+    sentences, prefix, prefix_token_counts, title_is_first, text = (_JOB_ITEMS if isinstance(job, dict) else _JOB_ATTRIBUTES)(job)
+    # (its own list of sentences: a prepared item serves many requests)
+    return ContextState(list(sentences), fragments, blocks, len(prefix), prefix, prefix_token_counts, title_is_first, text)
+
+
+_JOB_FIELDS = ("sentences", "prefix_sentences", "prefix_token_counts", "title_is_first_sentence", "context_text")
+_JOB_ITEMS, _JOB_ATTRIBUTES = operator.itemgetter(*_JOB_FIELDS), operator.attrgetter(*_JOB_FIELDS)
+
+
+def inference_job(query_idx: int, context_idx: int, block_idx: int, block: Sequence[FragmentRecord]) -> dict[str, Any]:
+    """One row of a forward: which block of which (query, context) pair, and the texts of its fragments."""
+
+    return {"query_idx": query_idx, "context_idx": context_idx, "block_idx": block_idx, "texts": [f.text for f in block]}
+
+
+def empty_stage_timing() -> dict[str, float]:
+    """The timers of the split / tokenize / fragment stages, at zero."""
+
+    return {"sentence_collect_seconds": 0.0, "sentence_normalize_seconds": 0.0, "tokenize_seconds": 0.0,
+            "fragment_split_seconds": 0.0, "fragment_decode_seconds": 0.0}
+
+
+def max_fragment_tokens(max_length: int, respect_sentence_boundaries: bool) -> int:
+    """The longest fragment a sentence is cut into: half a row, or -- sentences kept whole -- a row without its specials."""
+
+    return max(16, max_length - 2) if respect_sentence_boundaries else max(16, max_length // 2)
+
+
+def tokenize_query(tokenizer: Any, query: str) -> list[int]:
+    return [int(t) for t in tokenizer.encode(query, add_special_tokens=False)]
 
 
 # ---------------------------------------------------------------------------------------------
@@ -805,6 +842,53 @@ def auto_tune_preprocess_loader(
     return workers, batch, prefetch
 
 
+class LoaderSettings(NamedTuple):
+    workers: int
+    preprocess_batch: int
+    prefetch: int | None
+    workers_explicit: bool
+    batch_explicit: bool
+    prefetch_explicit: bool
+
+
+def loader_settings(preprocess_workers: int | None, preprocess_batch_size: int | None, batch_size: int,
+                    torch_dataloader_kwargs: Mapping[str, Any] | None, env_workers: str | None) -> LoaderSettings:
+    """What the caller said about the preprocess loader, before :func:`auto_tune_preprocess_loader` settles the rest:
+    workers (``preprocess_workers``, else a positive OPEN_PROVENCE_PREPROCESS_WORKERS = ``env_workers``, else the host's
+    default), the preprocess batch (= cap of blocks per inference pass, as the reference computes it), the prefetch factor,
+    and which of the three were given explicitly; ``torch_dataloader_kwargs`` overrides each of them."""
+
+    env_count = 0
+    if env_workers:
+        try:
+            env_count = int(env_workers)
+        except ValueError:
+            env_count = 0
+    if preprocess_workers is not None:
+        workers = max(0, int(preprocess_workers))
+    else:
+        workers = env_count if env_count > 0 else default_preprocess_workers()
+    preprocess_batch = max(1, int(preprocess_batch_size or batch_size))
+    workers_explicit = preprocess_workers is not None or env_count > 0
+    batch_explicit = preprocess_batch_size is not None
+    prefetch_explicit = False
+    prefetch: int | None = None
+    if torch_dataloader_kwargs:
+        custom = dict(torch_dataloader_kwargs)
+        if "num_workers" in custom:
+            workers_explicit = True
+            workers = int(custom["num_workers"])
+        if "batch_size" in custom:
+            batch_explicit = True
+            preprocess_batch = int(custom["batch_size"])
+        if "prefetch_factor" in custom:
+            prefetch_explicit = True
+            raw_prefetch = custom["prefetch_factor"]
+            if isinstance(raw_prefetch, (int, float)) or (isinstance(raw_prefetch, str) and raw_prefetch.isdigit()):
+                prefetch = int(raw_prefetch)
+    return LoaderSettings(workers, preprocess_batch, prefetch, workers_explicit, batch_explicit, prefetch_explicit)
+
+
 # ---------------------------------------------------------------------------------------------
 # post-processing (ref: _postprocess_contexts :2962-3202)
 # ---------------------------------------------------------------------------------------------
@@ -817,6 +901,12 @@ class PostprocessResult:
     removed_sentences: list[list[list[str]]] | None
     titles: list[list[Any]]
     sentence_probabilities: list[list[list[float]]] | None
+
+    def as_tuple(self) -> tuple:
+        """The seven lists themselves, in field order (the reference's entry points return them so)."""
+
+        return (self.pruned_contexts, self.reranking_scores, self.compression_rates, self.kept_sentences, self.removed_sentences,
+                self.titles, self.sentence_probabilities)
 
 
 def mean_f32_slice(values: np.ndarray) -> float:
@@ -1068,3 +1158,47 @@ def apply_reordering(result: PostprocessResult, top_k: int | None) -> Postproces
         if new.sentence_probabilities is not None:
             new.sentence_probabilities.append(pick(result.sentence_probabilities[q_idx], order))
     return new
+
+
+# ---------------------------------------------------------------------------------------------
+# the shape the caller gets back (ref: process :3740-3790)
+# ---------------------------------------------------------------------------------------------
+def shape_outputs(result: PostprocessResult, structure: str) -> tuple[Any, Any, Any, Any, Any, Any, Any]:
+    """Per-query, per-context result lists -> (pruned, scores, rates, kept, removed, titles, probabilities) in the shape of
+    the request (``normalize_inputs``): ``"str"`` one context of one query, ``"list"`` the contexts of one query,
+    ``"aligned"`` one context per query, anything else (``"nested"``) as they are.  ``kept`` / ``removed`` / ``probabilities``
+    stay None when they were not asked for; a result without queries keeps its lists."""
+
+    pruned, scores, rates, kept, removed, titles, probs = result.as_tuple()
+    if structure == "str" and result.pruned_contexts:
+        pruned = result.pruned_contexts[0][0] if result.pruned_contexts[0] else ""
+        scores = result.reranking_scores[0][0] if result.reranking_scores[0] else None
+        rates = result.compression_rates[0][0] if result.compression_rates[0] else 0.0
+        if kept is not None:
+            kept = result.kept_sentences[0][0] if result.kept_sentences[0] else []
+        if removed is not None:
+            removed = result.removed_sentences[0][0] if result.removed_sentences[0] else []
+        titles = result.titles[0][0] if result.titles[0] else None
+        if probs is not None and probs and probs[0]:
+            probs = probs[0][0]
+    elif structure == "list" and result.pruned_contexts:
+        pruned, scores, rates = result.pruned_contexts[0], result.reranking_scores[0], result.compression_rates[0]
+        if kept is not None:
+            kept = result.kept_sentences[0]
+        if removed is not None:
+            removed = result.removed_sentences[0]
+        titles = result.titles[0]
+        if probs is not None:
+            probs = probs[0] if probs else []
+    elif structure == "aligned" and result.pruned_contexts:
+        pruned = [e[0] if e else "" for e in result.pruned_contexts]
+        scores = [s[0] if s else None for s in result.reranking_scores]
+        rates = [r[0] if r else 0.0 for r in result.compression_rates]
+        if kept is not None:
+            kept = [v[0] if v else [] for v in result.kept_sentences]
+        if removed is not None:
+            removed = [v[0] if v else [] for v in result.removed_sentences]
+        titles = [v[0] if v else None for v in result.titles]
+        if probs is not None:
+            probs = [v[0] if v else [] for v in probs]
+    return pruned, scores, rates, kept, removed, titles, probs

@@ -162,14 +162,18 @@ class _RecordingRemote:
 
     def __init__(self):
         self.launches = []
+        self.submitted = []  # (rows, segments) of the forwards not yet answered, in order
 
     def submit(self, rows, segments):
-        self.launches.append([len(r) for r in rows])
-        return {"remote": self, "rows": rows, "segments": segments}
+        from open_provence_amd.launches import RemoteLaunch
 
-    def result(self, handle):
+        self.launches.append([len(r) for r in rows])
+        self.submitted.append((rows, segments))
+        return RemoteLaunch(remote=self, rows=len(rows), cu=None, seg_counts=[len(s) for s in segments])
+
+    def result(self, launch):
         ranks, means = [], []
-        for row, segs in zip(handle["rows"], handle["segments"]):
+        for row, segs in zip(*self.submitted.pop(0)):
             out = golden_stub_forward(input_ids=torch.tensor([row], dtype=torch.long))
             keep = torch.softmax(out["pruning_logits"][0], dim=-1)[:, 1].numpy()
             ranks.append(out["ranking_logits"][0])

@@ -235,7 +235,7 @@ def test_gather_on_a_real_sub_group_translates_the_root_rank(tmp_path):
 
 
 def _collect_worker(rank, world, port, out_path):
-    """The group form of the pipelined collect (modeling._collect_rows_sharded) on fabricated launch handles: each
+    """The group form of the pipelined collect (launches.collect_rows_sharded) on fabricated launch handles: each
     rank holds the fragment means + ranking logits of ITS rows, rank 0 must get every row's values in row order."""
 
     import sys
@@ -245,6 +245,7 @@ def _collect_worker(rank, world, port, out_path):
     sys.path.insert(0, str(Path(__file__).resolve().parent))
     from helpers import CharTokenizer, host_only_model
 
+    from open_provence_amd.launches import Launch
     from open_provence_amd.sharding import ShardPlan
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
@@ -262,10 +263,10 @@ def _collect_worker(rank, world, port, out_path):
             per_row = counts if with_segments else lengths
             vals = np.concatenate([np.arange(per_row[i], dtype=np.float32) + 1000.0 * i for i in mine]) if mine else np.zeros(0, np.float32)
             rk = np.asarray([[float(i), -float(i)] for i in mine], dtype=np.float32).reshape(-1)
-            handle = {"event": None, "pool": {"keep_np": vals, "rank_np": rk}, "total": int(sum(lengths[i] for i in mine)),
-                      "rows": len(mine), "cu": None, "seg_counts": [counts[i] for i in mine] if with_segments else None, "alive": None,
-                      "shard": {"mine": mine, "n_rows_all": len(lengths), "lengths": lengths, "shards": plan.shards,
-                                "counts_all": counts if with_segments else None}}
+            handle = Launch(event=None, pool={"keep_np": vals, "rank_np": rk}, total=int(sum(lengths[i] for i in mine)),
+                            rows=len(mine), cu=None, seg_counts=[counts[i] for i in mine] if with_segments else None, alive=None,
+                            shard={"mine": mine, "n_rows_all": len(lengths), "lengths": lengths, "shards": plan.shards,
+                                   "counts_all": counts if with_segments else None})
             rank_all, rows_out = model._collect_rows(handle)
             assert rank_all.shape == (len(lengths), 2) and len(rows_out) == len(lengths)
             if rank == 0:
