@@ -25,7 +25,7 @@ _COMMON = [CSRC / "opk_common.hip.h"]
 _ROWGEMM = [CSRC / name for name in ("opk_rowgemm.hip.h", "opk_rowgemm_pack.hip.h", "opk_rowgemm_stream.hip.h", "opk_rowgemm_ln.hip.h", "opk_kstream.hip.h",
                                      "opk_rowgemm_phase1.hip.h", "opk_rowgemm_mlp.hip.h", "opk_rowgemm_mlp_ops.inc", "opk_rowgemm_mlp_loop.inc",
                                      "opk_rowgemm_qkv_pairs.hip.h", "opk_rowgemm_chunks.hip.h")]
-_INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "opk_f32.hip.h", CSRC / "opk_attn.hip.h", CSRC / "opk_attn_probs.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
+_INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "op_policy.h", CSRC / "opk_f32.hip.h", CSRC / "opk_attn.hip.h", CSRC / "opk_attn_probs.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
 
 _PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
 _AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
@@ -35,7 +35,8 @@ _ASSEMBLE = CSRC / "opk_assemble.hip.h"  # prepared contexts: rows laid out on t
 
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
-    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_sets.h", CSRC / "opk_small.hip.h", CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, _POOL, INCLUDE]),
+    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_plan.h", CSRC / "op_kernel_sets.h", CSRC / "op_sets.h", CSRC / "opk_small.hip.h",
+                                                      CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, _POOL, INCLUDE]),
     ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"], _INTERNAL),
     ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"], _INTERNAL),
     ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"], _INTERNAL),
@@ -117,7 +118,10 @@ def build(force: bool = False, verbose: bool = False) -> Path:
         (BUILD_DIR / f"{name}.sha256").write_text(_unit_digest(unit))
 
     todo = [u for u in UNITS if force or _unit_is_stale(u)]
-    with ThreadPoolExecutor(max_workers=min(len(todo), os.cpu_count() or 4) or 1) as pool:
+    # MAX_JOBS where it is set; else the CPUs, but at most 16: a shared machine shows many times what one command may use
+    max_jobs = os.environ.get("MAX_JOBS", "").strip()
+    jobs = int(max_jobs) if max_jobs.isdigit() and int(max_jobs) > 0 else min(os.cpu_count() or 4, 16)
+    with ThreadPoolExecutor(max_workers=max(1, min(len(todo), jobs))) as pool:
         list(pool.map(compile_unit, todo))
     link = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(OUTPUT), *[str(BUILD_DIR / f"{u[0]}.o") for u in UNITS]]
     if verbose:

@@ -16,6 +16,7 @@
 
 #define OPK_PACK_KERNELS 1
 #include "op_internal.h"
+#include "op_plan.h"
 #include "op_sets.h"
 #include "opk_small.hip.h"
 #include "opk_pool.hip.h"
@@ -26,6 +27,11 @@
 using namespace opk;
 using opl::Policy;
 using namespace ops;
+using opp::AttnPlan;
+using opp::align_up;
+using opp::align_up_sz;
+
+static_assert(opp::ROW_ALIGN == opk::ROW_ALIGN, "op_plan.h chunks a batch by the kernels' row alignment");
 
 namespace {
 
@@ -146,6 +152,8 @@ int fail(op_handle* h, int code, const char* fmt, ...) {
   return code;
 }
 
+int fail(op_handle* h, const opp::Refusal& r) { return fail(h, r.code, "%s", r.text); }
+
 #define OP_HIP(h, expr)                                                                              \
   do {                                                                                               \
     hipError_t _e = (expr);                                                                          \
@@ -162,8 +170,6 @@ int dev_alloc(op_handle* h, T** out, size_t count) {
   return OP_OK;
 }
 
-inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
-inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 void erase_missing(op_handle* h, const std::string& name) {
   auto it = std::find(h->missing.begin(), h->missing.end(), name);
@@ -254,64 +260,29 @@ struct Workspace {
   size_t bytes;
 };
 
-// rows the largest chunk can hold (before the +64 slack / 128 rounding)
+// the rows a workspace of this geometry is carved for (op_workspace_bytes, op_forward_packed and the attention side passes)
 int chunk_row_capacity(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen) {
-  const long upper = (long)total_tokens + (long)(ROW_ALIGN - 1) * n_seqs;
-  const long all_rows = align_up((int)std::min<long>(upper, 1L << 30), ROW_ALIGN);
-  const int one_seq = align_up(std::max(max_seqlen, 1), ROW_ALIGN);
-  const long cap = std::max(h->chunk_rows, one_seq);
-  return (int)std::min<long>(all_rows, cap);
+  return opp::chunk_row_capacity(h->chunk_rows, n_seqs, total_tokens, max_seqlen);
 }
 
-// Every region is handed out through WS_TAKE: the member's own name and what it holds go to `layout` (op_debug_workspace_layout),
-// so a region added here is reported without a second list to keep in step.
-// f32: the planes of kernel set "fp32" follow the regions every set has (whose offsets therefore never move).
-void carve(const op_handle* h, char* base, int cap_rows_pad, int n_seqs, bool f32, Workspace& ws,
-           std::vector<op_workspace_region>* layout = nullptr) {
-  size_t off = 0;
-  auto take = [&](const char* name, int kind, size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    if (layout) layout->push_back(op_workspace_region{name, (uint64_t)off, (uint64_t)bytes, (int32_t)kind});
-    off += align_up_sz(bytes, 256);
-    return p;
-  };
-#define WS_TAKE(member, kind, bytes) ws.member = reinterpret_cast<decltype(ws.member)>(take(#member, kind, bytes))
-  const size_t R = (size_t)cap_rows_pad;
-  const size_t H = (size_t)h->H, I = (size_t)h->I;
-  WS_TAKE(x, OP_WS_FLOAT, R * H * 4);
-  WS_TAKE(ln_hi, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(ln_lo, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(q_hi, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(q_lo, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(k_hi, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(k_lo, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(vt_hi, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(vt_lo, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(o_hi, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(o_lo, OP_WS_FLOAT, R * H * 2);
-  WS_TAKE(h_hi, OP_WS_FLOAT, R * I * 2);
-  WS_TAKE(h_lo, OP_WS_FLOAT, R * I * 2);
-  WS_TAKE(row_seq, OP_WS_INDEX, R * 4);
-  WS_TAKE(row_pos, OP_WS_INDEX, R * 4);
-  WS_TAKE(row_tok, OP_WS_INDEX, R * 4);
-  WS_TAKE(roff, OP_WS_INDEX, ((size_t)n_seqs + 1) * 4);
-  WS_TAKE(qboff, OP_WS_INDEX, ((size_t)n_seqs + 1) * 4);
-  WS_TAKE(qboff_l, OP_WS_INDEX, ((size_t)n_seqs + 1) * 4);
-  WS_TAKE(cls, OP_WS_FLOAT, std::max<size_t>((size_t)n_seqs, 1) * H * 4);
-  WS_TAKE(range_flag, OP_WS_FLAG, sizeof(int));
+// the regions of a forward's workspace for a batch of this geometry; f32: with the planes of kernel set "fp32"
+opp::Layout forward_layout(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen, bool f32) {
+  return opp::workspace_layout(h->H, h->I, opp::padded_row_capacity(h->chunk_rows, n_seqs, total_tokens, max_seqlen), n_seqs, f32);
+}
+
+// The workspace's pointers from its layout, region by region: generated from the same list as the layout (op_plan.h).
+void carve(const opp::Layout& lay, char* base, Workspace& ws) {
+  int i = 0;
+#define WS_TAKE(member, kind, bytes) ws.member = reinterpret_cast<decltype(ws.member)>(base + lay.regions[i++].offset);
+  OPP_WORKSPACE_REGIONS(WS_TAKE)
 #undef WS_TAKE
   ws.f = WorkspaceF32{};
-  if (f32) {
-#define WS_TAKE_F32(member, bytes) ws.f.member = reinterpret_cast<float*>(take(#member "_f", OP_WS_FLOAT, bytes))
-    WS_TAKE_F32(ln, R * H * 4);
-    WS_TAKE_F32(q, R * H * 4);
-    WS_TAKE_F32(k, R * H * 4);
-    WS_TAKE_F32(v, R * H * 4);
-    WS_TAKE_F32(o, R * H * 4);
-    WS_TAKE_F32(h, R * I * 4);
+  if (i < lay.n) {  // the planes of kernel set "fp32"
+#define WS_TAKE_F32(member, bytes) ws.f.member = reinterpret_cast<float*>(base + lay.regions[i++].offset);
+    OPP_WORKSPACE_F32_PLANES(WS_TAKE_F32)
 #undef WS_TAKE_F32
   }
-  ws.bytes = off;
+  ws.bytes = lay.bytes;
 }
 
 template <int EPI>
@@ -352,10 +323,17 @@ struct HiddenReq {
   bool full(int index) const { return !slot.empty() && slot[index] >= 0; }
 };
 
-struct AttnPlan {
-  int waves_g;  // waves per block of the full-attention layers (8 or 4); sliding-window layers always use 4
-  int items_g;  // work items (sequence, query block) of a full-attention layer
-  int items_l;  // ... of a sliding-window layer (128-query blocks)
+// A packed batch as an entry point receives it, filled once there and passed down by reference.  Calls that take only part
+// of it (the attention side passes: no ids, no outputs) leave the rest null.
+struct PackedBatch {
+  const int32_t* ids_dev = nullptr;
+  const int32_t* cu_dev = nullptr;
+  const int32_t* cu_host = nullptr;  // the caller's host copy of cu_dev, or NULL: read back (host_cu_seqlens)
+  int n_seqs = 0, total_tokens = 0, max_seqlen = 0;
+  float *prune_out = nullptr, *rank_out = nullptr, *keep_prob = nullptr;
+  void* workspace = nullptr;
+  size_t workspace_bytes = 0;
+  hipStream_t stream = nullptr;
 };
 
 // One chunk of sequences through the whole encoder: the launch sequence of a forward.  The arguments and what every path
@@ -364,11 +342,9 @@ struct ChunkPass {
   op_handle* h;
   Launcher& L;
   const Workspace& ws;
-  const int32_t* ids_dev;
-  const int32_t* cu_dev;
-  int s0, ns, rows, max_len, total_tokens;
+  const PackedBatch& b;  // the whole batch: ids, cu_seqlens, outputs
+  int s0, ns, rows, max_len;  // this chunk: sequences [s0, s0 + ns), its rows and its longest sequence
   const AttnPlan& plan;
-  float *prune_out, *rank_out, *keep_prob;
   const HiddenReq* hid;  // per-call hidden-state request, or nullptr
 
   int H, I;
@@ -379,7 +355,7 @@ struct ChunkPass {
   Policy E, V;  // evaluated policy, instantiated kernel set (V has every term of E)
   int pi;       // ... its opl::kPolicies index
   bool clr_q, clr_k, clr_v, clr_o, clr_h, clr_ln_attn, clr_ln_mlp, zero_p_lo, split;
-  // the operand formats of the handle's kernel set (h->ks, op_sets.h), decided once here
+  // the operand formats of the handle's kernel set (h->ks, op_kernel_sets.h), decided once here
   bool o_f8, f16, f32, attn16, wi8, wlo8, range_flagged, embed_in_qkv0;
   bool mlp8[OP_MAX_LAYERS];  // sets 8 / 9, per layer: the MLP in the fp16 + e4m3 format
   PackFmt fmt_base, fmt_f8, fmt_side, fmt_wi;  // weight packs: layer-0 q / k / v, the fp16 + e4m3 GEMMs, attention side, Wi
@@ -393,11 +369,9 @@ struct ChunkPass {
   bool head_done = false;
   int hidden_stored = -1;  // the hidden-state entry the last layer launch stored itself (wave-pair kernel), -1: none
 
-  ChunkPass(op_handle* h_, Launcher& L_, const Workspace& ws_, const int32_t* ids_dev_, const int32_t* cu_dev_, int s0_, int ns_, int rows_,
-            int max_len_, int total_tokens_, const AttnPlan& plan_, float* prune_out_, float* rank_out_, float* keep_prob_,
-            const HiddenReq* hid_)
-      : h(h_), L(L_), ws(ws_), ids_dev(ids_dev_), cu_dev(cu_dev_), s0(s0_), ns(ns_), rows(rows_), max_len(max_len_),
-        total_tokens(total_tokens_), plan(plan_), prune_out(prune_out_), rank_out(rank_out_), keep_prob(keep_prob_), hid(hid_) {
+  ChunkPass(op_handle* h_, Launcher& L_, const Workspace& ws_, const PackedBatch& b_, int s0_, int ns_, int rows_, int max_len_,
+            const AttnPlan& plan_, const HiddenReq* hid_)
+      : h(h_), L(L_), ws(ws_), b(b_), s0(s0_), ns(ns_), rows(rows_), max_len(max_len_), plan(plan_), hid(hid_) {
     H = h->H;
     I = h->I;
     // Row path: exactly the computed rows, rounded to the 128-row block -- no slack rows: a 131072-row batch is 1024
@@ -472,12 +446,12 @@ struct ChunkPass {
   // row map, the range flag, padding rows of the attention output, embeddings
   int prologue() {
     OP_TRY(L.begin(PK_ROWMAP));
-    hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, st, cu_dev, s0, ns, ROW_ALIGN, ROW_ALIGN, ws.roff);
+    hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, st, b.cu_dev, s0, ns, ROW_ALIGN, ROW_ALIGN, ws.roff);
     if (fp_layout) {
-      hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, st, cu_dev, s0, ns, plan.waves_g * 32, 1, ws.qboff);
-      hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, st, cu_dev, s0, ns, 128, 1, ws.qboff_l);
+      hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, st, b.cu_dev, s0, ns, plan.waves_g * 32, 1, ws.qboff);
+      hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, st, b.cu_dev, s0, ns, 128, 1, ws.qboff_l);
     }
-    hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, st, cu_dev, s0, ns, ws.roff,
+    hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, st, b.cu_dev, s0, ns, ws.roff,
                        r_pad, ws.row_seq, ws.row_pos, ws.row_tok);
     OP_TRY(L.end());
 
@@ -504,10 +478,10 @@ struct ChunkPass {
     if (!embed_in_qkv0) {
       OP_TRY(L.begin(PK_EMBED_LN));
       if (split)
-        hipLaunchKernelGGL((embed_ln_kernel<true>), dim3(row_blocks), dim3(256), 0, st, ids_dev, ws.row_tok, h->emb,
+        hipLaunchKernelGGL((embed_ln_kernel<true>), dim3(row_blocks), dim3(256), 0, st, b.ids_dev, ws.row_tok, h->emb,
                            h->emb_norm, h->cfg.norm_eps, H, r_pad, h->V, ws.x, ws.ln_hi, ws.ln_lo);
       else
-        hipLaunchKernelGGL((embed_ln_kernel<false>), dim3(row_blocks), dim3(256), 0, st, ids_dev, ws.row_tok, h->emb,
+        hipLaunchKernelGGL((embed_ln_kernel<false>), dim3(row_blocks), dim3(256), 0, st, b.ids_dev, ws.row_tok, h->emb,
                            h->emb_norm, h->cfg.norm_eps, H, r_pad, h->V, ws.x, ws.ln_hi, ws.ln_lo);
       OP_TRY(L.end());
     }
@@ -518,7 +492,7 @@ struct ChunkPass {
     if (!h->capture) return OP_OK;
     OP_TRY(L.begin(PK_CAPTURE));
     hipLaunchKernelGGL(capture_rows_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, ws.row_tok, H, r_pad,
-                       h->capture + (size_t)index * total_tokens * H);
+                       h->capture + (size_t)index * b.total_tokens * H);
     return L.end();
   }
 
@@ -542,7 +516,7 @@ struct ChunkPass {
     if (!hid || !hid->pooled(index)) return OP_OK;
     OP_TRY(L.begin(PK_CAPTURE));
     hipLaunchKernelGGL(pool_hidden_kernel, dim3((unsigned)ns, (unsigned)((H + POOL_COLS - 1) / POOL_COLS)), dim3(256), 0, st, hid->scratch,
-                       cu_dev, s0, total_tokens, H, hid->pool_kind, hid->pool_out + (size_t)hid->pool_slot[index] * (size_t)hid->n_seqs * H);
+                       b.cu_dev, s0, b.total_tokens, H, hid->pool_kind, hid->pool_out + (size_t)hid->pool_slot[index] * (size_t)hid->n_seqs * H);
     if (hid->full(index))
       hipLaunchKernelGGL(hidden_repack_kernel, dim3(row_blocks), dim3(256), 0, st, hid->scratch, H, r_pad, ws.row_tok, ws.row_seq,
                          ws.row_pos, s0, hid->pad, hid->bf16, hid->out + (size_t)hid->slot[index] * hid->entry_bytes);
@@ -570,7 +544,7 @@ struct ChunkPass {
       ap.vt_fp = ws.vt_hi;
       ap.o_fp = ws.o_hi;
       ap.o_lo8 = ws.o_lo;
-      ap.cu = cu_dev;
+      ap.cu = b.cu_dev;
       ap.s0 = s0;
       ap.roff = ws.roff;
       ap.qboff = is_global ? ws.qboff : ws.qboff_l;
@@ -601,7 +575,7 @@ struct ChunkPass {
       ap.vt_lo = ws.vt_lo;
       ap.o_hi = ws.o_hi;
       ap.o_lo = ws.o_lo;
-      ap.cu = cu_dev;
+      ap.cu = b.cu_dev;
       ap.s0 = s0;
       ap.roff = ws.roff;
       ap.H = H;
@@ -664,7 +638,7 @@ struct ChunkPass {
       RowGemmParams rp = qkv_params(0);
       if (embed_in_qkv0) {
         rp.emb_table = h->emb;
-        rp.emb_ids = ids_dev;
+        rp.emb_ids = b.ids_dev;
         rp.emb_vocab = h->V;
         rp.row_tok = ws.row_tok;
         rp.ln_w = h->emb_norm;
@@ -754,8 +728,8 @@ struct ChunkPass {
         rl.fin_pb = h->prune_b;
         rl.row_tok = ws.row_tok;
         rl.row_seq = ws.row_seq;
-        rl.fin_prune = prune_out;
-        rl.fin_keep = keep_prob;
+        rl.fin_prune = b.prune_out;
+        rl.fin_keep = b.keep_prob;
         rl.fin_cls = ws.cls;
         rl.fin_pre_norm = h->cfg.prune_pre_final_norm ? 1 : 0;
         head_done = true;
@@ -1061,7 +1035,7 @@ struct ChunkPass {
     ap.k = ws.f.k;
     ap.v = ws.f.v;
     ap.o = ws.f.o;
-    ap.cu = cu_dev;
+    ap.cu = b.cu_dev;
     ap.s0 = s0;
     ap.roff = ws.roff;
     ap.H = H;
@@ -1100,19 +1074,19 @@ struct ChunkPass {
       OP_TRY(hidden(h->N, h->cfg.prune_pre_final_norm ? nullptr : h->final_norm));
       OP_TRY(L.begin(PK_FINAL_LN_PRUNE));
       hipLaunchKernelGGL(final_ln_prune_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, h->final_norm, h->cfg.norm_eps, H,
-                         r_pad, ws.row_tok, ws.row_seq, ws.row_pos, h->prune_w, h->prune_b, prune_out, keep_prob,
+                         r_pad, ws.row_tok, ws.row_seq, ws.row_pos, h->prune_w, h->prune_b, b.prune_out, b.keep_prob,
                          h->cfg.prune_pre_final_norm ? 1 : 0, mean_pool, ws.cls,
-                         h->capture ? h->capture + (size_t)h->N * total_tokens * H : nullptr,
+                         h->capture ? h->capture + (size_t)h->N * b.total_tokens * H : nullptr,
                          range_flagged ? ws.range_flag : nullptr);
       OP_TRY(L.end());
     }
     OP_TRY(L.begin(PK_RANK_HEAD));
     if (f32)
-      opl::launch_f32_rank_head(st, ns, ws.cls, ws.x, cu_dev, s0, ws.roff, mean_pool, H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps,
-                                h->cls_w, h->cls_b, rank_out);
+      opl::launch_f32_rank_head(st, ns, ws.cls, ws.x, b.cu_dev, s0, ws.roff, mean_pool, H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps,
+                                h->cls_w, h->cls_b, b.rank_out);
     else
-      hipLaunchKernelGGL(rank_head_kernel, dim3((unsigned)ns), dim3(256), 0, st, ws.cls, ws.x, cu_dev, s0, ws.roff, mean_pool,
-                       H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps, h->cls_w, h->cls_b, rank_out,
+      hipLaunchKernelGGL(rank_head_kernel, dim3((unsigned)ns), dim3(256), 0, st, ws.cls, ws.x, b.cu_dev, s0, ws.roff, mean_pool,
+                       H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps, h->cls_w, h->cls_b, b.rank_out,
                        range_flagged ? ws.range_flag : nullptr);
     OP_TRY(L.end());
     return OP_OK;
@@ -1136,11 +1110,6 @@ struct ChunkPass {
   }
 };
 
-int forward_chunk(op_handle* h, Launcher& L, const Workspace& ws, const int32_t* ids_dev, const int32_t* cu_dev, int s0,
-                  int ns, int rows, int max_len, int total_tokens, const AttnPlan& plan, float* prune_out, float* rank_out,
-                  float* keep_prob, const HiddenReq* hid) {
-  return ChunkPass(h, L, ws, ids_dev, cu_dev, s0, ns, rows, max_len, total_tokens, plan, prune_out, rank_out, keep_prob, hid).run();
-}
 
 // Every packed form of one GEMM weight tensor (op_load_weight), on the null stream: one method per packing kernel.
 struct WeightPacker {
@@ -1307,13 +1276,10 @@ int op_create(const op_config* cfg, op_handle** out) {
   h->req = h->eff = req;
   h->chunk_rows = cfg->chunk_rows > 0 ? align_up(cfg->chunk_rows, ROW_ALIGN) : 262144;  // grids must cover the chip several times over
   h->layers.resize(N);
-  // H % 64 and I % 32: every row-GEMM streams an EVEN number of 32-feature chunks on each side of the q/k -> v
-  // boundary (H/16 q/k chunks, H/32 v chunks, H/32 out-projection chunks, I/16 Wi chunks) -- rowgemm_kernel's
-  // two-stage loop is unrolled by two.
-  const bool force_tiled = (cfg->flags & OP_FLAG_FORCE_TILED) != 0;
-  h->row_path = (H <= 256) && (H % 64 == 0) && (I % 32 == 0) && !force_tiled;
-  // panels of 256 output features (4 heads; 128 GeGLU input + 128 gate columns), an even number of k-steps
-  h->panel_path = !h->row_path && (H % 256 == 0) && (I % 128 == 0) && !force_tiled;
+  // the dispatch path of this shape (opp::paths_of)
+  const opp::Paths paths = opp::paths_of(H, I, (unsigned)cfg->flags);
+  h->row_path = paths.row;
+  h->panel_path = paths.panel;
 
 #define OP_CREATE_TRY(expr)  \
   do {                       \
@@ -1345,16 +1311,11 @@ int op_create(const op_config* cfg, op_handle** out) {
   OP_CREATE_HIP(hipMemset(h->any_lo_dev, 0, (OP_FAM_COUNT + 3) * sizeof(int)));
   OP_CREATE_TRY(dev_alloc(h, &h->f16_fit_dev, 2));
   OP_CREATE_HIP(hipMemset(h->f16_fit_dev, 0, 2 * sizeof(float)));
-  // panel path: opt-in (OP_FLAG_PANEL_F8) -- at the depth of the published models (19-25 layers) the format's error
-  // reaches 0.45-1.0e-3 on logits, the (hi, lo) bf16 sets stay at 0.2-0.5e-3 (scripts/f8_depth_check.py)
-  // (panel path: the packs are always built -- the Wi GEMM takes the format by default for fp32-valued weights, see
-  // resolve_policy; OP_FLAG_PANEL_F8 extends it to every GEMM of the layer)
-  h->f8_packs = ((h->row_path && (H / 32) % 4 == 0) || h->panel_path) && !(cfg->flags & OP_FLAG_NO_F8);
-  // kernel set "f16": whole-layer kernel shapes (hidden 128 / 256) or the panel path; never with the A/B flags that pick
-  // another layer structure
-  h->h16_packs = ((h->row_path && (H == 128 || H == 256)) || h->panel_path) &&
-                 !(cfg->flags & (OP_FLAG_NO_F8 | OP_FLAG_NO_LAYER_FUSION | OP_FLAG_NO_POLICY_KERNELS));
-  h->f32_packs = (cfg->flags & OP_FLAG_F32_PACKS) != 0;
+  // the weight packs this shape and these flags build (opp::packs_of)
+  const opp::Packs packs = opp::packs_of(paths, H, (unsigned)cfg->flags);
+  h->f8_packs = packs.f8;
+  h->h16_packs = packs.h16;
+  h->f32_packs = packs.f32;
   OP_CREATE_TRY(dev_alloc(h, &h->emb, (size_t)h->V * H));
   OP_CREATE_TRY(dev_alloc(h, &h->emb_norm, H));
   OP_CREATE_TRY(dev_alloc(h, &h->final_norm, H));
@@ -1522,36 +1483,24 @@ int op_load_weight(op_handle* h, const char* name_c, const void* data, int dtype
 }  // extern "C"
 
 namespace {
-// Can this handle run kernel set `set` (op_kernel_set numbering)?  Packs present, a path that has the kernels, and no
-// weight tensor below the reach of an fp16 plane for the sets that carry one: the set's `needs` (op_sets.h).
-bool set_available(const op_handle* h, int set) {
-  if (set < 0 || set >= OP_KS_COUNT) return false;
-  const unsigned needs = kKernelSets[set].needs;
-  if ((needs & NEED_F32_PACKS) && !h->f32_packs) return false;
-  if (h->cfg.flags & OP_FLAG_NO_POLICY_KERNELS) return set == OP_KS_BF16X3 || set == OP_KS_F32;
-  if ((needs & NEED_FAST) && !h->row_path && !h->panel_path) return false;
-  if ((needs & NEED_PANEL) && !h->panel_path) return false;
-  if ((needs & NEED_F8_PACKS) && !h->f8_packs) return false;
-  if ((needs & NEED_H16_PACKS) && !h->h16_packs) return false;
-  if ((needs & NEED_F16_FIT) && h->f16_unfit) return false;
-  if ((needs & NEED_ROW_LAYER) && h->row_path && (h->cfg.flags & (OP_FLAG_NO_LAYER_FUSION | OP_FLAG_LAYER_8X16 | OP_FLAG_LAYER_M32)))
-    return false;
-  return true;
+// what selection reads from the handle (the device flags: resolve_policy)
+opp::SelectState select_state(const op_handle* h) {
+  opp::SelectState s;
+  s.req = h->req;
+  s.f16_unfit = h->f16_unfit;
+  s.row_path = h->row_path;
+  s.panel_path = h->panel_path;
+  s.f8_packs = h->f8_packs;
+  s.h16_packs = h->h16_packs;
+  s.f32_packs = h->f32_packs;
+  s.f8_off = h->f8_off;
+  s.flags = h->cfg.flags;
+  s.forced_set = h->forced_set;
+  s.forced_mlp_layers = h->forced_mlp_layers;
+  return s;
 }
 
-// MFMA pipe time per algorithmic product of a kernel set on this handle's path: op_calibrate's order of candidates
-float set_cost(const op_handle* h, int set) { return h->panel_path ? kKernelSets[set].cost_panel : kKernelSets[set].cost_row; }
-
-// The forward runs kernel set `set`; -1: the all-terms kernels with the lo operands `eff` does not carry cleared.
-void use_set(op_handle* h, int set) {
-  h->set = set;
-  h->ks = set >= 0 ? &kKernelSets[set] : &kClearedOperands;
-  h->mlp_layers = (mlp_by_layer(*h->ks) && set == h->forced_set) ? h->forced_mlp_layers : ~0ull;
-}
-
-// Evaluated policy = requested policy minus the hi x lo(weight) terms whose lo planes are identically zero for this
-// checkpoint (bf16 weights: dropping the term changes no bit of the result), then the kernel set that has exactly those
-// terms -- or the all-terms kernels with the unused lo operands cleared.
+// The weights' flags from the device, the selection (opp::select), the result into the handle.
 int resolve_policy(op_handle* h) {
   if (h->resolved) return OP_OK;
   // [OP_FAM_COUNT]: some GEMM weight is not exactly an fp16 value; [+ 2]: some weight TENSOR sits on fp16's subnormal grid
@@ -1559,43 +1508,25 @@ int resolve_policy(op_handle* h) {
   int any_lo[OP_FAM_COUNT + 3] = {0};
   OP_HIP(h, hipSetDevice(h->cfg.device_id));
   OP_HIP(h, hipMemcpy(any_lo, h->any_lo_dev, sizeof(any_lo), hipMemcpyDeviceToHost));
-  Policy e = h->req;
-  if (!any_lo[OP_FAM_WQKV]) e.wqkv &= ~OP_TERM_RIGHT_LO;
-  if (!any_lo[OP_FAM_ATTN_OUT]) e.attn_out &= ~OP_TERM_RIGHT_LO;
-  if (!any_lo[OP_FAM_WI]) e.wi &= ~OP_TERM_RIGHT_LO;
-  if (!any_lo[OP_FAM_MLP_OUT]) e.mlp_out &= ~OP_TERM_RIGHT_LO;
-  h->eff = e;
   h->f16_unfit = any_lo[OP_FAM_COUNT + 2] != 0;
-  // the default selection: the (hi, lo) bf16 set with exactly these terms (OP_FLAG_NO_POLICY_KERNELS: the all-terms one only)
-  int set = -1;
-  const int n_bf16_sets = (h->cfg.flags & OP_FLAG_NO_POLICY_KERNELS) ? 1 : OP_KS_BF16 + 1;
-  for (int s = n_bf16_sets - 1; s >= 0; --s)
-    if (kKernelSets[s].terms == e) set = s;
-  // bf16-valued weights that are also exact fp16 values, on the whole-layer kernel's shapes: the "f16 + fp8" kernel
-  // set evaluates the same terms at 1.5 instead of 2 MFMA units per product (op_internal.h)
-  const bool f8_ok = set >= 0 && h->f8_packs && !h->f8_off && !h->f16_unfit &&
-                     !(h->cfg.flags & (OP_FLAG_NO_POLICY_KERNELS | OP_FLAG_NO_LAYER_FUSION | OP_FLAG_LAYER_8X16 | OP_FLAG_LAYER_M32));
-  const bool exact_f16 = !any_lo[OP_FAM_COUNT];
-  // Panel path (hidden 512 / 768).  The whole layer in the format (OP_FLAG_PANEL_F8) costs 0.45-1.0e-3 on logits at the
-  // published depths: opt-in.  The Wi GEMM ALONE -- 52 % of the GEMM FLOPs -- costs 1-1.5e-4 (base / large / en-gte at
-  // 19-25 layers: <= 5.4e-4 against the oracle where the (hi, lo) bf16 sets give <= 4.7e-4; scripts/f8_depth_check.py,
-  // profiles/r04_f8_depth_check.txt) and takes the fp32-valued Wi GEMM from 3 to 2 MFMA units per product: +5.6 %
-  // pairs/s on base -- the DEFAULT for fp32-valued weights.  For bf16-valued weights (2 -> 1.5 units in a GEMM that
-  // is not pipe-bound there) it measures +0.7 %: only on request (OP_FLAG_PANEL_F8_WI).
-  const bool wi_only = h->panel_path && !(h->cfg.flags & OP_FLAG_PANEL_F8);
-  // every term requested and carried (fp32-valued weights): the same format with the weights' lo part as a third
-  // plane -- one kernel per layer at 2 MFMA units per product instead of two kernels at 3
-  if (f8_ok && set == OP_KS_BF16X3) set = wi_only ? OP_KS_BF16X3_WI_F8 : OP_KS_F16_F8_W;
-  else if (f8_ok && set == OP_KS_BF16_WEIGHTS && exact_f16 && (!wi_only || (h->cfg.flags & OP_FLAG_PANEL_F8_WI)))
-    set = wi_only ? OP_KS_BF16_WEIGHTS_WI_F8 : OP_KS_F16_F8;
-  // A kernel set pinned by op_select_kernel_set / chosen by op_calibrate replaces the default selection, and the evaluated
-  // terms become the set's own (a set with fewer terms than the checkpoint carries is an approximation -- op_calibrate
-  // measures it before choosing it).
-  const bool pinned = h->forced_set >= 0 && set_available(h, h->forced_set);
-  use_set(h, pinned ? h->forced_set : set);
-  if (pinned) h->eff = h->ks->terms;
+  opp::SelectState s = select_state(h);
+  for (int f = 0; f < OP_FAM_COUNT; ++f) s.any_lo[f] = any_lo[f] != 0;
+  s.not_f16 = any_lo[OP_FAM_COUNT] != 0;
+  const opp::Selection sel = opp::select(s);
+  h->eff = sel.eff;
+  h->set = sel.set;
+  h->ks = &opp::set_row(sel.set);
+  h->mlp_layers = sel.mlp_layers;
   h->resolved = true;
   return OP_OK;
+}
+
+// run kernel set `set` with layer mask `mlp_layers` from now on where the handle can (-1: the default selection)
+int pin(op_handle* h, int set, uint64_t mlp_layers = ~0ull) {
+  h->forced_set = set;
+  h->forced_mlp_layers = mlp_layers;
+  h->resolved = false;
+  return resolve_policy(h);
 }
 
 // deterministic calibration batch: 24 rows of min(512, max_pos) tokens + 14 ragged rows, ids uniform over the vocabulary
@@ -1622,6 +1553,37 @@ void synthetic_calibration_rows(const op_handle* h, std::vector<int32_t>& ids, s
     cu.push_back((int32_t)ids.size());
   }
 }
+
+// op_calibrate's visit to a handle.  While it lasts nothing is profiled or captured; when it ends, on whichever way out, both
+// come back -- and so does what was pinned before the call, unless the call got as far as pinning its own answer (keep_pin).
+struct CalibrationVisit {
+  op_handle* const h;
+  const bool profiling;
+  float* const capture;
+  const bool f8_off;
+  const int forced_set;
+  const uint64_t forced_mlp_layers;
+  bool pin_kept = false;
+
+  explicit CalibrationVisit(op_handle* h_)
+      : h(h_), profiling(h_->profiling), capture(h_->capture), f8_off(h_->f8_off), forced_set(h_->forced_set), forced_mlp_layers(h_->forced_mlp_layers) {
+    h->profiling = false;
+    h->capture = nullptr;
+  }
+  CalibrationVisit(const CalibrationVisit&) = delete;
+  void keep_pin() { pin_kept = true; }
+  int restore_pin() {
+    pin_kept = true;
+    h->f8_off = f8_off;
+    return pin(h, forced_set, forced_mlp_layers);
+  }
+  ~CalibrationVisit() {
+    h->profiling = profiling;
+    h->capture = capture;
+    if (!pin_kept) (void)restore_pin();
+  }
+};
+
 }  // namespace
 
 extern "C" {
@@ -1648,12 +1610,8 @@ int op_set_compact_operands(op_handle* h, int enabled, int* changed) {
   if (rc != OP_OK) return rc;
   const int before = h->set;
   h->f8_off = enabled == 0;
-  if (!enabled) {  // a pinned / calibrated compact set goes too
-    h->forced_set = -1;
-    h->forced_mlp_layers = ~0ull;
-  }
-  h->resolved = false;
-  rc = resolve_policy(h);
+  // (switching off: a pinned / calibrated compact set goes too)
+  rc = enabled ? pin(h, h->forced_set, h->forced_mlp_layers) : pin(h, -1);
   if (changed) *changed = (rc == OP_OK && h->set != before) ? 1 : 0;
   return rc;
 }
@@ -1665,21 +1623,16 @@ int op_select_kernel_set(op_handle* h, int kernel_set) {
   if (kernel_set == OP_KS_F32 && !h->f32_packs)
     return fail(h, OP_ERR_UNSUPPORTED, "op_select_kernel_set: kernel set %d (\"fp32\") needs the fp32 weight packs: create the handle with OP_FLAG_F32_PACKS",
                 kernel_set);
-  if (kernel_set != OP_KS_AUTO && !set_available(h, kernel_set))
+  if (kernel_set != OP_KS_AUTO && !opp::set_available(select_state(h), kernel_set))
     return fail(h, OP_ERR_UNSUPPORTED, "op_select_kernel_set: kernel set %d cannot run on this handle (shape, flags or weights)", kernel_set);
-  h->forced_set = kernel_set == OP_KS_AUTO ? -1 : kernel_set;
-  h->forced_mlp_layers = ~0ull;
-  h->resolved = false;
-  return resolve_policy(h);  // (the coverage follows the arithmetic: coverage_prepare)
+  return pin(h, kernel_set == OP_KS_AUTO ? -1 : kernel_set);  // (the coverage follows the arithmetic: coverage_prepare)
 }
 
 int op_mlp_correction_layers(op_handle* h, uint64_t* layer_mask) {
   if (!h || !layer_mask) return fail(h, OP_ERR_INVALID, "op_mlp_correction_layers: NULL argument");
   int rc = op_weights_ready(h);
   if (rc != OP_OK) return rc;
-  const int n = h->cfg.num_layers;
-  const uint64_t all = n >= 64 ? ~0ull : ((1ull << n) - 1ull);
-  *layer_mask = mlp_by_layer(*h->ks) ? (h->mlp_layers & all) : 0ull;
+  *layer_mask = mlp_by_layer(*h->ks) ? (h->mlp_layers & opp::all_layers_mask(h->cfg.num_layers)) : 0ull;
   return OP_OK;
 }
 
@@ -1691,9 +1644,7 @@ int op_select_mlp_correction_layers(op_handle* h, uint64_t layer_mask) {
     return fail(h, OP_ERR_STATE, "op_select_mlp_correction_layers: pin kernel set %d or %d first (op_select_kernel_set / op_calibrate)", OP_KS_F16_MLP_F8_W,
                 OP_KS_F16_MLP_F8);
   if (h->cfg.num_layers > 64) return fail(h, OP_ERR_UNSUPPORTED, "op_select_mlp_correction_layers: more than 64 layers");
-  h->forced_mlp_layers = layer_mask;
-  h->resolved = false;
-  return resolve_policy(h);
+  return pin(h, h->forced_set, layer_mask);
 }
 
 int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const int32_t* cu_seqlens_host, int n_seqs,
@@ -1708,42 +1659,24 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   if (rc != OP_OK) return rc;
   // the caller's batch is checked BEFORE the handle's state is touched: a refused call leaves a pinned set where it was
   if (ids_host) {
-    if (cu_seqlens_host[0] != 0 || cu_seqlens_host[n_seqs] <= 0)
-      return fail(h, OP_ERR_INVALID, "op_calibrate: cu_seqlens must start at 0 and hold at least one token");
-    for (int s = 0; s < n_seqs; ++s) {
-      const int len = cu_seqlens_host[s + 1] - cu_seqlens_host[s];
-      if (len < 0 || len > h->cfg.max_position_embeddings)
-        return fail(h, OP_ERR_INVALID, "op_calibrate: row %d has %d tokens (cu_seqlens must not decrease; max_position_embeddings is %d)", s, len,
-                    h->cfg.max_position_embeddings);
-    }
-    for (int i = 0; i < cu_seqlens_host[n_seqs]; ++i)
-      if (ids_host[i] < 0 || ids_host[i] >= h->cfg.vocab_size)
-        return fail(h, OP_ERR_INVALID, "op_calibrate: token id %d at position %d is outside the embedding table (vocab_size %d)", ids_host[i], i,
-                    h->cfg.vocab_size);
+    const opp::Refusal bad = opp::check_calibration_batch(ids_host, cu_seqlens_host, n_seqs, h->cfg.max_position_embeddings, h->cfg.vocab_size);
+    if (bad.code != OP_OK) return fail(h, bad);
   }
-  const bool full_report = report && (report->flags & OP_CAL_FULL_REPORT) != 0;
   OP_HIP(h, hipSetDevice(h->cfg.device_id));
   h->cov_clear = true;  // whatever set comes out, it has seen no real row
+  CalibrationVisit visit(h);
 
   // the default selection and its (hi, lo) bf16 realisation = the reference of the comparison
-  const bool f8_off_before = h->f8_off;
-  const int forced_before = h->forced_set;
-  const uint64_t forced_mlp_before = h->forced_mlp_layers;
-  h->forced_set = -1;
-  h->forced_mlp_layers = ~0ull;
-  h->resolved = false;
-  OP_TRY(resolve_policy(h));
+  OP_TRY(pin(h, -1));
   const int default_set = h->set;
   h->f8_off = true;
-  h->resolved = false;
-  OP_TRY(resolve_policy(h));
+  OP_TRY(pin(h, -1));
   // OP_CAL_REFERENCE_F32 on a handle with the fp32 packs: kernel set "fp32" is the reference, the (hi, lo) bf16 set a candidate
   // like any other (where it is cheaper than the default)
-  const bool ref_f32 = report && (report->flags & OP_CAL_REFERENCE_F32) != 0 && h->set >= 0 && set_available(h, OP_KS_F32);
+  const bool ref_f32 = report && (report->flags & OP_CAL_REFERENCE_F32) != 0 && h->set >= 0 && opp::set_available(select_state(h), OP_KS_F32);
   const int reference_set = ref_f32 ? (int)OP_KS_F32 : h->set;
-  h->f8_off = f8_off_before;
-  h->resolved = false;
-  OP_TRY(resolve_policy(h));
+  h->f8_off = visit.f8_off;
+  OP_TRY(pin(h, -1));
 
   op_calibration rep;
   memset(&rep, 0, sizeof(rep));
@@ -1759,21 +1692,12 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   };
   // nothing to measure: whatever was pinned before the call stays pinned
   auto finish_unchanged = [&]() -> int {
-    h->forced_set = forced_before;
-    h->forced_mlp_layers = forced_mlp_before;
-    h->resolved = false;
-    OP_TRY(resolve_policy(h));
+    OP_TRY(visit.restore_pin());
     rep.chosen_set = h->set;
     return finish();
   };
   if (default_set < 0 || reference_set < 0) return finish_unchanged();  // a custom policy on the all-terms kernels: nothing cheaper is defined
-
-  // candidates: every available kernel set cheaper than the default one, cheapest first
-  std::vector<int> cand;
-  for (int set = 0; set < OP_KS_COUNT; ++set)
-    if (set != default_set && set_available(h, set) && set_cost(h, set) < set_cost(h, default_set)) cand.push_back(set);
-  std::sort(cand.begin(), cand.end(), [&](int a, int b) { return set_cost(h, a) < set_cost(h, b); });
-  if (cand.size() > 16) cand.resize(16);
+  const std::vector<int> cand = opp::calibration_candidates(select_state(h), default_set);
   if (cand.empty() && !ref_f32) return finish_unchanged();  // (fp32 reference: the default itself is still measured against it)
 
   std::vector<int32_t> ids, cu;
@@ -1791,11 +1715,8 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   rep.n_tokens = total;
 
   size_t ws_bytes = op_workspace_bytes(h, n_seqs, total, max_len);
-  if (ref_f32) {  // the largest workspace of the sets that run: the fp32 set's (its planes follow everybody's regions)
-    Workspace sized;
-    carve(h, nullptr, align_up(chunk_row_capacity(h, n_seqs, total, max_len) + 64, 256), n_seqs, true, sized);
-    ws_bytes = std::max(ws_bytes, sized.bytes);
-  }
+  // the largest workspace of the sets that run: the fp32 set's (its planes follow everybody's regions)
+  if (ref_f32) ws_bytes = std::max(ws_bytes, forward_layout(h, n_seqs, total, max_len, true).bytes);
   const size_t n_prune = (size_t)total * 2, n_rank = (size_t)n_seqs * h->nl;
   int32_t *ids_dev = nullptr, *cu_dev = nullptr;
   float* out_dev = nullptr;
@@ -1821,113 +1742,39 @@ int op_calibrate(op_handle* h, float tolerance, const int32_t* ids_host, const i
   }
   void* ws_aligned = reinterpret_cast<void*>((reinterpret_cast<uintptr_t>(ws_dev) + 255) / 256 * 256);
   std::vector<float> ref(n_prune + n_rank), got(n_prune + n_rank);
-  const bool profiling = h->profiling;
-  float* const capture = h->capture;
-  h->profiling = false;
-  h->capture = nullptr;
-  auto run = [&](int set, std::vector<float>& out, uint64_t mlp_layers = ~0ull) -> int {
-    h->forced_set = set;
-    h->forced_mlp_layers = mlp_layers;
-    h->resolved = false;
-    OP_TRY(resolve_policy(h));
+  auto run = [&](int set, std::vector<float>& out, uint64_t mlp_layers) -> int {
+    OP_TRY(pin(h, set, mlp_layers));
     OP_TRY(op_forward_packed(h, ids_dev, cu_dev, cu.data(), n_seqs, total, max_len, out_dev, out_dev + n_prune, nullptr, ws_aligned,
                              ws_bytes, st));
     OP_HIP(h, hipStreamSynchronize(st));
     OP_HIP(h, hipMemcpy(out.data(), out_dev, out.size() * sizeof(float), hipMemcpyDeviceToHost));
     return OP_OK;
   };
-  rc = run(reference_set, ref);
-  bool ref_finite = true;
-  for (float v : ref) ref_finite = ref_finite && std::isfinite(v);
-  int chosen = -1;
-  auto max_diff = [&]() {
-    float err = 0.f;
-    for (size_t i = 0; i < got.size(); ++i) {
-      const float d = std::fabs(got[i] - ref[i]);
-      err = (d <= err) ? err : d;  // a NaN difference propagates: (NaN <= err) is false
-    }
-    return std::isfinite(err) ? err : INFINITY;
+  bool have_ref = false;  // the search's first measurement is the reference's own run
+  auto measure = [&](int set, uint64_t mlp_layers) -> opp::Measurement {
+    const bool is_ref = !have_ref;
+    have_ref = true;
+    const int run_rc = run(set, is_ref ? ref : got, mlp_layers);
+    if (run_rc != OP_OK) return {run_rc, INFINITY};
+    if (!is_ref) return {OP_OK, opp::max_diff(got, ref)};
+    bool ref_finite = true;
+    for (float v : ref) ref_finite = ref_finite && std::isfinite(v);
+    return {OP_OK, ref_finite ? 0.f : INFINITY};
   };
-  if (rc == OP_OK && ref_finite && default_set != reference_set) {
-    rc = run(default_set, got);
-    if (rc == OP_OK) rep.default_err = max_diff();
-  }
-  if (rc == OP_OK && ref_finite) {
-    for (size_t c = 0; c < cand.size() && rc == OP_OK; ++c) {
-      rc = run(cand[c], got);
-      if (rc != OP_OK) break;
-      const float err = max_diff();
-      rep.candidate_set[rep.n_candidates] = cand[c];
-      rep.candidate_err[rep.n_candidates] = err;
-      rep.n_candidates += 1;
-      if (chosen < 0 && err <= tolerance) chosen = cand[c];
-      if (chosen >= 0 && !full_report) break;  // cheapest first: the first one that holds is the answer (OP_CAL_FULL_REPORT measures them all)
-    }
-  }
-  // Kernel sets 8 / 9 chosen (the "f16" set alone is beyond the tolerance, the MLP in the fp16 + e4m3 format brings it back):
-  // the correction is a per-layer choice (panel_layer): drop it layer by layer for as long as the batch stays within the
-  // tolerance.  The error is a maximum over logits, not a sum over layers, so the order of the walk decides how many layers
-  // go: three walks (first to last, last to first, and by the price of dropping each layer alone), the one that keeps the
-  // fewest layers wins.  About four forwards of the calibration batch per layer, at load.
-  const int n_layers = h->cfg.num_layers;
-  const uint64_t all_layers = n_layers >= 64 ? ~0ull : ((1ull << n_layers) - 1ull);
-  uint64_t mlp_layers = all_layers;
-  if (rc == OP_OK && (chosen == OP_KS_F16_MLP_F8 || chosen == OP_KS_F16_MLP_F8_W) && n_layers <= 64 && !(rep.flags & OP_CAL_WHOLE_DEPTH)) {
-    std::vector<std::pair<float, int>> alone;
-    for (int li = 0; li < n_layers && rc == OP_OK; ++li) {
-      rc = run(chosen, got, all_layers & ~(1ull << li));
-      if (rc == OP_OK) alone.emplace_back(max_diff(), li);
-    }
-    std::vector<std::vector<int>> walks(3);
-    for (int li = 0; li < n_layers; ++li) {
-      walks[0].push_back(li);
-      walks[1].push_back(n_layers - 1 - li);
-    }
-    std::vector<std::pair<float, int>> by_price = alone;
-    std::stable_sort(by_price.begin(), by_price.end(), [](const std::pair<float, int>& a, const std::pair<float, int>& b) { return a.first < b.first; });
-    for (const auto& pr : by_price) walks[2].push_back(pr.second);
-    int best_kept = n_layers + 1;
-    for (size_t w = 0; w < walks.size() && rc == OP_OK && alone.size() == (size_t)n_layers; ++w) {
-      uint64_t mask = all_layers;
-      float mask_err = 0.f;
-      for (int li : walks[w]) {
-        const uint64_t trial = mask & ~(1ull << li);
-        if (trial == 0ull) break;  // (= the "f16" set, measured above)
-        float err = alone[li].first;
-        if (trial != (all_layers & ~(1ull << li))) {
-          rc = run(chosen, got, trial);
-          if (rc != OP_OK) break;
-          err = max_diff();
-        }
-        if (err <= tolerance) {
-          mask = trial;
-          mask_err = err;
-        }
-      }
-      const int kept = __builtin_popcountll(mask);
-      if (rc == OP_OK && kept < best_kept) {
-        best_kept = kept;
-        mlp_layers = mask;
-        rep.mlp_layers_err = mask_err;
-      }
-    }
-  }
-  h->profiling = profiling;
-  h->capture = capture;
+  const opp::SearchResult found = opp::calibration_search(cand, reference_set, default_set, tolerance, rep.flags, h->cfg.num_layers, measure);
   release();
-  // nothing cheaper holds: the default stays -- unless it cannot even represent this batch (fp16 range), or is itself further
-  // from the (hi, lo) bf16 kernels than TEN times the tolerance (1e-3 at the default tolerance: the path's own bar; the O(1)
-  // worst-case weights put it at 6e-4): a checkpoint with outlier channels at 30 - 100 x puts the fp16 + e4m3 default 4e-2
-  // from them (scripts/trained_like_probe.py) -- then the reference set runs, the most exact arithmetic this library has
-  if (rc == OP_OK && chosen < 0 && ref_finite && default_set != reference_set &&
-      (!std::isfinite(rep.default_err) || rep.default_err > 10.0f * tolerance))
-    chosen = reference_set;
-  h->forced_set = (rc == OP_OK && chosen >= 0) ? chosen : -1;
-  h->forced_mlp_layers = (rc == OP_OK && chosen >= 0) ? (mlp_layers | ~all_layers) : ~0ull;
-  h->resolved = false;
-  const int rc2 = resolve_policy(h);
-  if (rc != OP_OK) return rc;
+
+  // what the search chose runs from now on (after an error: the default selection)
+  visit.keep_pin();
+  const uint64_t all_layers = opp::all_layers_mask(h->cfg.num_layers);
+  const int rc2 = found.chosen >= 0 ? pin(h, found.chosen, found.mlp_layers | ~all_layers) : pin(h, -1);
+  if (found.rc != OP_OK) return found.rc;
   if (rc2 != OP_OK) return rc2;
+  rep.default_err = found.default_err;
+  rep.n_candidates = found.n_candidates;
+  std::copy(found.candidate_set, found.candidate_set + 16, rep.candidate_set);
+  std::copy(found.candidate_err, found.candidate_err + 16, rep.candidate_err);
+  rep.mlp_layers_err = found.mlp_layers_err;
   rep.chosen_set = h->set;
   rep.mlp_layers = mlp_by_layer(*h->ks) ? (h->mlp_layers & all_layers) : 0ull;
   return finish();
@@ -1949,22 +1796,16 @@ int op_effective_policy(op_handle* h, uint8_t* terms_out, int* kernel_set) {
 
 size_t op_workspace_bytes(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen) {
   if (!h || n_seqs < 0 || total_tokens < 0 || max_seqlen < 0) return 0;
-  const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
-  const int cap_pad = align_up(cap + 64, 256);
-  Workspace ws;
-  carve(h, nullptr, cap_pad, n_seqs, h->set == OP_KS_F32, ws);
-  return ws.bytes;
+  return forward_layout(h, n_seqs, total_tokens, max_seqlen, h->set == OP_KS_F32).bytes;
 }
 
 int op_debug_workspace_layout(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen, op_workspace_region* entries,
                               int max_entries) {
   if (!h || n_seqs < 0 || total_tokens < 0 || max_seqlen < 0 || max_entries < 0 || (!entries && max_entries > 0)) return OP_ERR_INVALID;
-  const int cap_pad = align_up(chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen) + 64, 256);  // (as op_workspace_bytes)
-  Workspace ws;
-  std::vector<op_workspace_region> layout;
-  carve(h, nullptr, cap_pad, n_seqs, h->set == OP_KS_F32, ws, &layout);
-  for (size_t i = 0; i < layout.size() && i < (size_t)max_entries; ++i) entries[i] = layout[i];
-  return (int)layout.size();
+  const opp::Layout lay = forward_layout(h, n_seqs, total_tokens, max_seqlen, h->set == OP_KS_F32);  // (as op_workspace_bytes)
+  for (int i = 0; i < lay.n && i < max_entries; ++i)
+    entries[i] = op_workspace_region{lay.regions[i].name, (uint64_t)lay.regions[i].offset, (uint64_t)lay.regions[i].bytes, (int32_t)lay.regions[i].kind};
+  return lay.n;
 }
 
 int op_debug_rope_tables(const op_handle* h, int global_table, float theta, int max_pos, float* cos_host, float* sin_host) {
@@ -2059,114 +1900,63 @@ int op_profile_read(op_handle* h, op_profile_entry* entries, int max_entries) {
 }
 
 // The batch's cu_seqlens on the host -- the caller's copy, or read back from the device (synchronises the stream once) -- held
-// to what every pass over a packed batch relies on: 0 .. total_tokens, monotone, no row beyond max_seqlen or the RoPE tables.
-static int host_cu_seqlens(op_handle* h, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs, int total_tokens, int max_seqlen,
-                           hipStream_t stream, std::vector<int32_t>& cu_copy, const int32_t** cu_out) {
-  const int32_t* cu = cu_host_in;
+// to what every pass over a packed batch relies on (opp::check_cu_seqlens).
+static int host_cu_seqlens(op_handle* h, const PackedBatch& b, std::vector<int32_t>& cu_copy, const int32_t** cu_out) {
+  const int32_t* cu = b.cu_host;
   if (!cu) {
-    cu_copy.resize((size_t)n_seqs + 1);
-    OP_HIP(h, hipMemcpyAsync(cu_copy.data(), cu_dev, cu_copy.size() * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-    OP_HIP(h, hipStreamSynchronize(stream));
+    cu_copy.resize((size_t)b.n_seqs + 1);
+    OP_HIP(h, hipMemcpyAsync(cu_copy.data(), b.cu_dev, cu_copy.size() * sizeof(int32_t), hipMemcpyDeviceToHost, b.stream));
+    OP_HIP(h, hipStreamSynchronize(b.stream));
     cu = cu_copy.data();
   }
-  if (cu[0] != 0 || cu[n_seqs] != total_tokens)
-    return fail(h, OP_ERR_INVALID, "cu_seqlens must start at 0 and end at total_tokens (%d): got %d..%d", total_tokens,
-                cu[0], cu[n_seqs]);
-  for (int s = 0; s < n_seqs; ++s) {
-    const int len = cu[s + 1] - cu[s];
-    if (len < 0) return fail(h, OP_ERR_INVALID, "cu_seqlens not monotone at %d", s);
-    if (len > max_seqlen) return fail(h, OP_ERR_INVALID, "sequence %d has %d tokens > max_seqlen %d", s, len, max_seqlen);
-    if (len > h->max_pos)
-      return fail(h, OP_ERR_UNSUPPORTED, "sequence %d has %d tokens > max_position_embeddings %d", s, len, h->max_pos);
-  }
+  const opp::Refusal bad = opp::check_cu_seqlens(cu, b.n_seqs, b.total_tokens, b.max_seqlen, h->max_pos);
+  if (bad.code != OP_OK) return fail(h, bad);
   *cu_out = cu;
   return OP_OK;
 }
 
-// The chunk of sequences that starts at s0: as many as fit `cap` rows (at least one) -> one past its last sequence, with
-// its rows (every sequence rounded up to ROW_ALIGN) and its longest sequence.
-static int next_chunk(const int32_t* cu, int s0, int n_seqs, int cap, int* rows_out, int* max_len_out) {
-  int rows = 0, s1 = s0, max_len = 0;
-  while (s1 < n_seqs) {
-    const int len = cu[s1 + 1] - cu[s1];
-    const int r = align_up(len, ROW_ALIGN);
-    if (s1 > s0 && rows + r > cap) break;
-    rows += r;
-    max_len = std::max(max_len, len);
-    ++s1;
-  }
-  *rows_out = rows;
-  *max_len_out = max_len;
-  return s1;
-}
-
-// op_forward_packed, and op_forward_packed_hidden with its validated request (hid; nullptr: none)
-static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
-                               int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
-                               void* workspace, size_t workspace_bytes, void* hip_stream, const HiddenReq* hid) {
+// op_forward_packed, and op_forward_packed_hidden / _pooled with their validated request (hid; nullptr: none)
+static int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid) {
   if (!h) return fail(nullptr, OP_ERR_INVALID, "op_forward_packed: NULL handle");
-  if (n_seqs < 0 || total_tokens < 0 || max_seqlen < 0) return fail(h, OP_ERR_INVALID, "negative size");
-  if (n_seqs == 0 || total_tokens == 0) {
-    if (n_seqs > 0 && rank_out) {
-      hipStream_t st = reinterpret_cast<hipStream_t>(hip_stream);
-      OP_HIP(h, hipMemsetAsync(rank_out, 0, (size_t)n_seqs * h->nl * sizeof(float), st));
-    }
-    if (n_seqs > 0 && hid && hid->n_pool > 0)  // only empty sequences: every pooled row is +0.0
-      OP_HIP(h, hipMemsetAsync(hid->pool_out, 0, (size_t)hid->n_pool * n_seqs * h->H * sizeof(float), reinterpret_cast<hipStream_t>(hip_stream)));
+  if (b.n_seqs < 0 || b.total_tokens < 0 || b.max_seqlen < 0) return fail(h, OP_ERR_INVALID, "negative size");
+  if (b.n_seqs == 0 || b.total_tokens == 0) {
+    if (b.n_seqs > 0 && b.rank_out) OP_HIP(h, hipMemsetAsync(b.rank_out, 0, (size_t)b.n_seqs * h->nl * sizeof(float), b.stream));
+    if (b.n_seqs > 0 && hid && hid->n_pool > 0)  // only empty sequences: every pooled row is +0.0
+      OP_HIP(h, hipMemsetAsync(hid->pool_out, 0, (size_t)hid->n_pool * b.n_seqs * h->H * sizeof(float), b.stream));
     return OP_OK;
   }
-  if (!ids_dev || !cu_dev || !prune_out || !rank_out || !workspace)
+  if (!b.ids_dev || !b.cu_dev || !b.prune_out || !b.rank_out || !b.workspace)
     return fail(h, OP_ERR_INVALID, "op_forward_packed: NULL buffer");
   if (op_weights_ready(h) != OP_OK) return OP_ERR_STATE;
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0)
+  if ((reinterpret_cast<uintptr_t>(b.workspace) & 255) != 0)
     return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-  const size_t need = op_workspace_bytes(h, n_seqs, total_tokens, max_seqlen);
-  if (workspace_bytes < need)
-    return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, need);
+  const opp::Layout lay = forward_layout(h, b.n_seqs, b.total_tokens, b.max_seqlen, h->set == OP_KS_F32);  // (= op_workspace_bytes)
+  if (b.workspace_bytes < lay.bytes)
+    return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", b.workspace_bytes, lay.bytes);
 
   OP_HIP(h, hipSetDevice(h->cfg.device_id));
-  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
-
   std::vector<int32_t> cu_copy;
   const int32_t* cu = nullptr;
-  OP_TRY(host_cu_seqlens(h, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, stream, cu_copy, &cu));
+  OP_TRY(host_cu_seqlens(h, b, cu_copy, &cu));
 
-  const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
-  const int cap_pad = align_up(cap + 64, 256);
+  const int cap = chunk_row_capacity(h, b.n_seqs, b.total_tokens, b.max_seqlen);
   Workspace ws;
-  carve(h, reinterpret_cast<char*>(workspace), cap_pad, n_seqs, h->set == OP_KS_F32, ws);
+  carve(lay, reinterpret_cast<char*>(b.workspace), ws);
 
-  Launcher L{h, stream};
+  Launcher L{h, b.stream};
   int s0 = 0;
-  while (s0 < n_seqs) {
+  while (s0 < b.n_seqs) {
     int rows = 0, max_len = 0;
-    const int s1 = next_chunk(cu, s0, n_seqs, cap, &rows, &max_len);
+    const int s1 = opp::next_chunk(cu, s0, b.n_seqs, cap, &rows, &max_len);
     if (rows > cap) return fail(h, OP_ERR_WORKSPACE, "internal: chunk of %d rows exceeds capacity %d", rows, cap);
-    // attention work items of the full-attention layers: 256-query blocks (8 waves) once a sequence is longer than
-    // 128 tokens, else 128 -- unless that leaves CUs idle (small request): then 128-query blocks, twice as many work
-    // items.  Sliding-window layers always use 128-query blocks.
-    auto count_items = [&](int waves) {
-      int items = 0;
-      for (int s = s0; s < s1; ++s) items += (cu[s + 1] - cu[s] + waves * 32 - 1) / (waves * 32);
-      return items;
-    };
-    const bool forced = (h->cfg.flags & (OP_FLAG_ATT_WAVES_4 | OP_FLAG_ATT_WAVES_8)) != 0;
-    AttnPlan plan;
-    plan.waves_g = forced ? ((h->cfg.flags & OP_FLAG_ATT_WAVES_4) ? 4 : 8) : (max_len > 128 ? 8 : 4);
-    plan.items_g = count_items(plan.waves_g);
-    if (!forced && plan.waves_g == 8 && (long)plan.items_g * h->nh <= h->n_cus) {
-      plan.waves_g = 4;
-      plan.items_g = count_items(4);
-    }
-    plan.items_l = count_items(4);
+    const AttnPlan plan = opp::attention_plan(cu, s0, s1, max_len, h->nh, h->n_cus, h->cfg.flags);
     if (rows > 0) {
-      OP_TRY(forward_chunk(h, L, ws, ids_dev, cu_dev, s0, s1 - s0, rows, max_len, total_tokens, plan, prune_out, rank_out,
-                           keep_prob, hid));
+      OP_TRY(ChunkPass(h, L, ws, b, s0, s1 - s0, rows, max_len, plan, hid).run());
     } else {
       // only empty sequences in this chunk
-      OP_HIP(h, hipMemsetAsync(rank_out + (size_t)s0 * h->nl, 0, (size_t)(s1 - s0) * h->nl * sizeof(float), stream));
+      OP_HIP(h, hipMemsetAsync(b.rank_out + (size_t)s0 * h->nl, 0, (size_t)(s1 - s0) * h->nl * sizeof(float), b.stream));
       for (int e = 0; hid && e < hid->n_pool; ++e)  // (their pooled rows: +0.0)
-        OP_HIP(h, hipMemsetAsync(hid->pool_out + ((size_t)e * n_seqs + s0) * h->H, 0, (size_t)(s1 - s0) * h->H * sizeof(float), stream));
+        OP_HIP(h, hipMemsetAsync(hid->pool_out + ((size_t)e * b.n_seqs + s0) * h->H, 0, (size_t)(s1 - s0) * h->H * sizeof(float), b.stream));
     }
     s0 = s1;
   }
@@ -2176,15 +1966,14 @@ static int forward_packed_impl(op_handle* h, const int32_t* ids_dev, const int32
 int op_forward_packed(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
                       int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
                       void* workspace, size_t workspace_bytes, void* hip_stream) {
-  return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
-                             workspace, workspace_bytes, hip_stream, nullptr);
+  const PackedBatch b{ids_dev,  cu_dev,    cu_host_in, n_seqs,    total_tokens,    max_seqlen,
+                      prune_out, rank_out, keep_prob,  workspace, workspace_bytes, reinterpret_cast<hipStream_t>(hip_stream)};
+  return forward_packed_impl(h, b, nullptr);
 }
 
 // op_forward_packed_hidden / op_forward_packed_pooled: the two requests checked (their own fields first: none of them needs the
 // handle), then one forward with whatever they select
-static int forward_packed_requests(const char* what, op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in,
-                                   int n_seqs, int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
-                                   void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req,
+static int forward_packed_requests(const char* what, op_handle* h, const PackedBatch& b, const op_hidden_request* req,
                                    const op_pool_request* pool, bool pool_required) {
   if (req) {
     if (req->struct_bytes != sizeof(op_hidden_request))
@@ -2192,8 +1981,8 @@ static int forward_packed_requests(const char* what, op_handle* h, const int32_t
                   sizeof(op_hidden_request));
     if (req->dtype != OP_HIDDEN_F32 && req->dtype != OP_HIDDEN_BF16)
       return fail(h, OP_ERR_INVALID, "%s: unknown dtype %d", what, req->dtype);
-    if (req->pad_width < 0 || (req->pad_width > 0 && req->pad_width < max_seqlen))
-      return fail(h, OP_ERR_INVALID, "%s: pad_width %d below max_seqlen %d", what, req->pad_width, max_seqlen);
+    if (req->pad_width < 0 || (req->pad_width > 0 && req->pad_width < b.max_seqlen))
+      return fail(h, OP_ERR_INVALID, "%s: pad_width %d below max_seqlen %d", what, req->pad_width, b.max_seqlen);
   }
   if (pool_required && !pool) return fail(h, OP_ERR_INVALID, "%s: the pooled request is NULL", what);
   if (pool) {
@@ -2205,9 +1994,7 @@ static int forward_packed_requests(const char* what, op_handle* h, const int32_t
       return fail(h, OP_ERR_INVALID, "%s: scratch_dev must be 16-byte aligned", what);
   }
   if (!h) return fail(nullptr, OP_ERR_INVALID, "%s: NULL handle", what);
-  if (!req && !pool)
-    return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
-                               workspace, workspace_bytes, hip_stream, nullptr);
+  if (!req && !pool) return forward_packed_impl(h, b, nullptr);
   HiddenReq hid;
   int n_sel = 0;
   if (req) {
@@ -2217,7 +2004,7 @@ static int forward_packed_requests(const char* what, op_handle* h, const int32_t
     hid.slot.assign((size_t)h->N + 1, -1);
     for (int i = 0; i <= h->N; ++i)
       if (!req->select || req->select[i]) hid.slot[i] = n_sel++;
-    const size_t rows = hid.pad > 0 ? (size_t)std::max(n_seqs, 0) * (size_t)hid.pad : (size_t)std::max(total_tokens, 0);
+    const size_t rows = hid.pad > 0 ? (size_t)std::max(b.n_seqs, 0) * (size_t)hid.pad : (size_t)std::max(b.total_tokens, 0);
     if (rows > (size_t)INT32_MAX)  // (destination rows are 32-bit indices in the kernels' epilogues)
       return fail(h, OP_ERR_INVALID, "%s: %zu destination rows per entry exceed 2^31 - 1", what, rows);
     hid.entry_bytes = rows * (size_t)h->H * (hid.bf16 ? 2 : 4);
@@ -2229,36 +2016,37 @@ static int forward_packed_requests(const char* what, op_handle* h, const int32_t
     hid.pool_kind = pool->kind == OP_HIDDEN_POOL_MEAN ? POOL_MEAN : POOL_FIRST;
     hid.pool_out = pool->out_dev;
     hid.scratch = reinterpret_cast<float*>(pool->scratch_dev);
-    hid.n_seqs = std::max(n_seqs, 0);
+    hid.n_seqs = std::max(b.n_seqs, 0);
     hid.pool_slot.assign((size_t)h->N + 1, -1);
     for (int i = 0; i <= h->N; ++i)
       if (!pool->select || pool->select[i]) hid.pool_slot[i] = hid.n_pool++;
-    const size_t scratch_need = (size_t)std::max(total_tokens, 0) * (size_t)h->H * sizeof(float);
-    if (hid.n_pool > 0 && n_seqs > 0 && !hid.pool_out)
+    const size_t scratch_need = (size_t)std::max(b.total_tokens, 0) * (size_t)h->H * sizeof(float);
+    if (hid.n_pool > 0 && b.n_seqs > 0 && !hid.pool_out)
       return fail(h, OP_ERR_INVALID, "%s: the pooled out_dev is NULL with %d entries selected", what, hid.n_pool);
-    if (hid.n_pool > 0 && n_seqs > 0 && scratch_need > 0 && !hid.scratch)
+    if (hid.n_pool > 0 && b.n_seqs > 0 && scratch_need > 0 && !hid.scratch)
       return fail(h, OP_ERR_INVALID, "%s: scratch_dev is NULL", what);
-    if (hid.n_pool > 0 && n_seqs > 0 && pool->scratch_bytes < scratch_need)
+    if (hid.n_pool > 0 && b.n_seqs > 0 && pool->scratch_bytes < scratch_need)
       return fail(h, OP_ERR_INVALID, "%s: scratch has %zu bytes, one packed fp32 entry needs %zu", what, (size_t)pool->scratch_bytes, scratch_need);
     if (hid.n_pool == 0) hid.pool_slot.clear();
   }
-  return forward_packed_impl(h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out, rank_out, keep_prob,
-                             workspace, workspace_bytes, hip_stream, (n_sel > 0 || hid.n_pool > 0) ? &hid : nullptr);
+  return forward_packed_impl(h, b, (n_sel > 0 || hid.n_pool > 0) ? &hid : nullptr);
 }
 
 int op_forward_packed_hidden(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
                              int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
                              void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req) {
-  return forward_packed_requests("op_forward_packed_hidden", h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out,
-                                 rank_out, keep_prob, workspace, workspace_bytes, hip_stream, req, nullptr, false);
+  const PackedBatch b{ids_dev,  cu_dev,    cu_host_in, n_seqs,    total_tokens,    max_seqlen,
+                      prune_out, rank_out, keep_prob,  workspace, workspace_bytes, reinterpret_cast<hipStream_t>(hip_stream)};
+  return forward_packed_requests("op_forward_packed_hidden", h, b, req, nullptr, false);
 }
 
 int op_forward_packed_pooled(op_handle* h, const int32_t* ids_dev, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs,
                              int total_tokens, int max_seqlen, float* prune_out, float* rank_out, float* keep_prob,
                              void* workspace, size_t workspace_bytes, void* hip_stream, const op_hidden_request* req,
                              const op_pool_request* pool) {
-  return forward_packed_requests("op_forward_packed_pooled", h, ids_dev, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, prune_out,
-                                 rank_out, keep_prob, workspace, workspace_bytes, hip_stream, req, pool, true);
+  const PackedBatch b{ids_dev,  cu_dev,    cu_host_in, n_seqs,    total_tokens,    max_seqlen,
+                      prune_out, rank_out, keep_prob,  workspace, workspace_bytes, reinterpret_cast<hipStream_t>(hip_stream)};
+  return forward_packed_requests("op_forward_packed_pooled", h, b, req, pool, true);
 }
 
 // ---- op_attention_probs: the softmax probabilities of one layer, a side pass over that layer's input hidden state ----------
@@ -2301,35 +2089,34 @@ size_t op_attention_workspace_bytes(const op_handle* h, int n_seqs, int total_to
 // then enqueues the call's own kernel over the chunk's q and k.
 extern "C++" {
 template <typename Tail>
-static int attention_side_pass(op_handle* h, const char* what, const int32_t* cu_dev, const int32_t* cu_host_in, int n_seqs, int total_tokens,
-                               int max_seqlen, int li, const float* hidden_dev, void* workspace, size_t workspace_bytes, hipStream_t stream,
-                               Tail&& tail) {
-  if (!cu_dev || !workspace) return fail(h, OP_ERR_INVALID, "%s: NULL buffer", what);
-  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-  const size_t need = op_attention_workspace_bytes(h, n_seqs, total_tokens, max_seqlen);
-  if (workspace_bytes < need) return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, need);
+static int attention_side_pass(op_handle* h, const char* what, const PackedBatch& b, int li, const float* hidden_dev, Tail&& tail) {
+  if (!b.cu_dev || !b.workspace) return fail(h, OP_ERR_INVALID, "%s: NULL buffer", what);
+  if ((reinterpret_cast<uintptr_t>(b.workspace) & 255) != 0) return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  const size_t need = op_attention_workspace_bytes(h, b.n_seqs, b.total_tokens, b.max_seqlen);
+  if (b.workspace_bytes < need) return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", b.workspace_bytes, need);
 
   std::vector<int32_t> cu_copy;
   const int32_t* cu = nullptr;
-  OP_TRY(host_cu_seqlens(h, cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, stream, cu_copy, &cu));
+  OP_TRY(host_cu_seqlens(h, b, cu_copy, &cu));
 
   const int H = h->H;
+  const hipStream_t stream = b.stream;
   const bool is_global = h->cfg.layer_is_global[li] != 0;
   const float* attn_norm = li != 0 ? h->layers[li].attn_norm : nullptr;  // layer 0: the identity, as in the forward
-  const int cap = chunk_row_capacity(h, n_seqs, total_tokens, max_seqlen);
+  const int cap = chunk_row_capacity(h, b.n_seqs, b.total_tokens, b.max_seqlen);
   AttnProbsWorkspace ws;
-  carve_attention(h, reinterpret_cast<char*>(workspace), align_up(cap + 64, 256), n_seqs, ws);
+  carve_attention(h, reinterpret_cast<char*>(b.workspace), align_up(cap + 64, 256), b.n_seqs, ws);
 
   int s0 = 0;
-  while (s0 < n_seqs) {  // chunks of sequences, as the forward takes them
+  while (s0 < b.n_seqs) {  // chunks of sequences, as the forward takes them
     int rows = 0, max_len = 0;
-    const int s1 = next_chunk(cu, s0, n_seqs, cap, &rows, &max_len);
+    const int s1 = opp::next_chunk(cu, s0, b.n_seqs, cap, &rows, &max_len);
     if (rows > cap) return fail(h, OP_ERR_WORKSPACE, "internal: chunk of %d rows exceeds capacity %d", rows, cap);
     const int ns = s1 - s0;
     const int r_pad = align_up(std::max(rows, 1), GEMM_BM);
     // row map; the state's rows (zero rows where the map holds no token); LayerNorm; q | k with RoPE, q scaled
-    hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, stream, cu_dev, s0, ns, ROW_ALIGN, ROW_ALIGN, ws.roff);
-    hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, stream, cu_dev, s0, ns, ws.roff, r_pad,
+    hipLaunchKernelGGL(seq_offsets_kernel, dim3(1), dim3(1024), 0, stream, b.cu_dev, s0, ns, ROW_ALIGN, ROW_ALIGN, ws.roff);
+    hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, stream, b.cu_dev, s0, ns, ws.roff, r_pad,
                        ws.row_seq, ws.row_pos, ws.row_tok);
     opl::launch_attn_probs_gather(stream, hidden_dev, ws.row_tok, H, r_pad, ws.x);
     if (attn_norm) opl::launch_f32_ln(stream, ws.x, attn_norm, h->cfg.norm_eps, H, r_pad, ws.ln);
@@ -2391,8 +2178,11 @@ int op_attention_probs(op_handle* h, const int32_t* cu_dev, const int32_t* cu_ho
     OP_HIP(h, hipMemsetAsync(out, 0, (size_t)n_seqs * mat_elems * sizeof(float), stream));
     return OP_OK;
   }
-  return attention_side_pass(h, "op_attention_probs", cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, req->layer, req->hidden_dev,
-                             workspace, workspace_bytes, stream, [&](const AttnProbsWorkspace& ws, int s0, int ns, bool is_global) {
+  PackedBatch b;
+  b.cu_dev = cu_dev, b.cu_host = cu_host_in, b.n_seqs = n_seqs, b.total_tokens = total_tokens, b.max_seqlen = max_seqlen;
+  b.workspace = workspace, b.workspace_bytes = workspace_bytes, b.stream = stream;
+  return attention_side_pass(h, "op_attention_probs", b, req->layer, req->hidden_dev,
+                             [&](const AttnProbsWorkspace& ws, int s0, int ns, bool is_global) {
                                AttnProbsParams ap;
                                ap.q = ws.q;
                                ap.k = ws.k;
@@ -2451,8 +2241,11 @@ int op_attention_rows(op_handle* h, const int32_t* cu_dev, const int32_t* cu_hos
     OP_HIP(h, hipMemsetAsync(out, 0, (size_t)n_seqs * row_elems * sizeof(float), stream));
     return OP_OK;
   }
-  return attention_side_pass(h, "op_attention_rows", cu_dev, cu_host_in, n_seqs, total_tokens, max_seqlen, req->layer, req->hidden_dev,
-                             workspace, workspace_bytes, stream, [&](const AttnProbsWorkspace& ws, int s0, int ns, bool is_global) {
+  PackedBatch b;
+  b.cu_dev = cu_dev, b.cu_host = cu_host_in, b.n_seqs = n_seqs, b.total_tokens = total_tokens, b.max_seqlen = max_seqlen;
+  b.workspace = workspace, b.workspace_bytes = workspace_bytes, b.stream = stream;
+  return attention_side_pass(h, "op_attention_rows", b, req->layer, req->hidden_dev,
+                             [&](const AttnProbsWorkspace& ws, int s0, int ns, bool is_global) {
                                AttnRowsParams ar;
                                ar.q = ws.q;
                                ar.k = ws.k;

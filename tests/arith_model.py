@@ -131,8 +131,8 @@ _F16F8 = _table("f16+f8", "bf16x3", "bf16x3", "f16+f8", "f16+f8", "f16+f8")
 _F16F8W = _table("f16+2f8", "bf16x3", "bf16x3", "f16+2f8", "f16+2f8", "f16+2f8")
 _F16 = _table(*["f16"] * 6)
 
-# Set name -> per-family scheme.  From op_internal.h kPolicies (term masks 3 = bf16x3, 1 = bf16x2, 0 = single pass;
-# fmt 1 = the fp16 + e4m3 format, fmt 2 = fp16 single plane), apply_set() in op_api.hip (which families a composite set
+# Set name -> per-family scheme.  From op_policy.h kPolicies (term masks 3 = bf16x3, 1 = bf16x2, 0 = single pass;
+# fmt 1 = the fp16 + e4m3 format, fmt 2 = fp16 single plane), kKernelSets in op_kernel_sets.h (which families a composite set
 # takes from which) and the set descriptions of include/open_provence_hip.h.  Row-path departures: ROW_PATH below.
 KERNEL_SETS: dict[str, dict[str, str]] = {
     "bf16x3": _BF16X3,                                           # 0: every operand (hi, lo)

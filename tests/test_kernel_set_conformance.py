@@ -55,7 +55,7 @@ SHAPES = {**MODELS, "panel512x4": (512, 2048, 8, 4), "tiled3": (384, 192, 6, 3)}
 PATH_OF = {"row": "row", "panel512": "panel", "panel768": "panel", "tiled": "tiled", "engte": "panel", "h1024": "panel",
            "row128": "row", "row320": "row", "panel512x4": "panel", "tiled3": "tiled"}
 
-# What each path supports, as an explicit expectation (op_api.hip set_available): every other set must be refused.
+# What each path supports, as an explicit expectation (op_plan.h set_available): every other set must be refused.
 ROW_SETS = ["bf16x3", "bf16-weights", "bf16", "f16-f8", "f16-f8-w", "f16"]
 SUPPORTED = {
     "row": ROW_SETS,
@@ -330,7 +330,7 @@ def test_kernel_set_matches_its_model(model, kernel_set, recipe):
 @pytest.mark.parametrize("weights", ["o1-damped", "o1-bf16-damped"])
 def test_damped_weights_keep_every_expected_set(model, weights):
     """The damped output projection sits on fp16's grid, so no set with an fp16 weight plane is refused for it
-    (f16_unfit in op_api.hip): every set the model supports still pins."""
+    (f16_unfit in op_plan.h): every set the model supports still pins."""
 
     from open_provence_amd.engine import HipEncoder
 
