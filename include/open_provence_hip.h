@@ -658,6 +658,93 @@ typedef struct op_assemble_request {
 } op_assemble_request;
 int op_assemble_rows(op_handle* h, const op_assemble_request* req, int32_t* ids_dev, void* hip_stream);
 
+/* Replaces: the per-fragment `float(block_probs[start:end].mean())` of the reference's post-processing
+ * (standalone.py:3075-3082) for a PREPARED request, with the token ranges derived on the device from the row plan that
+ * op_assemble_rows laid the rows out from -- op_segment_means without the host loop that builds and uploads the ranges.
+ * Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).
+ *   rows                                    the op_assemble_request of the forward whose keep-probabilities are averaged
+ *                                           (corpus_dev, query_ids_dev and the template's ids are not read, the pieces'
+ *                                           lengths are)
+ *   keep_prob_dev [rows->total_tokens] fp32 the keep-probabilities of that forward (op_forward_packed's keep_prob_dev)
+ *   frag_shift_dev [rows->n_frag] int32     per fragment of the corpus, the title tokens in front of its sentence: its
+ *                                           range is shifted LEFT by as much (ref :3075-3081); values only, no index
+ *   slot_off_dev / slot_off_host [n_rows + 1] int32  where each row's fragments go in the outputs: slot_off[r + 1] =
+ *                                           slot_off[r] + n_frag of row r, from any slot_off[0] >= 0 (a forward's slice of
+ *                                           the slots of a whole request) to at most n_slots
+ *   mean_out_dev [n_slots] fp32, slot_frag_out_dev [n_slots] int32
+ *                                           for fragment j of row r, f = first_frag + j, at slot_off[r] + j: the mean of
+ *                                           keep_prob over the fragment's range within the row -- from n_prefix + query
+ *                                           length + n_middle + the lengths of the row's fragments before it (the first
+ *                                           one `clip` long where clip > 0), as long as the fragment, both ends less
+ *                                           frag_shift[f], clamped to [0, row length) -- in numpy's float32 pairwise order,
+ *                                           divided in float64, bit for bit as op_segment_means; 1.0 for an empty range;
+ *                                           and f itself.  Nothing outside the rows' slots is written, and every one of
+ *                                           them is when the host and device copies agree.
+ * The request is checked on the host copies (rows->*_host, slot_off_host) and the kernel holds every index it reads from the
+ * device copies inside the buffers all the same.  Asynchronous on hip_stream; the handle's state is neither read nor changed
+ * beyond its device and error text.  OP_ERR_INVALID, before anything is enqueued: a NULL request, rows or handle, a wrong
+ * struct_bytes (either struct), a negative count, a NULL buffer while there are rows, a row whose query or fragments lie
+ * outside the request / the corpus or whose clip exceeds its first fragment, offsets that decrease, cu_seqlens_host that does
+ * not run from 0 to total_tokens, and a slot_off_host that is not the prefix sums of the rows' n_frag inside [0, n_slots].
+ * Kernel: a wave per row, a lane per fragment, vector stores only, no atomics (csrc/opk_decide.hip.h). */
+typedef struct op_planned_means_request {
+  uint32_t struct_bytes; /* sizeof(op_planned_means_request) */
+  int32_t n_slots;
+  const float* keep_prob_dev;
+  const int32_t* frag_shift_dev;
+  const int32_t* slot_off_dev;
+  const int32_t* slot_off_host;
+  float* mean_out_dev;
+  int32_t* slot_frag_out_dev;
+} op_planned_means_request;
+int op_planned_fragment_means(op_handle* h, const op_assemble_request* rows, const op_planned_means_request* req, void* hip_stream);
+
+/* Replaces: the per-sentence loop of the reference's post-processing (standalone.py:3100-3140) for a PREPARED request: the
+ * average of a sentence's fragment means, clamped to [0, 1], the threshold, and the title rule, on the slots
+ * op_planned_fragment_means filled.  Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).
+ *   instances_dev / instances_host [n_instances][OP_DECISIONS_INSTANCE_WORDS] int32
+ *                                           per (query, context) pair of the request {slot_begin, slot_end, sent_out_begin,
+ *                                           n_sentences, item_sent_base, title_index}: its fragments' slots
+ *                                           [slot_begin, slot_end) in fragment order, where its n_sentences results go,
+ *                                           the corpus-wide number of its first sentence, and the sentence the title rule
+ *                                           keeps (or -1)
+ *   mean_dev [n_slots] fp32, slot_frag_dev [n_slots] int32   the outputs of op_planned_fragment_means
+ *   frag_sent_dev [n_frag] int32            per fragment of the corpus, the corpus-wide number of its sentence; within a
+ *                                           context it must not decrease from fragment to fragment
+ *   threshold                               fp64
+ *   avg_out_dev [n_out] fp64, keep_out_dev [n_out] uint8
+ *                                           sentence k of an instance, at sent_out_begin + k: its values are the run of the
+ *                                           instance's slots whose fragment belongs to sentence item_sent_base + k, widened
+ *                                           to fp64; avg = 0.0 without values, the value itself for one, else their sum in
+ *                                           numpy's float64 pairwise order divided by their number; then Python's
+ *                                           max(0.0, min(avg, 1.0)) (a NaN average comes out as 0.0); keep = avg > threshold;
+ *                                           and where title_index >= 0 and any sentence of the instance is kept,
+ *                                           keep[title_index] = 1.  Every element is written.
+ * Checked on instances_host; the kernel holds what it reads from the device copies inside the buffers all the same.
+ * Asynchronous on hip_stream; no handle state.  OP_ERR_INVALID, before anything is enqueued: a NULL request or handle, a wrong
+ * struct_bytes, a negative count, a NULL buffer while there is something to read or write, an instance whose slots lie outside
+ * [0, n_slots] or run backwards, whose sentences do not start where the previous instance's ended (from 0 to n_out: the
+ * instances' results tile the outputs), whose item_sent_base is negative, or whose title_index lies outside
+ * [-1, n_sentences).  Kernel: one thread per instance, sequential (the data is a few KB), vector stores only, no atomics
+ * (csrc/opk_decide.hip.h). */
+#define OP_DECISIONS_INSTANCE_WORDS 6
+typedef struct op_decisions_request {
+  uint32_t struct_bytes; /* sizeof(op_decisions_request) */
+  int32_t n_instances;
+  int32_t n_slots;
+  int32_t n_frag;
+  int32_t n_out;
+  double threshold;
+  const int32_t* instances_dev;
+  const int32_t* instances_host;
+  const float* mean_dev;
+  const int32_t* slot_frag_dev;
+  const int32_t* frag_sent_dev;
+  double* avg_out_dev;
+  uint8_t* keep_out_dev;
+} op_decisions_request;
+int op_sentence_decisions(op_handle* h, const op_decisions_request* req, void* hip_stream);
+
 /* Test hook.  Replaces: output_hidden_states=True of the reference forward (standalone.py:1689,
  * 1727).  When `hidden_dev` is non-NULL the next forwards also write the (num_layers+1) hidden
  * states, fp32 [num_layers+1, total_tokens, hidden]; entry num_layers is the post-final_norm

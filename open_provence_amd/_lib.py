@@ -75,6 +75,8 @@ EXPORTED_SYMBOLS = (
     "op_audit_compare",
     "op_segment_means",
     "op_assemble_rows",
+    "op_planned_fragment_means",
+    "op_sentence_decisions",
     "op_debug_workspace_layout",
     "op_debug_rope_tables",
     "op_debug_primitive",
@@ -305,6 +307,46 @@ class OpAssembleRequest(ctypes.Structure):
 OP_ASSEMBLE_MAX_PIECE = 8
 
 
+class OpPlannedMeansRequest(ctypes.Structure):
+    """``op_planned_means_request``: the keep-probabilities of a forward, the corpus' shift table and where the rows' fragment
+    means go (``op_planned_fragment_means``; the rows themselves are the forward's ``op_assemble_request``)."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("n_slots", ctypes.c_int32),
+        ("keep_prob_dev", ctypes.c_void_p),
+        ("frag_shift_dev", ctypes.c_void_p),
+        ("slot_off_dev", ctypes.c_void_p),
+        ("slot_off_host", ctypes.c_void_p),
+        ("mean_out_dev", ctypes.c_void_p),
+        ("slot_frag_out_dev", ctypes.c_void_p),
+    ]
+
+
+OP_DECISIONS_INSTANCE_WORDS = 6  # slot_begin, slot_end, sent_out_begin, n_sentences, item_sent_base, title_index
+
+
+class OpDecisionsRequest(ctypes.Structure):
+    """``op_decisions_request``: the (query, context) instances of a prepared request, the fragment means and the outputs of
+    one ``op_sentence_decisions`` call."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("n_instances", ctypes.c_int32),
+        ("n_slots", ctypes.c_int32),
+        ("n_frag", ctypes.c_int32),
+        ("n_out", ctypes.c_int32),
+        ("threshold", ctypes.c_double),
+        ("instances_dev", ctypes.c_void_p),
+        ("instances_host", ctypes.c_void_p),
+        ("mean_dev", ctypes.c_void_p),
+        ("slot_frag_dev", ctypes.c_void_p),
+        ("frag_sent_dev", ctypes.c_void_p),
+        ("avg_out_dev", ctypes.c_void_p),
+        ("keep_out_dev", ctypes.c_void_p),
+    ]
+
+
 class OpWorkspaceRegion(ctypes.Structure):
     """``op_workspace_region``: one region of the forward's workspace (``op_debug_workspace_layout``)."""
 
@@ -443,6 +485,12 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "op_assemble_rows"):  # (prepared contexts, additive to ABI 10)
         lib.op_assemble_rows.restype = ci
         lib.op_assemble_rows.argtypes = [vp, ctypes.POINTER(OpAssembleRequest), vp, vp]
+    if hasattr(lib, "op_planned_fragment_means"):  # (prepared requests, additive to ABI 10)
+        lib.op_planned_fragment_means.restype = ci
+        lib.op_planned_fragment_means.argtypes = [vp, ctypes.POINTER(OpAssembleRequest), ctypes.POINTER(OpPlannedMeansRequest), vp]
+    if hasattr(lib, "op_sentence_decisions"):
+        lib.op_sentence_decisions.restype = ci
+        lib.op_sentence_decisions.argtypes = [vp, ctypes.POINTER(OpDecisionsRequest), vp]
     lib.op_segment_means.restype = ci
     lib.op_segment_means.argtypes = [vp, vp, ci, vp, ci, vp, vp]
     lib.op_debug_capture_hidden.restype = ci

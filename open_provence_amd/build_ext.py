@@ -25,18 +25,20 @@ _COMMON = [CSRC / "opk_common.hip.h"]
 _ROWGEMM = [CSRC / name for name in ("opk_rowgemm.hip.h", "opk_rowgemm_pack.hip.h", "opk_rowgemm_stream.hip.h", "opk_rowgemm_ln.hip.h", "opk_kstream.hip.h",
                                      "opk_rowgemm_phase1.hip.h", "opk_rowgemm_mlp.hip.h", "opk_rowgemm_mlp_ops.inc", "opk_rowgemm_mlp_loop.inc",
                                      "opk_rowgemm_qkv_pairs.hip.h", "opk_rowgemm_chunks.hip.h")]
-_INTERNAL = _COMMON + [CSRC / "op_internal.h", CSRC / "op_policy.h", CSRC / "opk_f32.hip.h", CSRC / "opk_attn.hip.h", CSRC / "opk_attn_probs.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
+_INTERNAL = _COMMON + [INCLUDE, CSRC / "op_internal.h", CSRC / "op_policy.h", CSRC / "opk_f32.hip.h", CSRC / "opk_attn.hip.h", CSRC / "opk_attn_probs.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
 
 _PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
 _AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
 _LOSS = CSRC / "opk_loss.hip.h"  # the evaluation losses: fp64 terms, fixed-order reduction
 _POOL = CSRC / "opk_pool.hip.h"  # pooled hidden states: the reduction of the scratch entry, fixed-order fp64 mean
 _ASSEMBLE = CSRC / "opk_assemble.hip.h"  # prepared contexts: rows laid out on the device from a resident corpus
+_PAIRWISE = CSRC / "opk_pairwise.hip.h"  # numpy's pairwise sums, float32 and float64
+_DECIDE = CSRC / "opk_decide.hip.h"  # prepared requests: fragment means from the row plan, sentence decisions
 
 # (object name, source, extra defines, headers it depends on)
 UNITS = [
     ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_plan.h", CSRC / "op_kernel_sets.h", CSRC / "op_sets.h", CSRC / "opk_small.hip.h",
-                                                      CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, _POOL, INCLUDE]),
+                                                      CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, _POOL, _PAIRWISE]),
     ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"], _INTERNAL),
     ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"], _INTERNAL),
     ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"], _INTERNAL),
@@ -54,6 +56,7 @@ UNITS = [
     ("op_launch_probe", CSRC / "op_launch_probe.hip", [], _INTERNAL + [CSRC / "opk_probe.hip.h"]),
     ("op_launch_loss", CSRC / "op_launch_loss.hip", [], [_LOSS]),
     ("op_launch_assemble", CSRC / "op_launch_assemble.hip", [], _INTERNAL + [_ASSEMBLE]),
+    ("op_launch_decide", CSRC / "op_launch_decide.hip", [], _INTERNAL + [_DECIDE, _PAIRWISE]),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
 HEADERS = sorted({h for u in UNITS for h in u[3]})

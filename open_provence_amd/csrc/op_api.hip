@@ -2661,4 +2661,27 @@ int op_assemble_rows(op_handle* h, const op_assemble_request* req, int32_t* ids_
   return OP_OK;
 }
 
+int op_planned_fragment_means(op_handle* h, const op_assemble_request* rows, const op_planned_means_request* req, void* hip_stream) {
+  // (the requests first, on the host copies -- opp::check_planned_means: nothing is enqueued before the last check)
+  const opp::Refusal refused = opp::check_planned_means(rows, req);
+  if (refused.code != OP_OK) return fail(h, refused);
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_planned_fragment_means: NULL handle");
+  if (rows->n_rows == 0 || req->slot_off_host[rows->n_rows] == req->slot_off_host[0]) return OP_OK;  // (no fragment in any row)
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  opl::launch_planned_fragment_means(reinterpret_cast<hipStream_t>(hip_stream), *rows, *req);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
+int op_sentence_decisions(op_handle* h, const op_decisions_request* req, void* hip_stream) {
+  const opp::Refusal refused = opp::check_decisions(req);
+  if (refused.code != OP_OK) return fail(h, refused);
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_sentence_decisions: NULL handle");
+  if (req->n_instances == 0) return OP_OK;  // (n_out is 0 too: the instances tile the outputs)
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  opl::launch_sentence_decisions(reinterpret_cast<hipStream_t>(hip_stream), *req);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
 }  // extern "C"

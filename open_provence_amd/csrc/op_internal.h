@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "../../include/open_provence_hip.h"
 #include "op_policy.h"
 #include "opk_attn.hip.h"
 #include "opk_attn_probs.hip.h"
@@ -117,5 +118,10 @@ constexpr int ASSEMBLE_PIECE_MAX = 8;
 void launch_assemble_rows(hipStream_t st, const int32_t* corpus, const int32_t* frag_off, int n_frag, int n_corpus, const int32_t* query_ids,
                           const int32_t* q_off, int n_queries, int n_query_tokens, const int32_t* const pieces[3], const int n_pieces[3],
                           const int32_t* plan, const int32_t* cu, int n_rows, int total, int32_t* out);
+
+// op_planned_fragment_means / op_sentence_decisions (opk_decide.hip.h; op_launch_decide.hip): the requests as the caller gave
+// them, checked (opp::check_planned_means / opp::check_decisions); n_rows > 0 resp. n_instances > 0.
+void launch_planned_fragment_means(hipStream_t st, const op_assemble_request& rows, const op_planned_means_request& req);
+void launch_sentence_decisions(hipStream_t st, const op_decisions_request& req);
 
 }  // namespace opl

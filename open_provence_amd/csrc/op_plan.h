@@ -459,4 +459,90 @@ inline Layout workspace_layout(int hidden, int inter, int cap_rows_pad, int n_se
   return lay;
 }
 
+// ---- prepared requests: fragment means and sentence decisions (op_planned_fragment_means, op_sentence_decisions) -----------------
+// Both look at the caller's HOST copies only, before anything is enqueued and before the handle is looked at.
+
+// `rows` is the op_assemble_request of the forward (its plan, offsets and cu_seqlens; the ids it names are not needed here).
+inline Refusal check_planned_means(const op_assemble_request* rows, const op_planned_means_request* req) {
+  const char* const fn = "op_planned_fragment_means";
+  if (!rows || !req) return refuse(OP_ERR_INVALID, "%s: %s is NULL", fn, !rows ? "rows" : "request");
+  if (rows->struct_bytes != sizeof(op_assemble_request))
+    return refuse(OP_ERR_INVALID, "%s: op_assemble_request.struct_bytes is %u, expected %zu", fn, rows->struct_bytes, sizeof(op_assemble_request));
+  if (req->struct_bytes != sizeof(op_planned_means_request))
+    return refuse(OP_ERR_INVALID, "%s: op_planned_means_request.struct_bytes is %u, expected %zu", fn, req->struct_bytes,
+                  sizeof(op_planned_means_request));
+  if (rows->n_frag < 0 || rows->n_queries < 0 || rows->n_rows < 0 || rows->total_tokens < 0 || req->n_slots < 0 || rows->n_prefix < 0 ||
+      rows->n_middle < 0 || rows->n_prefix > OP_ASSEMBLE_MAX_PIECE || rows->n_middle > OP_ASSEMBLE_MAX_PIECE)
+    return refuse(OP_ERR_INVALID, "%s: negative count (n_frag %d, n_queries %d, n_rows %d, total_tokens %d, n_slots %d) or template piece (%d, %d)",
+                  fn, rows->n_frag, rows->n_queries, rows->n_rows, rows->total_tokens, req->n_slots, rows->n_prefix, rows->n_middle);
+  if (rows->n_rows == 0) return Refusal{};
+  if (!rows->plan_dev || !rows->plan_host || !rows->cu_seqlens_dev || !rows->cu_seqlens_host || !rows->q_off_dev || !rows->q_off_host ||
+      !rows->frag_off_dev || !rows->frag_off_host || !req->slot_off_dev || !req->slot_off_host || !req->frag_shift_dev)
+    return refuse(OP_ERR_INVALID, "%s: a plan, cu_seqlens, offset, slot_off or frag_shift buffer is NULL", fn);
+  if (rows->q_off_host[0] != 0 || rows->frag_off_host[0] != 0) return refuse(OP_ERR_INVALID, "%s: offsets do not start at 0", fn);
+  for (int q = 0; q < rows->n_queries; ++q)
+    if (rows->q_off_host[q + 1] < rows->q_off_host[q]) return refuse(OP_ERR_INVALID, "%s: q_off decreases at query %d", fn, q);
+  const int n_corpus = rows->frag_off_host[rows->n_frag];
+  if (n_corpus < 0) return refuse(OP_ERR_INVALID, "%s: frag_off ends at %d", fn, n_corpus);
+  if (rows->cu_seqlens_host[0] != 0 || rows->cu_seqlens_host[rows->n_rows] != rows->total_tokens)
+    return refuse(OP_ERR_INVALID, "%s: cu_seqlens_host runs from %d to %d, expected 0 to total_tokens (%d)", fn, rows->cu_seqlens_host[0],
+                  rows->cu_seqlens_host[rows->n_rows], rows->total_tokens);
+  if (req->slot_off_host[0] < 0) return refuse(OP_ERR_INVALID, "%s: slot_off_host[0] is %d", fn, req->slot_off_host[0]);
+  int64_t slot = req->slot_off_host[0];
+  for (int r = 0; r < rows->n_rows; ++r) {
+    const int32_t* pr = rows->plan_host + (size_t)r * 4;
+    const int query = pr[0], first = pr[1], n = pr[2], clip = pr[3];
+    if (rows->cu_seqlens_host[r + 1] < rows->cu_seqlens_host[r]) return refuse(OP_ERR_INVALID, "%s: cu_seqlens_host decreases at row %d", fn, r);
+    if (query < 0 || query >= rows->n_queries) return refuse(OP_ERR_INVALID, "%s: row %d names query %d of %d", fn, r, query, rows->n_queries);
+    if (first < 0 || n < 0 || first > rows->n_frag - n)
+      return refuse(OP_ERR_INVALID, "%s: row %d takes fragments %d .. %d + %d of %d", fn, r, first, first, n, rows->n_frag);
+    if (n > 0) {
+      const int32_t* fo = rows->frag_off_host + first;
+      if (fo[0] < 0 || fo[1] < fo[0] || fo[n] < fo[1] || fo[n] > n_corpus)
+        return refuse(OP_ERR_INVALID, "%s: frag_off decreases or leaves the corpus at row %d", fn, r);
+      if (clip < 0 || clip > fo[1] - fo[0])
+        return refuse(OP_ERR_INVALID, "%s: row %d clips its first fragment of %d ids to %d", fn, r, fo[1] - fo[0], clip);
+    }
+    slot += n;
+    if (slot > (int64_t)req->n_slots || (int64_t)req->slot_off_host[r + 1] != slot)
+      return refuse(OP_ERR_INVALID, "%s: slot_off_host[%d] is %d, the plan's fragments end at %lld of %d slots", fn, r + 1,
+                    req->slot_off_host[r + 1], (long long)slot, req->n_slots);
+  }
+  if (rows->total_tokens > 0 && !req->keep_prob_dev) return refuse(OP_ERR_INVALID, "%s: keep_prob_dev is NULL", fn);
+  if (slot > (int64_t)req->slot_off_host[0] && (!req->mean_out_dev || !req->slot_frag_out_dev))
+    return refuse(OP_ERR_INVALID, "%s: mean_out_dev or slot_frag_out_dev is NULL", fn);
+  return Refusal{};
+}
+
+inline Refusal check_decisions(const op_decisions_request* req) {
+  const char* const fn = "op_sentence_decisions";
+  if (!req) return refuse(OP_ERR_INVALID, "%s: request is NULL", fn);
+  if (req->struct_bytes != sizeof(op_decisions_request))
+    return refuse(OP_ERR_INVALID, "%s: op_decisions_request.struct_bytes is %u, expected %zu", fn, req->struct_bytes, sizeof(op_decisions_request));
+  if (req->n_instances < 0 || req->n_slots < 0 || req->n_frag < 0 || req->n_out < 0)
+    return refuse(OP_ERR_INVALID, "%s: negative count (n_instances %d, n_slots %d, n_frag %d, n_out %d)", fn, req->n_instances, req->n_slots,
+                  req->n_frag, req->n_out);
+  if (req->n_instances > 0 && (!req->instances_dev || !req->instances_host)) return refuse(OP_ERR_INVALID, "%s: instances buffer is NULL", fn);
+  if (req->n_slots > 0 && (!req->mean_dev || !req->slot_frag_dev)) return refuse(OP_ERR_INVALID, "%s: mean_dev or slot_frag_dev is NULL", fn);
+  if (req->n_frag > 0 && !req->frag_sent_dev) return refuse(OP_ERR_INVALID, "%s: frag_sent_dev is NULL", fn);
+  if (req->n_out > 0 && (!req->avg_out_dev || !req->keep_out_dev)) return refuse(OP_ERR_INVALID, "%s: avg_out_dev or keep_out_dev is NULL", fn);
+  int64_t out = 0;
+  for (int i = 0; i < req->n_instances; ++i) {
+    const int32_t* in = req->instances_host + (size_t)i * OP_DECISIONS_INSTANCE_WORDS;
+    const int slot_begin = in[0], slot_end = in[1], out_begin = in[2], n_sent = in[3], sent_base = in[4], title = in[5];
+    if (slot_begin < 0 || slot_end < slot_begin || slot_end > req->n_slots)
+      return refuse(OP_ERR_INVALID, "%s: instance %d takes slots %d .. %d of %d", fn, i, slot_begin, slot_end, req->n_slots);
+    if (n_sent < 0 || (int64_t)out_begin != out || out + n_sent > (int64_t)req->n_out)
+      return refuse(OP_ERR_INVALID, "%s: instance %d writes sentences %d .. %d + %d, the previous one ended at %lld of %d", fn, i, out_begin,
+                    out_begin, n_sent, (long long)out, req->n_out);
+    if (sent_base < 0) return refuse(OP_ERR_INVALID, "%s: instance %d has item_sent_base %d", fn, i, sent_base);
+    if (title < -1 || title >= n_sent)
+      return refuse(OP_ERR_INVALID, "%s: instance %d has title_index %d outside [-1, %d)", fn, i, title, n_sent);
+    out += n_sent;
+  }
+  if (out != (int64_t)req->n_out)
+    return refuse(OP_ERR_INVALID, "%s: the instances hold %lld sentences, n_out is %d", fn, (long long)out, req->n_out);
+  return Refusal{};
+}
+
 }  // namespace opp

@@ -653,7 +653,32 @@ class HipEncoder:
 
         if not hasattr(self.lib, "op_assemble_rows"):
             raise _lib.HipLibraryError("this library has no op_assemble_rows")
-        device_side = {"corpus": corpus, "frag_off": frag_off, "query_ids": query_ids, "q_off": q_off, "plan": plan, "cu_seqlens": cu_seqlens}
+        req, _pieces, total = self._assemble_request(corpus, frag_off, frag_off_host, query_ids, q_off, q_off_host, template, plan, plan_host,
+                                                     cu_seqlens, cu_seqlens_host)
+        if out is None:
+            out = torch.empty(max(total, 0), dtype=torch.int32, device=self.device)
+        elif out.dtype != torch.int32 or out.device != self.device or not out.is_contiguous() or out.numel() < total:
+            raise ValueError(f"out must be a contiguous int32 tensor of at least {total} elements on {self.device}")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_assemble_rows(self._handle, ctypes.byref(req), ctypes.c_void_p(out.data_ptr()) if out.numel() else None,
+                                             ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_assemble_rows")
+        return out[:total]
+
+    def _assemble_request(self, corpus: "torch.Tensor | None", frag_off: torch.Tensor, frag_off_host: np.ndarray,
+                          query_ids: "torch.Tensor | None", q_off: torch.Tensor, q_off_host: np.ndarray, template: "Sequence[Sequence[int]]",
+                          plan: torch.Tensor, plan_host: np.ndarray, cu_seqlens: torch.Tensor,
+                          cu_seqlens_host: np.ndarray) -> "tuple[_lib.OpAssembleRequest, list[np.ndarray], int]":
+        """The ``op_assemble_request`` of :meth:`assemble_rows` and :meth:`planned_fragment_means` from their shared arguments,
+        sizes and dtypes checked -> (the request, the template pieces it points into, total tokens).  ``corpus`` / ``query_ids``
+        may be None where the call does not read the ids."""
+
+        device_side = {"frag_off": frag_off, "q_off": q_off, "plan": plan, "cu_seqlens": cu_seqlens}
+        if corpus is not None:
+            device_side["corpus"] = corpus
+        if query_ids is not None:
+            device_side["query_ids"] = query_ids
         for name, tensor in device_side.items():
             if tensor.dtype != torch.int32 or tensor.device != self.device or not tensor.is_contiguous():
                 raise ValueError(f"{name} must be a contiguous int32 tensor on {self.device}")
@@ -666,33 +691,111 @@ class HipEncoder:
         if (n_rows < 0 or plan_host.size != 4 * n_rows or plan.numel() != 4 * n_rows or cu_seqlens.numel() != n_rows + 1
                 or frag_off.numel() != frag_off_host.size or q_off.numel() != q_off_host.size or frag_off_host.size < 1 or q_off_host.size < 1):
             raise ValueError("plan / cu_seqlens / offsets: the host and device copies differ in size, or do not describe n_rows rows")
-        if corpus.numel() < int(frag_off_host[-1]) or query_ids.numel() < int(q_off_host[-1]):
+        if (corpus is not None and corpus.numel() < int(frag_off_host[-1])) or (query_ids is not None and query_ids.numel() < int(q_off_host[-1])):
             raise ValueError("corpus / query_ids are shorter than their offsets say")
         total = int(cu_seqlens_host[-1])
         pieces = [np.ascontiguousarray(np.asarray(piece, dtype=np.int32).reshape(-1)) for piece in template]
         if len(pieces) != 3:
             raise ValueError("template must be (prefix, middle, suffix)")
-        if out is None:
-            out = torch.empty(max(total, 0), dtype=torch.int32, device=self.device)
-        elif out.dtype != torch.int32 or out.device != self.device or not out.is_contiguous() or out.numel() < total:
-            raise ValueError(f"out must be a contiguous int32 tensor of at least {total} elements on {self.device}")
         req = _lib.OpAssembleRequest()
         req.struct_bytes = ctypes.sizeof(_lib.OpAssembleRequest)
         req.n_frag, req.n_queries, req.n_rows, req.total_tokens = int(frag_off_host.size) - 1, int(q_off_host.size) - 1, n_rows, total
         req.n_prefix, req.n_middle, req.n_suffix = (int(p.size) for p in pieces)
         req.prefix, req.middle, req.suffix = (p.ctypes.data if p.size else None for p in pieces)
-        req.corpus_dev = corpus.data_ptr() if corpus.numel() else None
+        req.corpus_dev = corpus.data_ptr() if corpus is not None and corpus.numel() else None
         req.frag_off_dev, req.frag_off_host = frag_off.data_ptr(), frag_off_host.ctypes.data
-        req.query_ids_dev = query_ids.data_ptr() if query_ids.numel() else None
+        req.query_ids_dev = query_ids.data_ptr() if query_ids is not None and query_ids.numel() else None
         req.q_off_dev, req.q_off_host = q_off.data_ptr(), q_off_host.ctypes.data
         req.plan_dev, req.plan_host = (plan.data_ptr(), plan_host.ctypes.data) if n_rows else (None, None)
         req.cu_seqlens_dev, req.cu_seqlens_host = cu_seqlens.data_ptr(), cu_seqlens_host.ctypes.data
+        return req, pieces, total
+
+    def planned_fragment_means(self, frag_off: torch.Tensor, frag_off_host: np.ndarray, q_off: torch.Tensor, q_off_host: np.ndarray,
+                               template: "Sequence[Sequence[int]]", plan: torch.Tensor, plan_host: np.ndarray, cu_seqlens: torch.Tensor,
+                               cu_seqlens_host: np.ndarray, keep_prob: torch.Tensor, frag_shift: torch.Tensor, slot_off: torch.Tensor,
+                               slot_off_host: np.ndarray, mean_out: torch.Tensor, slot_frag_out: torch.Tensor) -> None:
+        """``op_planned_fragment_means``: for the rows :meth:`assemble_rows` laid out from the same ``plan`` (same arguments,
+        without the ids), the mean of ``keep_prob`` (fp32, the forward's keep-probabilities) over every fragment's token range
+        -- derived on the device from the plan, shifted left by ``frag_shift[f]`` (int32, per fragment of the corpus) and
+        clamped to the row; numpy's float32 pairwise order bit for bit, 1.0 for an empty range -- into ``mean_out[slot]``
+        (fp32), and the fragment's number into ``slot_frag_out[slot]`` (int32), ``slot = slot_off[row] + j``.  ``slot_off`` /
+        ``slot_off_host`` (int32 ``[n_rows + 1]``) are the prefix sums of the rows' ``n_frag`` from any start inside the
+        outputs.  The library checks the request on the host copies and refuses before it enqueues.  Asynchronous on the
+        current stream."""
+
+        if not hasattr(self.lib, "op_planned_fragment_means"):
+            raise _lib.HipLibraryError("this library has no op_planned_fragment_means")
+        rows, _pieces, total = self._assemble_request(None, frag_off, frag_off_host, None, q_off, q_off_host, template, plan, plan_host,
+                                                      cu_seqlens, cu_seqlens_host)
+        n_rows = int(rows.n_rows)
+        for name, tensor, dtype in (("keep_prob", keep_prob, torch.float32), ("frag_shift", frag_shift, torch.int32), ("slot_off", slot_off, torch.int32),
+                                    ("mean_out", mean_out, torch.float32), ("slot_frag_out", slot_frag_out, torch.int32)):
+            if tensor.dtype != dtype or tensor.device != self.device or not tensor.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor on {self.device}")
+        if not isinstance(slot_off_host, np.ndarray) or slot_off_host.dtype != np.int32 or not slot_off_host.flags.c_contiguous:
+            raise ValueError("slot_off_host must be a C-contiguous int32 numpy array")
+        if (slot_off_host.size != n_rows + 1 or slot_off.numel() != n_rows + 1 or keep_prob.numel() < total
+                or frag_shift.numel() != int(frag_off_host.size) - 1 or slot_frag_out.numel() != mean_out.numel()):
+            raise ValueError("keep_prob / frag_shift / slot_off / outputs: sizes do not fit the rows, the corpus or each other")
+        req = _lib.OpPlannedMeansRequest()
+        req.struct_bytes = ctypes.sizeof(_lib.OpPlannedMeansRequest)
+        req.n_slots = int(mean_out.numel())
+        req.keep_prob_dev = keep_prob.data_ptr() if keep_prob.numel() else None
+        req.frag_shift_dev = frag_shift.data_ptr() if frag_shift.numel() else None
+        req.slot_off_dev, req.slot_off_host = slot_off.data_ptr(), slot_off_host.ctypes.data
+        req.mean_out_dev = mean_out.data_ptr() if mean_out.numel() else None
+        req.slot_frag_out_dev = slot_frag_out.data_ptr() if slot_frag_out.numel() else None
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            code = self.lib.op_assemble_rows(self._handle, ctypes.byref(req), ctypes.c_void_p(out.data_ptr()) if out.numel() else None,
-                                             ctypes.c_void_p(stream))
-        _lib.check(self.lib, self._handle, code, "op_assemble_rows")
-        return out[:total]
+            code = self.lib.op_planned_fragment_means(self._handle, ctypes.byref(rows), ctypes.byref(req), ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_planned_fragment_means")
+
+    def sentence_decisions(self, instances: torch.Tensor, instances_host: np.ndarray, means: torch.Tensor, slot_frag: torch.Tensor,
+                           frag_sent: torch.Tensor, threshold: float, avg_out: "torch.Tensor | None" = None,
+                           keep_out: "torch.Tensor | None" = None) -> "tuple[torch.Tensor, torch.Tensor]":
+        """``op_sentence_decisions``: per (query, context) instance ``{slot_begin, slot_end, sent_out_begin, n_sentences,
+        item_sent_base, title_index}`` (``instances`` int32 ``[n, 6]`` and its host copy) the sentences' averages over the
+        fragment means in ``means[slot]`` (fp32; ``slot_frag[slot]`` names the fragment, ``frag_sent[f]`` its corpus-wide
+        sentence) -- fp64, numpy's pairwise order, Python's ``max(0.0, min(avg, 1.0))`` -- and ``avg > threshold`` with the
+        title rule -> ``(avg[n_out] fp64, keep[n_out] uint8)`` on this device, ``n_out`` = the instances' sentences, which tile
+        the outputs in order.  Asynchronous on the current stream; ``avg_out`` / ``keep_out`` or new tensors."""
+
+        if not hasattr(self.lib, "op_sentence_decisions"):
+            raise _lib.HipLibraryError("this library has no op_sentence_decisions")
+        for name, tensor, dtype in (("instances", instances, torch.int32), ("means", means, torch.float32), ("slot_frag", slot_frag, torch.int32),
+                                    ("frag_sent", frag_sent, torch.int32)):
+            if tensor.dtype != dtype or tensor.device != self.device or not tensor.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor on {self.device}")
+        words = _lib.OP_DECISIONS_INSTANCE_WORDS
+        if (not isinstance(instances_host, np.ndarray) or instances_host.dtype != np.int32 or not instances_host.flags.c_contiguous
+                or instances_host.size % words or instances.numel() != instances_host.size):
+            raise ValueError(f"instances_host must be a C-contiguous int32 numpy array of {words} words per instance, as large as instances")
+        if slot_frag.numel() != means.numel():
+            raise ValueError("means and slot_frag differ in size")
+        table = instances_host.reshape(-1, words)
+        n_out = int(table[:, 3].sum()) if table.shape[0] else 0
+        if avg_out is None:
+            avg_out = torch.empty(n_out, dtype=torch.float64, device=self.device)
+        if keep_out is None:
+            keep_out = torch.empty(n_out, dtype=torch.uint8, device=self.device)
+        for name, tensor, dtype in (("avg_out", avg_out, torch.float64), ("keep_out", keep_out, torch.uint8)):
+            if tensor.dtype != dtype or tensor.device != self.device or not tensor.is_contiguous() or tensor.numel() != n_out:
+                raise ValueError(f"{name} must be a contiguous {dtype} tensor of {n_out} elements on {self.device}")
+        req = _lib.OpDecisionsRequest()
+        req.struct_bytes = ctypes.sizeof(_lib.OpDecisionsRequest)
+        req.n_instances, req.n_slots, req.n_frag, req.n_out = int(table.shape[0]), int(means.numel()), int(frag_sent.numel()), n_out
+        req.threshold = float(threshold)
+        req.instances_dev, req.instances_host = (instances.data_ptr(), instances_host.ctypes.data) if table.shape[0] else (None, None)
+        req.mean_dev = means.data_ptr() if means.numel() else None
+        req.slot_frag_dev = slot_frag.data_ptr() if slot_frag.numel() else None
+        req.frag_sent_dev = frag_sent.data_ptr() if frag_sent.numel() else None
+        req.avg_out_dev = avg_out.data_ptr() if n_out else None
+        req.keep_out_dev = keep_out.data_ptr() if n_out else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_sentence_decisions(self._handle, ctypes.byref(req), ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_sentence_decisions")
+        return avg_out, keep_out
 
     def forward_packed(
         self,

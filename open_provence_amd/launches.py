@@ -62,7 +62,8 @@ class Launch:
     """One enqueued forward of this process.  ``pool``: the staging slot its results land in; ``total`` / ``rows``: tokens and
     rows of the launch; ``seg_counts``: ranges per row when the means are taken on the device, else None; ``alive``: the
     device tensors of the launch, held until it is collected; ``shard``: the row assignment of a row-sharded call
-    (:func:`launch_rows`); ``retry`` / ``f8`` / ``slot`` / ``ids_dev``: what the range guard needs to repeat it."""
+    (:func:`launch_rows`); ``retry`` / ``f8`` / ``slot`` / ``ids_dev``: what the range guard needs to repeat it; ``planned``: the
+    tables of a prepared request whose fragment means come from the row plan (``op_planned_fragment_means``), for the repeat too."""
 
     event: Any
     pool: Any
@@ -76,6 +77,7 @@ class Launch:
     f8: bool = False
     slot: int | None = None
     ids_dev: Any = None
+    planned: dict[str, Any] | None = None
 
     @classmethod
     def empty(cls, cu: Any, reduced: bool) -> "Launch":
@@ -177,14 +179,16 @@ def launch_rows(model, rows: list[list[int]], segments: list[list[tuple[int, int
 
 def enqueue_packed(model, ids_np: np.ndarray | None, cu_np: np.ndarray, max_len: int, seg_flat: np.ndarray | None,
                    seg_counts: list[int] | None, reuse_slot: int | None = None, *, assemble: dict[str, Any] | None = None,
-                   ids_dev: torch.Tensor | None = None) -> Launch:
+                   ids_dev: torch.Tensor | None = None, planned: dict[str, Any] | None = None) -> Launch:
     """Enqueue one forward over packed rows (:func:`pack_launch`); also what the range guard of the fp16 + e4m3
     kernel sets repeats, see :func:`guard_launch`."""
 
     retry = (ids_np, cu_np, max_len, seg_flat, seg_counts)
     # Prepared contexts (``ids_np`` is None): the ids are laid out on the device by ``assemble`` (``_assemble_on_device``
     # from the request's plan) or, the range guard's repeat, are the launch's own ``ids_dev`` once more.  They were
-    # checked when the corpus and the request's queries were uploaded.
+    # checked when the corpus and the request's queries were uploaded.  With ``assemble["means"]`` (or, the repeat, ``planned``)
+    # the fragment means follow from the same plan on the device (``_planned_means_on_device``), into the forward's slice of
+    # the request's buffer; 4 bytes per fragment come back for the range guard, as with ``seg_flat``.
     if ids_np is not None:
         model.encoder.check_ids(ids_np)
     total, n_rows, nl = int(cu_np[-1]), len(cu_np) - 1, int(model.dims.num_labels)
@@ -211,19 +215,27 @@ def enqueue_packed(model, ids_np: np.ndarray | None, cu_np: np.ndarray, max_len:
         np.copyto(pool["ids_np"][: plan_np.size], plan_np.reshape(-1))
         plan_dev = pool["ids"][: plan_np.size].to(dev, non_blocking=True)
         ids_dev = model._assemble_on_device(assemble, plan_dev, plan_np, cu_dev, cu_np)
+        if "means" in assemble:
+            planned = dict(assemble, plan_dev=plan_dev)
     keep_dev = torch.empty(total, dtype=torch.float32, device=dev)
     seg_dev = means_dev = None
     n_seg = 0
-    if seg_counts is not None:
+    if planned is not None:
+        seg_flat, seg_counts = None, planned["seg_counts"]
+        n_seg = sum(seg_counts)
+    elif seg_counts is not None:
         n_seg = sum(seg_counts)
         if 2 * n_seg > pool["seg"].numel():
             seg_flat = seg_counts = None  # (cannot happen for non-empty fragments; fall back to the token payload)
-    if seg_counts is not None:
+    if seg_counts is not None and planned is None:
         np.copyto(pool["seg_np"][: 2 * n_seg], seg_flat)
         seg_dev = pool["seg"][: 2 * n_seg].to(dev, non_blocking=True).view(n_seg, 2)
     _, rank_dev = model.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev, ids_host=ids_np)
     count_forward(model, n_rows, total)
-    if seg_counts is not None:
+    if planned is not None:
+        means_dev = model._planned_means_on_device(planned, cu_dev, cu_np, keep_dev)
+        pool["keep"][:n_seg].copy_(means_dev, non_blocking=True)
+    elif seg_counts is not None:
         means_dev = model.encoder.segment_means(keep_dev, seg_dev)
         pool["keep"][:n_seg].copy_(means_dev, non_blocking=True)
     else:
@@ -233,7 +245,7 @@ def enqueue_packed(model, ids_np: np.ndarray | None, cu_np: np.ndarray, max_len:
     event.record(torch.cuda.current_stream(dev))
     return Launch(event=event, pool=pool, total=total, rows=n_rows, cu=cu_np, seg_counts=seg_counts,
                   alive=(ids_dev, cu_dev, keep_dev, rank_dev, seg_dev, means_dev), retry=retry,
-                  f8=model.encoder.f8_active(), slot=slot, ids_dev=ids_dev if ids_np is None else None)
+                  f8=model.encoder.f8_active(), slot=slot, ids_dev=ids_dev if ids_np is None else None, planned=planned)
 
 
 def guard_launch(model, launch: Launch) -> Launch:
@@ -254,7 +266,8 @@ def guard_launch(model, launch: Launch) -> Launch:
         return launch  # (nothing to fall back to: the caller reports the NaN)
     launch.alive = None
     # (a device-assembled launch is repeated on the ids it laid out: the same device buffer, no second assembly)
-    again = model._enqueue_packed(*launch.retry, reuse_slot=launch.slot, ids_dev=launch.ids_dev)
+    # (... and its planned fragment means are taken again, into the same slice of the request's buffer)
+    again = model._enqueue_packed(*launch.retry, reuse_slot=launch.slot, ids_dev=launch.ids_dev, planned=launch.planned)
     again.shard = launch.shard
     again.event.synchronize()
     return again

@@ -903,6 +903,7 @@ class OpenProvenceModel:
     _launch_rows = launches.launch_rows
     _enqueue_packed = launches.enqueue_packed
     _guard_launch = launches.guard_launch
+    _finish_launch = launches.finish_launch
     _collect_rows = launches.collect_rows
     _collect_packed = launches.collect_packed
 
@@ -1381,27 +1382,38 @@ class OpenProvenceModel:
             self._store_raw_predictions(chunk, ranges_per_job, queries, states, rank, keeps)
         return elapsed
 
-    def _store_raw_predictions(self, chunk, ranges_per_job, queries, states, rank, keeps) -> None:
+    @staticmethod
+    def _ranking_scores(rank: torch.Tensor) -> list[float]:
+        """Ranking logits ``[rows, nl]`` (or flat) -> the rows' scores as Python floats."""
+
         rank_scores = rank[:, 0] if rank.ndim == 2 and rank.shape[1] > 1 else rank.reshape(-1)
         # = _ranking_score row by row (ref :2913-2916), bit for bit: ATen's vectorized sigmoid of a contiguous batch differs
         # from the scalar one the reference's one-row tensors take by 1 ulp in ~4 % of the elements -- and by WHICH elements
         # depends on a row's position in the batch.  A strided view sends every element through the scalar functor.
         spread = torch.empty((rank_scores.numel(), 2), dtype=torch.float32)
         spread[:, 0] = rank_scores.reshape(-1).to(torch.float32)
-        scores = torch.sigmoid(spread[:, 0]).tolist()
+        return torch.sigmoid(spread[:, 0]).tolist()
+
+    def _warn_nan_once(self) -> None:
+        if self.__dict__.get("_nan_warned"):
+            return
+        # The fp16 + e4m3 kernel sets turn an MLP activation beyond fp16's range into Inf on purpose
+        # (csrc/opk_common.hip.h: set_overflowing_conversions) and _guard_launch / _predict_rows_local have already
+        # repeated such a batch on the (hi, lo) bf16 sets: what arrives here is NaN in fp32-range arithmetic, i.e.
+        # what the reference computes for this checkpoint / input too.  It goes on as the reference's does (a NaN
+        # probability fails `> threshold`, standalone.py:3130) -- said once, not raised: a drop-in must not fail
+        # where the reference returns, and a raise on one rank of a process group would strand the others.
+        self.__dict__["_nan_warned"] = True
+        LOGGER.warning("the forward returned NaN for a (query, context) block on kernel set %r (every set with an fp16 operand "
+                       "plane has been left by now): the checkpoint holds non-finite weights or the inputs overflow fp32; results "
+                       "follow the reference (NaN scores)", self.encoder.effective_policy()["kernel_set"] if self._forward_is_native() else "replaced forward")
+
+    def _store_raw_predictions(self, chunk, ranges_per_job, queries, states, rank, keeps) -> None:
+        scores = self._ranking_scores(rank)
         for i, job in enumerate(chunk):
             reduced = isinstance(keeps[i], list)  # per-fragment means from the device (see _launch_rows)
-            if (scores[i] != scores[i] or (reduced and any(m != m for m in keeps[i]))) and not self.__dict__.get("_nan_warned"):
-                # The fp16 + e4m3 kernel sets turn an MLP activation beyond fp16's range into Inf on purpose
-                # (csrc/opk_common.hip.h: set_overflowing_conversions) and _guard_launch / _predict_rows_local have already
-                # repeated such a batch on the (hi, lo) bf16 sets: what arrives here is NaN in fp32-range arithmetic, i.e.
-                # what the reference computes for this checkpoint / input too.  It goes on as the reference's does (a NaN
-                # probability fails `> threshold`, standalone.py:3130) -- said once, not raised: a drop-in must not fail
-                # where the reference returns, and a raise on one rank of a process group would strand the others.
-                self.__dict__["_nan_warned"] = True
-                LOGGER.warning("the forward returned NaN for a (query, context) block on kernel set %r (every set with an fp16 operand "
-                               "plane has been left by now): the checkpoint holds non-finite weights or the inputs overflow fp32; results "
-                               "follow the reference (NaN scores)", self.encoder.effective_policy()["kernel_set"] if self._forward_is_native() else "replaced forward")
+            if scores[i] != scores[i] or (reduced and any(m != m for m in keeps[i])):
+                self._warn_nan_once()
             states[(job["query_idx"], job["context_idx"])].raw_blocks.append(
                 (
                     job["block_idx"],
@@ -1529,12 +1541,30 @@ class OpenProvenceModel:
                 "device": dev, "ids": torch.from_numpy(ids_np).to(dev), "frag_off": torch.from_numpy(frag_off_np).to(dev),
                 "frag_off_np": frag_off_np, "pieces": pieces,
             }
+            # the tables of the last stages on the device (an eligible corpus; 8 more bytes per fragment)
+            tables = corpus.decision_tables()
+            if tables is not None:
+                device["frag_shift"] = torch.from_numpy(tables["frag_shift"]).to(dev)
+                device["frag_sent"] = torch.from_numpy(tables["frag_sent"]).to(dev)
         return device
 
     def _assemble_on_device(self, assemble: dict[str, Any], plan_dev, plan_np, cu_dev, cu_np) -> torch.Tensor:
         corpus, queries = assemble["corpus"], assemble["queries"]
         return self.encoder.assemble_rows(corpus["ids"], corpus["frag_off"], corpus["frag_off_np"], queries["ids"], queries["off"],
                                           queries["off_np"], corpus["pieces"], plan_dev, plan_np, cu_dev, cu_np)
+
+    def _planned_means_on_device(self, planned: dict[str, Any], cu_dev, cu_np, keep_dev) -> torch.Tensor:
+        """The fragment means of one forward of a prepared request, from its plan (``planned``: the forward's ``assemble``
+        with ``plan_dev``) -> the forward's slice of the request's means buffer (``means["values"]``)."""
+
+        corpus, queries, means = planned["corpus"], planned["queries"], planned["means"]
+        first, last = means["rows"]
+        self.encoder.planned_fragment_means(
+            corpus["frag_off"], corpus["frag_off_np"], queries["off"], queries["off_np"], corpus["pieces"], planned["plan_dev"], planned["plan"],
+            cu_dev, cu_np, keep_dev, corpus["frag_shift"], means["slot_off"][first: last + 1], means["slot_off_np"][first: last + 1],
+            means["values"], means["slot_frag"])
+        slot_off = means["slot_off_np"]
+        return means["values"][int(slot_off[first]): int(slot_off[last])]
 
     def _gather_job_results(self, result, owned, info, error: BaseException | None = None):
         """Job-sharded ``process()``: every rank sends the post-processed fields of the contexts it owns to rank
@@ -1824,7 +1854,7 @@ class OpenProvenceModel:
         trace = ProcessPerformanceTrace(
             preprocess_seconds=preprocess_time, assembly_seconds=run.assembly_seconds, inference_seconds=inference_time,
             postprocess_seconds=post_time, total_seconds=perf_counter() - start_total, **timing)
-        runtime = rq.runtime_facts(self, forward_stats)
+        runtime = rq.runtime_facts(self, forward_stats, run.prepared_decisions)
         if runtime:
             object.__setattr__(trace, "runtime", runtime)  # (frozen dataclass: an attribute beside its ten fields)
         if debug_callback is not None:

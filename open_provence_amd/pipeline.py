@@ -1120,6 +1120,107 @@ def postprocess_contexts(
     return out
 
 
+def postprocess_decided(
+    queries: list[str],
+    contexts: list[list[Any]],
+    items: Sequence[Sequence[Any]],
+    instance_of: Sequence[Sequence[int]],
+    instance_rows: Sequence[tuple[int, int]],
+    instance_sentences: Sequence[int],
+    scores: Sequence[float],
+    averages: np.ndarray,
+    keeps: np.ndarray,
+    *,
+    use_best_reranker_score: bool,
+    want_sentence_probabilities: bool,
+    want_sentence_texts: bool,
+    first_line_as_title: bool,
+    zero_score_when_empty: bool,
+) -> PostprocessResult:
+    """:func:`postprocess_contexts` for a prepared request whose sentence decisions were taken on the device
+    (``op_sentence_decisions``): the texts, the compression and the context's score from flat arrays.
+
+    ``items[q][c]``: the prepared item of context ``c`` of query ``q`` (``sentences``, ``prefix_sentences``, ``fragments``,
+    ``context_text``); ``instance_of[q][c]``: its instance, or -1 for a context without rows (the branches of
+    :func:`postprocess_contexts` for those); per instance ``instance_rows`` = its rows ``[first, last)`` in block order --
+    ``scores`` holds one ranking score per row -- and ``instance_sentences`` = where its sentences start in ``averages``
+    (float64, already clamped) and ``keeps`` (the threshold and the title rule applied)."""
+
+    out = PostprocessResult([], [], [], [] if want_sentence_texts else None, [] if want_sentence_texts else None, [],
+                            [] if want_sentence_probabilities else None)
+    for q_idx in range(len(queries)):
+        q_pruned: list[str] = []
+        q_scores: list[float | None] = []
+        q_comp: list[float] = []
+        q_kept: list[list[str]] = []
+        q_removed: list[list[str]] = []
+        q_titles: list[Any] = []
+        q_probs: list[list[float]] = []
+        for c_idx, entry in enumerate(contexts[q_idx]):
+            item = items[q_idx][c_idx]
+            inst = instance_of[q_idx][c_idx]
+            if inst < 0:  # no row went through a forward: no fragments, or no blocks
+                prefix = tuple(str(p) for p in item.prefix_sentences)
+                fallback_title: Any = None
+                if first_line_as_title and prefix:
+                    fallback_title = prefix[0] if len(prefix) == 1 else list(prefix)
+                q_pruned.append(entry)
+                q_scores.append(None)
+                q_comp.append(0.0)
+                q_removed.append([])
+                q_titles.append(fallback_title)
+                if not item.fragments:
+                    q_kept.append([entry] if entry else [])
+                    q_probs.append([])
+                else:
+                    q_kept.append(list(item.sentences))
+                    q_probs.append([1.0] * len(item.sentences))
+                continue
+
+            first_row, last_row = instance_rows[inst]
+            # the first block's score, or the best one: score_fragments' order and max()
+            ranking: float | None = scores[first_row]
+            if use_best_reranker_score:
+                for row in range(first_row + 1, last_row):
+                    ranking = max(ranking, scores[row])
+
+            sentences = item.sentences
+            n_prefix = len(item.prefix_sentences)
+            at = instance_sentences[inst]
+            keep = keeps[at: at + len(sentences)].tolist()
+            kept = [s for s, k in zip(sentences, keep) if k]
+            removed = [s for s, k in zip(sentences, keep) if not k]
+            pruned_text = "".join(s for i, (s, k) in enumerate(zip(sentences, keep)) if k and i >= n_prefix)
+            original = item.context_text
+            compression = (len(original) - len(pruned_text)) / max(len(original), 1) * 100.0
+            if zero_score_when_empty and not pruned_text.strip():
+                ranking = 0.0
+            if item.prefix_sentences:
+                title_value: Any = item.prefix_sentences[0] if len(item.prefix_sentences) == 1 else list(item.prefix_sentences)
+            else:
+                title_value = None
+
+            q_pruned.append(pruned_text)
+            q_scores.append(ranking)
+            q_comp.append(compression)
+            q_kept.append(kept)
+            q_removed.append(removed)
+            q_titles.append(title_value)
+            q_probs.append(averages[at: at + len(sentences)].tolist())  # (float64 -> Python float, exact)
+
+        out.pruned_contexts.append(q_pruned)
+        out.reranking_scores.append(q_scores)
+        out.compression_rates.append(q_comp)
+        if out.kept_sentences is not None:
+            out.kept_sentences.append(q_kept)
+        if out.removed_sentences is not None:
+            out.removed_sentences.append(q_removed)
+        out.titles.append(q_titles)
+        if out.sentence_probabilities is not None:
+            out.sentence_probabilities.append(q_probs)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------
 # reordering (ref: _apply_reordering :3204-3312)
 # ---------------------------------------------------------------------------------------------

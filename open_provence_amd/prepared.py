@@ -153,6 +153,7 @@ class PreparedContexts:
         self.n_fragments = sum(len(item.fragments) for item in items)
         self.n_tokens = sum(len(f.token_ids) for item in items for f in item.fragments)
         self._device: dict[str, Any] | None = None  # the resident corpus, uploaded on first use with the native forward
+        self._decision_tables: "dict[str, np.ndarray] | None | bool" = False  # (False: not built yet; see decision_tables)
 
     def __len__(self) -> int:
         return len(self.items)
@@ -183,6 +184,59 @@ class PreparedContexts:
         frag_off[1:] = np.cumsum(lengths)
         ids = np.fromiter((t for item in self.items for f in item.fragments for t in f.token_ids), dtype=np.int32, count=self.n_tokens)
         return ids, frag_off
+
+    def decision_tables(self) -> "dict[str, np.ndarray] | None":
+        """The per-corpus tables behind the last stages of a request on the device (``op_planned_fragment_means``,
+        ``op_sentence_decisions``), built on first use -- or None for a corpus that is not eligible.  Per fragment, int32:
+
+        * ``frag_shift``: the left shift of ``pipeline.fragment_token_ranges`` / ``score_fragments``: 0 for a fragment of
+          sentence 0, else ``sum(prefix_token_counts[:min(k, len(counts))])`` for sentence index ``k``;
+        * ``frag_sent``: the corpus-wide number of its sentence, the item's sentence base plus ``sentence_index``;
+        * ``frag_first_id`` (host only): its first token id, -1 for a fragment without tokens (an empty context's fallback
+          sentence: a request that takes a row from it keeps the host stages);
+
+        and per item ``sent_base`` (``[n_items + 1]``, the prefix sums of ``len(sentences)``) and ``item_title`` (the sentence
+        ``always_select_title`` keeps when any is kept: 0 with prefix sentences or a title that is the first sentence, else
+        -1, as ``postprocess_contexts`` picks it).  Eligible: in every item
+        ``sentence_index`` does not decrease over the fragments and lies inside ``len(sentences)`` -- a sentence's fragments are
+        then one run of the context's fragments, which is what the device walks."""
+
+        if self._decision_tables is False:
+            n_sentences = np.fromiter((len(item.sentences) for item in self.items), dtype=np.int64, count=len(self.items))
+            sent_base = np.zeros(len(self.items) + 1, dtype=np.int64)
+            sent_base[1:] = np.cumsum(n_sentences)
+            tables = None
+            if int(sent_base[-1]) < 2**31 - 1 and self.n_tokens < 2**31 - 1:
+                frag_shift = np.zeros(self.n_fragments, dtype=np.int32)
+                frag_sent = np.zeros(self.n_fragments, dtype=np.int32)
+                frag_first_id = np.zeros(self.n_fragments, dtype=np.int32)
+                eligible, at = True, 0
+                for item, base in zip(self.items, sent_base.tolist()):
+                    counts = item.prefix_token_counts
+                    offsets = [0]
+                    for c in counts:
+                        offsets.append(offsets[-1] + c)
+                    previous, limit, last = 0, len(item.sentences), len(counts)
+                    for fragment in item.fragments:
+                        k = fragment.sentence_index
+                        if k < previous or k >= limit:
+                            eligible = False
+                            break
+                        previous = k
+                        frag_shift[at] = offsets[k if k < last else last] if k > 0 else 0
+                        frag_sent[at] = base + k
+                        frag_first_id[at] = fragment.token_ids[0] if fragment.token_ids else -1
+                        at += 1
+                    if not eligible:
+                        break
+                if eligible:
+                    item_title = np.fromiter(
+                        (0 if item.sentences and (item.prefix_sentences or item.title_is_first_sentence) else -1 for item in self.items),
+                        dtype=np.int32, count=len(self.items))
+                    tables = {"frag_shift": frag_shift, "frag_sent": frag_sent, "frag_first_id": frag_first_id,
+                              "sent_base": sent_base.astype(np.int32), "item_title": item_title}
+            self._decision_tables = tables
+        return self._decision_tables
 
 
 def as_request(question: Any, context: Any) -> "tuple[list[str], list[PreparedView], str] | None":

@@ -188,6 +188,10 @@ class Run:
     assembly_seconds: float = 0.0
     inference_seconds: float = 0.0
     blocks: int = 0
+    # a prepared request: where its fragment means and sentence decisions were taken ("device" / "host"), and on the device
+    # what post-processing needs (:class:`Decided`)
+    prepared_decisions: str | None = None
+    decided: "Decided | None" = None
 
 
 def run_raw_jobs(model, request: Request, run: Run, splitter, owned, thread_workers: int, preprocess_batch: int, batch_size: int,
@@ -307,6 +311,183 @@ def _plan_prepared_forward(model, layout: _RowLayout, rows: list[tuple], lengths
     return chunk, plan_np, ranges_per_job, segments, on_host
 
 
+# -- prepared requests whose fragment means and sentence decisions are taken on the device ---------------------------------------
+# OPEN_PROVENCE_PREPARED_DECISIONS, read at call time: "0" keeps the host stages (_plan_prepared_forward, score_fragments,
+# postprocess_contexts) for every prepared request; anything else lets an eligible request take the device path.  Unset = "0":
+# on the request the switch was to be judged by (scripts/process_e2e.py --prepared with its own question, whose letters begin
+# nearly every context under the char tokenizer) no request is eligible and the wall time does not fall; where requests are
+# eligible it falls by 16-23 % (profiles/prepared_decisions.txt).
+PREPARED_DECISIONS_DEFAULT = "0"
+
+
+@dataclass
+class Decided:
+    """A prepared request on the device path: its rows and (query, context) instances as flat tables, the request's device
+    buffers, and the ranking logits of the launches collected so far.  No ``ContextState``, no ``FragmentRecord`` is touched."""
+
+    tables: dict[str, np.ndarray]     # PreparedContexts.decision_tables()
+    corpus: dict[str, Any]            # the resident corpus (model._prepared_device_corpus)
+    items: list[list[Any]]            # per query, per context: the prepared item
+    instance_of: list[list[int]]      # ... and its instance, -1 for a context without rows
+    instance_item: np.ndarray         # per instance: its item's index in the corpus
+    instance_rows: list[tuple[int, int]]  # ... its rows [first, last) of the request, in block order
+    instance_slots: np.ndarray        # ... its fragments' slots [n, 2]
+    means: dict[str, Any]             # values / slot_frag [n_slots] and slot_off [n_rows + 1] on the device, slot_off_np
+    rank: np.ndarray                  # [n_rows, num_labels] ranking logits
+    nan_seen: bool = False
+
+
+def prepared_decisions_on_device(model, corpus) -> bool:
+    """What a prepared request needs, whatever its rows, for its last host stages to run on the device."""
+
+    lib = model.encoder.lib
+    return (os.getenv("OPEN_PROVENCE_PREPARED_DECISIONS", PREPARED_DECISIONS_DEFAULT) != "0"
+            and hasattr(lib, "op_planned_fragment_means") and hasattr(lib, "op_sentence_decisions")
+            and corpus.decision_tables() is not None)
+
+
+def _plan_decided(model, views: Sequence[PreparedView], q_lens: list[int], sep_len: int, n_fixed: int):
+    """The rows of a prepared request as flat arrays -> (plan [n_rows, 4] int32, row lengths int64, per query the items and
+    their instances, per instance its item / rows / slots).  Per row: four plan words and a length."""
+
+    items_all = views[0].corpus.items
+    tokenizer, max_length = model.tokenizer, model.max_length
+    plan_words: list[int] = []
+    lengths: list[int] = []
+    items: list[list[Any]] = []
+    instance_of: list[list[int]] = []
+    instance_item: list[int] = []
+    instance_rows: list[tuple[int, int]] = []
+    instance_slots: list[int] = []
+    n_slots = 0
+    for q_idx, view in enumerate(views):
+        q_len = q_lens[q_idx]
+        fixed = n_fixed + q_len
+        q_items, q_instances = [], []
+        for at in view.indices:
+            item = items_all[at]
+            q_items.append(item)
+            plan = item.blocks_for(tokenizer, q_len, sep_len, max_length)[1]
+            if not plan:
+                q_instances.append(-1)
+                continue
+            q_instances.append(len(instance_item))
+            instance_item.append(at)
+            first_row, base, slot_begin = len(lengths), item.frag_base, n_slots
+            for first, count, clip, ctx_len in plan:
+                plan_words += (q_idx, base + first, count, clip)
+                lengths.append(fixed + ctx_len)
+                n_slots += count
+            instance_rows.append((first_row, len(lengths)))
+            instance_slots += (slot_begin, n_slots)
+        items.append(q_items)
+        instance_of.append(q_instances)
+    return (np.array(plan_words, dtype=np.int32).reshape(-1, 4), np.array(lengths, dtype=np.int64), items, instance_of,
+            np.array(instance_item, dtype=np.int64), instance_rows, np.array(instance_slots, dtype=np.int32).reshape(-1, 2))
+
+
+def _run_decided(model, request: Request, run: Run, batch_size: int, query_token_ids: list[list[int]], t_asm: float) -> bool:
+    """The device path of :func:`run_prepared_request`; False (nothing enqueued, ``run`` untouched) when a row of the request
+    rules it out: a row without fragments or context tokens, or a first fragment that begins with an id of its query's
+    ``heads`` (its place in the row then does not follow from lengths alone)."""
+
+    views = request.views
+    corpus = views[0].corpus
+    template, q_lens = corpus.template, [len(q) for q in query_token_ids]
+    n_head = len(template.prefix) + len(template.middle)
+    n_fixed = n_head + len(template.suffix)
+    tables = corpus.decision_tables()
+    plan_np, lengths, items, instance_of, instance_item, instance_rows, instance_slots = _plan_decided(model, views, q_lens, request.sep_len, n_fixed)
+    n_rows = int(plan_np.shape[0])
+    if n_rows == 0:
+        return False
+    q_of_row = plan_np[:, 0]
+    if (plan_np[:, 2] <= 0).any() or (lengths - n_fixed - np.asarray(q_lens, dtype=np.int64)[q_of_row] <= 0).any():
+        return False
+    first_ids = tables["frag_first_id"][plan_np[:, 1]]
+    if (first_ids < 0).any():  # (a block that begins with a fragment without tokens)
+        return False
+    for q_idx, query in enumerate(query_token_ids):
+        heads = np.fromiter(set(template.prefix) | set(query) | set(template.middle), dtype=np.int64)
+        if heads.size and np.isin(first_ids[q_of_row == q_idx], heads).any():
+            return False
+
+    run.blocks += n_rows
+    spans = pl.plan_forward_chunks(lengths.tolist(), batch_size, model.forward_token_budget)
+    dev = model._runtime_device
+    corpus_dev = model._prepared_device_corpus(corpus)
+    slot_off_np = np.zeros(n_rows + 1, dtype=np.int32)
+    slot_off_np[1:] = np.cumsum(plan_np[:, 2])
+    n_slots = int(slot_off_np[-1])
+    means = {"values": torch.empty(n_slots, dtype=torch.float32, device=dev), "slot_frag": torch.empty(n_slots, dtype=torch.int32, device=dev),
+             "slot_off": torch.from_numpy(slot_off_np).to(dev), "slot_off_np": slot_off_np}
+    assemble = {"corpus": corpus_dev, "queries": _upload_queries(model, query_token_ids, q_lens)}
+    counts = plan_np[:, 2].tolist()
+    decided = Decided(tables, corpus_dev, items, instance_of, instance_item, instance_rows, instance_slots, means,
+                      np.empty((n_rows, int(model.dims.num_labels)), dtype=np.float32))
+    run.assembly_seconds += perf_counter() - t_asm
+
+    def collect(entry) -> None:
+        launch, start, stop = entry
+        launch, rank, values = model._finish_launch(launch)  # (the range guard's repeat runs the planned means again)
+        decided.rank[start:stop] = rank
+        decided.nan_seen = decided.nan_seen or bool(np.isnan(values).any())
+
+    in_flight: list[tuple] = []
+    for start, stop in spans:
+        t_asm = perf_counter()
+        cu_np = np.zeros(stop - start + 1, dtype=np.int32)
+        cu_np[1:] = np.cumsum(lengths[start:stop])
+        forward = dict(assemble, plan=plan_np[start:stop], means=dict(means, rows=(start, stop)), seg_counts=counts[start:stop])
+        run.assembly_seconds += perf_counter() - t_asm
+        t0 = perf_counter()
+        in_flight.append((model._enqueue_packed(None, cu_np, int(lengths[start:stop].max()), None, None, assemble=forward), start, stop))
+        if len(in_flight) > 1:
+            collect(in_flight.pop(0))
+        run.inference_seconds += perf_counter() - t0
+    t0 = perf_counter()
+    while in_flight:
+        collect(in_flight.pop(0))
+    run.inference_seconds += perf_counter() - t0
+    run.decided = decided
+    return True
+
+
+def postprocess_decided_request(model, request: Request, decided: Decided, *, threshold: float, always_select_title: bool,
+                                use_best_reranker_score: bool, sentence_probability_groups_requested: bool, collect_sentence_texts: bool,
+                                first_line_as_title: bool, zero_score_when_empty: bool) -> tuple[pl.PostprocessResult, float]:
+    """After the last launch of a device-path request is collected: ONE ``op_sentence_decisions`` over every instance, one copy
+    of the averages and keep flags, one synchronise, then the texts (``pipeline.postprocess_decided``) -> (result, seconds)."""
+
+    t0 = perf_counter()
+    tables, item_of = decided.tables, decided.instance_item
+    n_inst = int(item_of.shape[0])
+    sent_base = tables["sent_base"]
+    n_sent = sent_base[item_of + 1] - sent_base[item_of]
+    out_at = np.zeros(n_inst + 1, dtype=np.int64)
+    out_at[1:] = np.cumsum(n_sent)
+    n_out = int(out_at[-1])
+    instances = np.empty((n_inst, 6), dtype=np.int32)  # slot_begin, slot_end, sent_out_begin, n_sentences, item_sent_base, title_index
+    instances[:, 0:2] = decided.instance_slots
+    instances[:, 2], instances[:, 3], instances[:, 4] = out_at[:-1], n_sent, sent_base[item_of]
+    instances[:, 5] = tables["item_title"][item_of] if always_select_title else -1
+    dev = model._runtime_device
+    # averages (fp64) and keep flags (uint8) side by side in one buffer: one copy back, one synchronise
+    out_dev = torch.empty(9 * n_out, dtype=torch.uint8, device=dev)
+    model.encoder.sentence_decisions(torch.from_numpy(instances).to(dev), instances, decided.means["values"], decided.means["slot_frag"],
+                                     decided.corpus["frag_sent"], float(threshold), out_dev[: 8 * n_out].view(torch.float64), out_dev[8 * n_out:])
+    out_np = out_dev.cpu().numpy()
+    averages, keeps = out_np[: 8 * n_out].view(np.float64), out_np[8 * n_out:]
+    scores = model._ranking_scores(torch.from_numpy(decided.rank))
+    if decided.nan_seen or any(s != s for s in scores):
+        model._warn_nan_once()
+    result = pl.postprocess_decided(
+        request.queries, request.contexts, decided.items, decided.instance_of, decided.instance_rows, out_at, scores, averages, keeps,
+        use_best_reranker_score=use_best_reranker_score, want_sentence_probabilities=sentence_probability_groups_requested,
+        want_sentence_texts=collect_sentence_texts, first_line_as_title=first_line_as_title, zero_score_when_empty=zero_score_when_empty)
+    return result, perf_counter() - t0
+
+
 def run_prepared_request(model, request: Request, run: Run, batch_size: int) -> None:
     """The request-time half of ``process()`` on prepared contexts.
 
@@ -321,10 +502,18 @@ def run_prepared_request(model, request: Request, run: Run, batch_size: int) -> 
     views, queries, states, pending = request.views, request.queries, run.states, run.pending
     query_token_ids = [pl.tokenize_query(model.tokenizer, query) for query in queries]
     corpus = views[0].corpus
-    rows = prepared_rows(model, views, query_token_ids, request.sep_len, states)
-    run.blocks += len(rows)
     on_device = (model._forward_is_native() and corpus.template is not None and hasattr(model.encoder.lib, "op_assemble_rows")
                  and model.__dict__.get("_remote_forward") is None)
+    # An eligible corpus (prepared.decision_tables) on a library with op_planned_fragment_means / op_sentence_decisions: the
+    # fragments' ranges and means follow on the device from the plan of op_assemble_rows, the sentence decisions from the means
+    # (postprocess_decided_request) -- the host keeps four plan words and a length per row.  A request it does not fit (a row
+    # without context tokens, a context that begins with a token of its query or of the template) goes on below, as before.
+    run.prepared_decisions = "host"
+    if on_device and prepared_decisions_on_device(model, corpus) and _run_decided(model, request, run, batch_size, query_token_ids, t_asm):
+        run.prepared_decisions = "device"
+        return
+    rows = prepared_rows(model, views, query_token_ids, request.sep_len, states)
+    run.blocks += len(rows)
     if not rows or not on_device:
         inference_jobs = []
         for q_idx, c_idx, b_idx, item, blocks, _entry in rows:
@@ -377,8 +566,11 @@ def postprocess_and_gather(model, request: Request, run: Run, sharding: JobShard
     """-> (the per-query, per-context results -- on the gather's destination rank of a job-sharded call: of every rank --,
     post-processing seconds, the gather included)."""
 
-    *fields, post_time = model._postprocess_contexts(request.queries, request.contexts, run.states, **options)
-    result = pl.PostprocessResult(*fields)
+    if run.decided is not None:  # (a prepared request on the device path; never sharded)
+        result, post_time = postprocess_decided_request(model, request, run.decided, **options)
+    else:
+        *fields, post_time = model._postprocess_contexts(request.queries, request.contexts, run.states, **options)
+        result = pl.PostprocessResult(*fields)
     if sharding is not None:
         t_gather = perf_counter()
         sharding.entered = True
@@ -412,10 +604,13 @@ def owner_stage_seconds(model, start_total: float, assembly: float, stages: tupl
     return preprocess, inference, float(max(total_now - preprocess - inference - assembly, 0.0))
 
 
-def runtime_facts(model, forward_stats: dict[str, int]) -> dict[str, Any]:
-    """``performance_trace.runtime``: the kernel set and its calibration, the forwards of the call, the host replicas."""
+def runtime_facts(model, forward_stats: dict[str, int], prepared_decisions: str | None = None) -> dict[str, Any]:
+    """``performance_trace.runtime``: the kernel set and its calibration, the forwards of the call, the host replicas; on a
+    prepared request ``prepared_decisions``: ``"device"`` or ``"host"``, where its fragment means and sentence decisions were taken."""
 
     runtime: dict[str, Any] = {}
+    if prepared_decisions is not None:
+        runtime["prepared_decisions"] = prepared_decisions
     if model._forward_is_native() and getattr(model, "encoder", None) is not None:
         runtime["kernel_set"] = model.encoder.effective_policy()["kernel_set"]
         runtime["calibration"] = model.encoder.calibration

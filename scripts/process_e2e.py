@@ -106,6 +106,10 @@ def main():
     ap.add_argument("--prepared", action="store_true",
                     help="prepare the contexts once, outside the timed region (OpenProvenceModel.prepare_contexts), and time requests on the "
                     "prepared object; in-process only.  The line gains the one-off preparation time and the forwards of a request")
+    ap.add_argument("--question", default=None,
+                    help="the question, instead of the lower-case default.  With the char tokenizer every context begins with a letter of the "
+                    "default question, which keeps a prepared request on the host stages (INTEGRATION.md section 6, "
+                    "OPEN_PROVENCE_PREPARED_DECISIONS); an upper-case question shares no token id with the contexts")
     args = ap.parse_args()
     if args.prepared and (args.front_end or args.host_front_end):
         raise SystemExit("--prepared runs in this process: prepared contexts take no front-end")
@@ -117,6 +121,8 @@ def main():
     if args.stock_tokenizer:
         os.environ["E2E_STOCK_TOKENIZER"] = "1"
     question, contexts = make_request(args.contexts, args.chars)
+    if args.question is not None:
+        question = args.question
     budgets = [b.strip() for b in args.forward_tokens.split(",")] if args.forward_tokens else []
 
     def budget_value(text):
@@ -168,7 +174,7 @@ def main():
     torch.cuda.synchronize()
     audits_warm = audits_so_far()
     best = None
-    inference_all = []
+    inference_all, stages_all = [], []
     walls, forwards = [], None
     for _ in range(args.reps):
         r0 = resource.getrusage(resource.RUSAGE_SELF)
@@ -181,6 +187,7 @@ def main():
                  "minor_faults": r1.ru_minflt - r0.ru_minflt, "vol_ctx_switches": r1.ru_nvcsw - r0.ru_nvcsw,
                  "invol_ctx_switches": r1.ru_nivcsw - r0.ru_nivcsw}
         inference_all.append(round(float(out["timing"]["inference_seconds"]), 5))
+        stages_all.append({k: round(float(out["timing"][k]), 5) for k in ("assembly_seconds", "postprocess_seconds", "inference_seconds")})
         if best is None or dt < best[0]:
             best = (dt, out["timing"], usage)
         walls.append(round(dt, 5))
@@ -193,7 +200,9 @@ def main():
     if args.prepared:
         audit_info = {**audit_info, "prepared": True, "prepare_seconds": round(prepare_seconds, 4),
                       "prepare_stage_seconds": {k: round(float(v), 4) for k, v in prepared.timing.items()},
-                      "corpus_tokens": prepared.n_tokens, "corpus_device_bytes": prepared.device_bytes}
+                      "corpus_tokens": prepared.n_tokens, "corpus_device_bytes": prepared.device_bytes,
+                      "prepared_decisions": getattr(out["performance_trace"], "runtime", {}).get("prepared_decisions"),
+                      "stage_seconds_per_call": stages_all}
     audit_info = {**audit_info, "batch_size": args.batch_size, "forwards": forwards, "wall_s_per_call": walls,
                   "wall_s_median": round(float(np.median(walls)), 5)}
     print(json.dumps({**audit_info, "contexts": args.contexts, "chars": args.chars, "tokenizer": args.tokenizer, "workers": args.workers, "front_end_processes": args.front_end, "host_replicas": args.host_front_end, "wall_s": dt, "contexts_per_s": args.contexts / dt, "rusage": usage, "owner_trace": getattr(front, "last_trace", None),
