@@ -699,6 +699,33 @@ typedef struct op_planned_means_request {
 } op_planned_means_request;
 int op_planned_fragment_means(op_handle* h, const op_assemble_request* rows, const op_planned_means_request* req, void* hip_stream);
 
+/* Replaces: op_planned_fragment_means for a request whose contexts may also occur further LEFT in their rows, i.e. the
+ * reference's own way of placing a context (standalone.py:2104-2196): it does not compute where the context starts, it looks the
+ * whole context up in the finished row and takes the first place it occurs (`_find_subsequence`).  Almost always that is
+ * n_prefix + query length + n_middle; it is earlier when the context's ids also occur in prefix + query + middle, or in those
+ * followed by the beginning of the context's own copy -- and the fragments' ranges, means and kept sentences start there.
+ * Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).
+ *   rows, req                               exactly what op_planned_fragment_means takes, read and checked the same way
+ *   ids_dev [rows->total_tokens] int32      the rows themselves: the output of op_assemble_rows for the same `rows`
+ *   ctx_start_out_dev [rows->n_rows] int32  per row r, with head_len = n_prefix + query length + n_middle and n_ctx = the ids
+ *                                           of the row's fragments (the first one `clip` long where clip > 0), held to row
+ *                                           length - head_len: the smallest idx in [0, head_len] with
+ *                                           ids[idx + j] == ids[head_len + j] for every 0 <= j < n_ctx (idx = head_len always
+ *                                           qualifies).  A row without fragments or without context ids gets head_len and
+ *                                           none of its slots is written.
+ *   req->mean_out_dev, req->slot_frag_out_dev  as op_planned_fragment_means writes them, with every range starting from
+ *                                           ctx_start_out[r] instead of head_len: same shift, same clamp to [0, row length),
+ *                                           same float32 pairwise sum and float64 division, 1.0 for an empty range
+ * The request is checked on the host copies and the kernel holds every index it reads from the device copies inside the buffers
+ * all the same; every id it compares lies inside the row's own [cu[r], cu[r + 1]) within [0, total_tokens).  Asynchronous on
+ * hip_stream; the handle's state is neither read nor changed beyond its device and error text.  OP_ERR_INVALID, before anything
+ * is enqueued: every refusal of op_planned_fragment_means, and ids_dev or ctx_start_out_dev NULL while there are rows.
+ * Kernel: a wave per row; the lookup runs a lane per candidate place in ascending passes of 64 and ends with the first pass
+ * that holds a match (at most head_len x n_ctx id compares per row), then a lane per fragment; vector stores only, no atomics,
+ * no LDS (csrc/opk_decide.hip.h). */
+int op_located_fragment_means(op_handle* h, const op_assemble_request* rows, const op_planned_means_request* req, const int32_t* ids_dev,
+                              int32_t* ctx_start_out_dev, void* hip_stream);
+
 /* Replaces: the per-sentence loop of the reference's post-processing (standalone.py:3100-3140) for a PREPARED request: the
  * average of a sentence's fragment means, clamped to [0, 1], the threshold, and the title rule, on the slots
  * op_planned_fragment_means filled.  Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).

@@ -76,6 +76,7 @@ EXPORTED_SYMBOLS = (
     "op_segment_means",
     "op_assemble_rows",
     "op_planned_fragment_means",
+    "op_located_fragment_means",
     "op_sentence_decisions",
     "op_debug_workspace_layout",
     "op_debug_rope_tables",
@@ -488,6 +489,9 @@ def load_library() -> ctypes.CDLL:
     if hasattr(lib, "op_planned_fragment_means"):  # (prepared requests, additive to ABI 10)
         lib.op_planned_fragment_means.restype = ci
         lib.op_planned_fragment_means.argtypes = [vp, ctypes.POINTER(OpAssembleRequest), ctypes.POINTER(OpPlannedMeansRequest), vp]
+    if hasattr(lib, "op_located_fragment_means"):
+        lib.op_located_fragment_means.restype = ci
+        lib.op_located_fragment_means.argtypes = [vp, ctypes.POINTER(OpAssembleRequest), ctypes.POINTER(OpPlannedMeansRequest), vp, vp, vp]
     if hasattr(lib, "op_sentence_decisions"):
         lib.op_sentence_decisions.restype = ci
         lib.op_sentence_decisions.argtypes = [vp, ctypes.POINTER(OpDecisionsRequest), vp]

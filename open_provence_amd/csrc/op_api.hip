@@ -2673,6 +2673,18 @@ int op_planned_fragment_means(op_handle* h, const op_assemble_request* rows, con
   return OP_OK;
 }
 
+int op_located_fragment_means(op_handle* h, const op_assemble_request* rows, const op_planned_means_request* req, const int32_t* ids_dev,
+                              int32_t* ctx_start_out_dev, void* hip_stream) {
+  const opp::Refusal refused = opp::check_located_means(rows, req, ids_dev, ctx_start_out_dev);
+  if (refused.code != OP_OK) return fail(h, refused);
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "op_located_fragment_means: NULL handle");
+  if (rows->n_rows == 0) return OP_OK;  // (a row without fragments still gets its ctx_start)
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  opl::launch_located_fragment_means(reinterpret_cast<hipStream_t>(hip_stream), *rows, *req, ids_dev, ctx_start_out_dev);
+  OP_HIP(h, hipGetLastError());
+  return OP_OK;
+}
+
 int op_sentence_decisions(op_handle* h, const op_decisions_request* req, void* hip_stream) {
   const opp::Refusal refused = opp::check_decisions(req);
   if (refused.code != OP_OK) return fail(h, refused);

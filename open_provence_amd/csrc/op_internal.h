@@ -122,6 +122,9 @@ void launch_assemble_rows(hipStream_t st, const int32_t* corpus, const int32_t* 
 // op_planned_fragment_means / op_sentence_decisions (opk_decide.hip.h; op_launch_decide.hip): the requests as the caller gave
 // them, checked (opp::check_planned_means / opp::check_decisions); n_rows > 0 resp. n_instances > 0.
 void launch_planned_fragment_means(hipStream_t st, const op_assemble_request& rows, const op_planned_means_request& req);
+// op_located_fragment_means: the same requests (opp::check_located_means), the rows' ids [total_tokens] and ctx_start_out [n_rows]
+void launch_located_fragment_means(hipStream_t st, const op_assemble_request& rows, const op_planned_means_request& req, const int32_t* ids,
+                                   int32_t* ctx_start_out);
 void launch_sentence_decisions(hipStream_t st, const op_decisions_request& req);
 
 }  // namespace opl

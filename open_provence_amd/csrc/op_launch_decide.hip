@@ -1,4 +1,5 @@
-// op_launch_decide.hip -- launches of op_planned_fragment_means' and op_sentence_decisions' kernels (opk_decide.hip.h).
+// op_launch_decide.hip -- launches of op_planned_fragment_means', op_located_fragment_means' and op_sentence_decisions' kernels
+// (opk_decide.hip.h).
 #include "op_internal.h"
 #include "opk_decide.hip.h"
 
@@ -7,7 +8,7 @@ using namespace opk;
 
 static_assert(DECIDE_INSTANCE_WORDS == OP_DECISIONS_INSTANCE_WORDS, "the public header and opk_decide.hip.h disagree on an instance's words");
 
-void launch_planned_fragment_means(hipStream_t st, const op_assemble_request& rows, const op_planned_means_request& req) {
+static PlannedMeansParams planned_means_params(const op_assemble_request& rows, const op_planned_means_request& req) {
   PlannedMeansParams p = {};
   p.keep_prob = req.keep_prob_dev, p.frag_off = rows.frag_off_dev, p.frag_shift = req.frag_shift_dev, p.q_off = rows.q_off_dev;
   p.plan = rows.plan_dev, p.cu = rows.cu_seqlens_dev, p.slot_off = req.slot_off_dev;
@@ -15,7 +16,20 @@ void launch_planned_fragment_means(hipStream_t st, const op_assemble_request& ro
   p.n_frag = rows.n_frag, p.n_queries = rows.n_queries, p.n_query_tokens = rows.q_off_host[rows.n_queries];
   p.n_rows = rows.n_rows, p.total = rows.total_tokens, p.n_slots = req.n_slots;
   p.n_prefix = rows.n_prefix, p.n_middle = rows.n_middle;
+  return p;
+}
+
+void launch_planned_fragment_means(hipStream_t st, const op_assemble_request& rows, const op_planned_means_request& req) {
+  const PlannedMeansParams p = planned_means_params(rows, req);
   hipLaunchKernelGGL(planned_fragment_means_kernel, dim3((unsigned)((rows.n_rows + 3) / 4)), dim3(256), 0, st, p);
+}
+
+void launch_located_fragment_means(hipStream_t st, const op_assemble_request& rows, const op_planned_means_request& req, const int32_t* ids,
+                                   int32_t* ctx_start_out) {
+  LocatedMeansParams p = {};
+  p.planned = planned_means_params(rows, req);
+  p.ids = ids, p.ctx_start_out = ctx_start_out;
+  hipLaunchKernelGGL(located_fragment_means_kernel, dim3((unsigned)((rows.n_rows + 3) / 4)), dim3(256), 0, st, p);
 }
 
 void launch_sentence_decisions(hipStream_t st, const op_decisions_request& req) {

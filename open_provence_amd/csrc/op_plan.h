@@ -459,12 +459,14 @@ inline Layout workspace_layout(int hidden, int inter, int cap_rows_pad, int n_se
   return lay;
 }
 
-// ---- prepared requests: fragment means and sentence decisions (op_planned_fragment_means, op_sentence_decisions) -----------------
-// Both look at the caller's HOST copies only, before anything is enqueued and before the handle is looked at.
+// ---- prepared requests: fragment means and sentence decisions (op_planned_fragment_means, op_located_fragment_means,
+// op_sentence_decisions) ----------------------------------------------------------------------------------------------------------
+// All look at the caller's HOST copies only, before anything is enqueued and before the handle is looked at.
 
 // `rows` is the op_assemble_request of the forward (its plan, offsets and cu_seqlens; the ids it names are not needed here).
-inline Refusal check_planned_means(const op_assemble_request* rows, const op_planned_means_request* req) {
-  const char* const fn = "op_planned_fragment_means";
+// (`fn`: the call the refusal's text names -- op_located_fragment_means makes the same checks)
+inline Refusal check_planned_means(const op_assemble_request* rows, const op_planned_means_request* req,
+                                   const char* fn = "op_planned_fragment_means") {
   if (!rows || !req) return refuse(OP_ERR_INVALID, "%s: %s is NULL", fn, !rows ? "rows" : "request");
   if (rows->struct_bytes != sizeof(op_assemble_request))
     return refuse(OP_ERR_INVALID, "%s: op_assemble_request.struct_bytes is %u, expected %zu", fn, rows->struct_bytes, sizeof(op_assemble_request));
@@ -511,6 +513,18 @@ inline Refusal check_planned_means(const op_assemble_request* rows, const op_pla
   if (rows->total_tokens > 0 && !req->keep_prob_dev) return refuse(OP_ERR_INVALID, "%s: keep_prob_dev is NULL", fn);
   if (slot > (int64_t)req->slot_off_host[0] && (!req->mean_out_dev || !req->slot_frag_out_dev))
     return refuse(OP_ERR_INVALID, "%s: mean_out_dev or slot_frag_out_dev is NULL", fn);
+  return Refusal{};
+}
+
+// op_located_fragment_means: everything check_planned_means checks, and the two buffers of the lookup -- the rows' ids
+// (op_assemble_rows' output for the same `rows`) and one ctx_start per row -- while there are rows.
+inline Refusal check_located_means(const op_assemble_request* rows, const op_planned_means_request* req, const int32_t* ids_dev,
+                                   const int32_t* ctx_start_out_dev) {
+  const char* const fn = "op_located_fragment_means";
+  const Refusal planned = check_planned_means(rows, req, fn);
+  if (planned.code != OP_OK) return planned;
+  if (rows->n_rows > 0 && !ctx_start_out_dev) return refuse(OP_ERR_INVALID, "%s: ctx_start_out_dev is NULL", fn);
+  if (rows->n_rows > 0 && !ids_dev) return refuse(OP_ERR_INVALID, "%s: ids_dev is NULL", fn);
   return Refusal{};
 }
 

@@ -1,9 +1,12 @@
 // opk_decide.hip.h -- the last host stages of a prepared request on the device: op_planned_fragment_means (the mean
 // keep-probability of every fragment of every row, its token range derived from the row plan op_assemble_rows laid the row out
-// from) and op_sentence_decisions (per context: the sentences' averages over their fragments, the threshold, the title rule).
+// from), op_located_fragment_means (the same with the context looked up in the assembled row first, as the reference looks it
+// up: at most head_len x n_ctx id compares per row) and op_sentence_decisions (per context: the sentences' averages over their
+// fragments, the threshold, the title rule).
 // Tiny next to a forward: plain C++, vector stores only, no LDS, no atomics.  Every index the kernels read from device memory
 // -- the row plan, the offsets, the slot table, the instance table -- is held inside the buffers' sizes before it addresses
 // anything, as in opk_assemble.hip.h: a load lands inside its source buffer, a store inside the output, whatever the tables hold.
+// Every loop is bounded by a length from the plan, clamped; nothing waits on memory another thread writes.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -63,6 +66,104 @@ __global__ __launch_bounds__(256) void planned_fragment_means_kernel(PlannedMean
     const long long len = j == 0 ? first_len : f1 - f0;
     // (fragments are consecutive in the corpus: those before fragment j hold first_len + frag_off[f] - frag_off[first + 1] ids)
     long long start = head_len + (j == 0 ? 0 : first_len + (f0 - first_end));
+    long long end = start + len;
+    const long long shift = p.frag_shift[f];
+    start -= shift;
+    end -= shift;
+    if (start < 0) start = 0;
+    if (end > (long long)row_len) end = row_len;
+    float value = 1.0f;
+    if (end > start) {
+      const int count = (int)(end - start);
+      const float sum = np_pairwise_sum_f32(p.keep_prob + (size_t)lo + (size_t)start, count);
+      value = (float)((double)sum / (double)count);
+    }
+    p.mean_out[slot] = value;
+    p.slot_frag_out[slot] = f;
+  }
+}
+
+struct LocatedMeansParams {  // by value in the kernel's arguments
+  PlannedMeansParams planned;
+  const int32_t* ids;     // [total]: the rows op_assemble_rows laid out from the same plan
+  int32_t* ctx_start_out; // [n_rows]
+};
+
+// op_located_fragment_means: planned_fragment_means_kernel with the context LOOKED UP in the row, as the reference does
+// (pipeline.prepare_block_inputs: _find_subsequence(ids, ctx)) -- the first place at or left of head_len = prefix + query + middle
+// where the row's whole context (n_ctx ids: the row's fragments end to end, the first one `clip` long when clip > 0, held to
+// row_len - head_len) occurs.  It is left of head_len when the context also occurs in prefix + query + middle, or in those
+// followed by the start of its own copy; head_len itself always matches.  A wave per row.  The search: lane-per-candidate over
+// idx = 0 .. head_len - 1 in ascending passes of 64; a lane whose first id matches compares on until a mismatch; a ballot picks
+// the lowest matching lane of the pass, and the first pass with a match ends the search (the branch is uniform across the wave:
+// it tests the ballot).  Work per row: at most head_len x n_ctx compares.  Every read is ids[lo + k] with k < head_len + n_ctx <=
+// row_len, inside the row's own [cu[row], cu[row + 1]) within [0, total).  ctx_start_out[row] = the place found; a row the
+// plain kernel skips, or one without context ids, gets head_len (0 ids for a query that is not the request's) and no slots.
+// The fragments' ranges, shift, clamp and mean are then the plain kernel's with head_len replaced by the place found.
+__global__ __launch_bounds__(256) void located_fragment_means_kernel(LocatedMeansParams lp) {
+  const PlannedMeansParams& p = lp.planned;
+  const int lane = (int)(threadIdx.x & 63);
+  const long long wave = (long long)blockIdx.x * 4 + (long long)(threadIdx.x >> 6);
+  if (wave >= (long long)p.n_rows) return;
+  const int row = (int)wave;
+  int lo = p.cu[row], hi = p.cu[row + 1];
+  if (lo < 0) lo = 0;
+  if (hi > p.total) hi = p.total;
+  const int row_len = hi > lo ? hi - lo : 0;
+  const int32_t* pr = p.plan + (size_t)row * DECIDE_PLAN_WORDS;
+  const int query = pr[0], first = pr[1], n = pr[2], clip = pr[3];
+  int q_len = 0;
+  if (query >= 0 && query < p.n_queries) {
+    int q0 = p.q_off[query], q1 = p.q_off[query + 1];
+    if (q0 < 0) q0 = 0;
+    if (q1 > p.n_query_tokens) q1 = p.n_query_tokens;
+    q_len = q1 > q0 ? q1 - q0 : 0;
+  }
+  const long long head_sum = (long long)p.n_prefix + q_len + p.n_middle;
+  const int head_len = head_sum < (long long)INT32_MAX ? (int)head_sum : INT32_MAX;
+  const bool planned = query >= 0 && query < p.n_queries && first >= 0 && n > 0 && first <= p.n_frag - n;
+  long long first_off = 0, first_end = 0, first_len = 0;
+  int n_ctx = 0;
+  if (planned) {
+    first_off = p.frag_off[first], first_end = p.frag_off[first + 1];
+    first_len = clip > 0 ? (long long)clip : first_end - first_off;
+    long long ctx = first_len + ((long long)p.frag_off[first + n] - first_end);
+    if (ctx > (long long)row_len - head_len) ctx = (long long)row_len - head_len;
+    n_ctx = ctx > 0 ? (int)ctx : 0;
+  }
+  int found = head_len;
+  if (n_ctx > 0) {
+    const int32_t* rid = lp.ids + (size_t)lo;
+    const int32_t* ctx = rid + head_len;  // (head_len + n_ctx <= row_len)
+    const int32_t ctx0 = ctx[0];
+    for (int base = 0; base < head_len; base += 64) {
+      const int idx = base + lane;
+      bool match = idx < head_len && rid[idx] == ctx0;
+      if (match) {
+        for (int j = 1; j < n_ctx; ++j) {  // (idx + j < head_len + n_ctx)
+          if (rid[idx + j] != ctx[j]) {
+            match = false;
+            break;
+          }
+        }
+      }
+      const unsigned long long hits = __ballot(match);
+      if (hits != 0ull) {
+        found = base + __builtin_ctzll(hits);
+        break;
+      }
+    }
+  }
+  if (lane == 0) lp.ctx_start_out[row] = found;
+  if (n_ctx <= 0) return;
+  const long long slot0 = p.slot_off[row];
+  for (int j = lane; j < n; j += 64) {
+    const long long slot = slot0 + j;
+    if (slot < 0 || slot >= (long long)p.n_slots) continue;
+    const int f = first + j;
+    const long long f0 = p.frag_off[f], f1 = p.frag_off[f + 1];
+    const long long len = j == 0 ? first_len : f1 - f0;
+    long long start = (long long)found + (j == 0 ? 0 : first_len + (f0 - first_end));
     long long end = start + len;
     const long long shift = p.frag_shift[f];
     start -= shift;

@@ -725,8 +725,48 @@ class HipEncoder:
 
         if not hasattr(self.lib, "op_planned_fragment_means"):
             raise _lib.HipLibraryError("this library has no op_planned_fragment_means")
-        rows, _pieces, total = self._assemble_request(None, frag_off, frag_off_host, None, q_off, q_off_host, template, plan, plan_host,
-                                                      cu_seqlens, cu_seqlens_host)
+        rows, _pieces, req = self._planned_means_request(frag_off, frag_off_host, q_off, q_off_host, template, plan, plan_host, cu_seqlens,
+                                                         cu_seqlens_host, keep_prob, frag_shift, slot_off, slot_off_host, mean_out, slot_frag_out)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_planned_fragment_means(self._handle, ctypes.byref(rows), ctypes.byref(req), ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_planned_fragment_means")
+
+    def located_fragment_means(self, frag_off: torch.Tensor, frag_off_host: np.ndarray, q_off: torch.Tensor, q_off_host: np.ndarray,
+                               template: "Sequence[Sequence[int]]", plan: torch.Tensor, plan_host: np.ndarray, cu_seqlens: torch.Tensor,
+                               cu_seqlens_host: np.ndarray, keep_prob: torch.Tensor, frag_shift: torch.Tensor, slot_off: torch.Tensor,
+                               slot_off_host: np.ndarray, mean_out: torch.Tensor, slot_frag_out: torch.Tensor, ids: torch.Tensor,
+                               ctx_start_out: torch.Tensor) -> None:
+        """``op_located_fragment_means``: :meth:`planned_fragment_means` (same arguments) with every row's context looked up in
+        the row first, as the reference looks it up: ``ids`` (int32, at least the rows' tokens) is what :meth:`assemble_rows`
+        laid out from the same ``plan``; ``ctx_start_out`` (int32 ``[n_rows]``) receives, per row, the first place at or left
+        of ``len(prefix) + len(query) + len(middle)`` where the row's whole context occurs, and the fragments' ranges start
+        there.  Asynchronous on the current stream."""
+
+        if not hasattr(self.lib, "op_located_fragment_means"):
+            raise _lib.HipLibraryError("this library has no op_located_fragment_means")
+        rows, _pieces, req = self._planned_means_request(frag_off, frag_off_host, q_off, q_off_host, template, plan, plan_host, cu_seqlens,
+                                                         cu_seqlens_host, keep_prob, frag_shift, slot_off, slot_off_host, mean_out, slot_frag_out)
+        for name, tensor in (("ids", ids), ("ctx_start_out", ctx_start_out)):
+            if tensor.dtype != torch.int32 or tensor.device != self.device or not tensor.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous {torch.int32} tensor on {self.device}")
+        if ids.numel() < int(rows.total_tokens) or ctx_start_out.numel() != int(rows.n_rows):
+            raise ValueError("ids / ctx_start_out: sizes do not fit the rows")
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            code = self.lib.op_located_fragment_means(
+                self._handle, ctypes.byref(rows), ctypes.byref(req), ctypes.c_void_p(ids.data_ptr()) if ids.numel() else None,
+                ctypes.c_void_p(ctx_start_out.data_ptr()) if ctx_start_out.numel() else None, ctypes.c_void_p(stream))
+        _lib.check(self.lib, self._handle, code, "op_located_fragment_means")
+
+    def _planned_means_request(self, frag_off, frag_off_host, q_off, q_off_host, template, plan, plan_host, cu_seqlens, cu_seqlens_host,
+                               keep_prob, frag_shift, slot_off, slot_off_host, mean_out,
+                               slot_frag_out) -> "tuple[_lib.OpAssembleRequest, list[np.ndarray], _lib.OpPlannedMeansRequest]":
+        """The two requests of :meth:`planned_fragment_means` and :meth:`located_fragment_means` from their shared arguments,
+        dtypes, devices and sizes checked -> (rows, the template pieces it points into, the means request)."""
+
+        rows, pieces, total = self._assemble_request(None, frag_off, frag_off_host, None, q_off, q_off_host, template, plan, plan_host,
+                                                     cu_seqlens, cu_seqlens_host)
         n_rows = int(rows.n_rows)
         for name, tensor, dtype in (("keep_prob", keep_prob, torch.float32), ("frag_shift", frag_shift, torch.int32), ("slot_off", slot_off, torch.int32),
                                     ("mean_out", mean_out, torch.float32), ("slot_frag_out", slot_frag_out, torch.int32)):
@@ -745,10 +785,7 @@ class HipEncoder:
         req.slot_off_dev, req.slot_off_host = slot_off.data_ptr(), slot_off_host.ctypes.data
         req.mean_out_dev = mean_out.data_ptr() if mean_out.numel() else None
         req.slot_frag_out_dev = slot_frag_out.data_ptr() if slot_frag_out.numel() else None
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            code = self.lib.op_planned_fragment_means(self._handle, ctypes.byref(rows), ctypes.byref(req), ctypes.c_void_p(stream))
-        _lib.check(self.lib, self._handle, code, "op_planned_fragment_means")
+        return rows, pieces, req
 
     def sentence_decisions(self, instances: torch.Tensor, instances_host: np.ndarray, means: torch.Tensor, slot_frag: torch.Tensor,
                            frag_sent: torch.Tensor, threshold: float, avg_out: "torch.Tensor | None" = None,

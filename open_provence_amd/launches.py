@@ -233,7 +233,9 @@ def enqueue_packed(model, ids_np: np.ndarray | None, cu_np: np.ndarray, max_len:
     _, rank_dev = model.encoder.forward_packed(ids_dev, cu_dev, cu_np, max_len, keep_prob=keep_dev, ids_host=ids_np)
     count_forward(model, n_rows, total)
     if planned is not None:
-        means_dev = model._planned_means_on_device(planned, cu_dev, cu_np, keep_dev)
+        # (ids_dev: the rows this launch assembled or, the range guard's repeat, the first launch's -- what a located request,
+        # ``means["locate"]``, looks its contexts up in)
+        means_dev = model._planned_means_on_device(planned, cu_dev, cu_np, keep_dev, ids_dev)
         pool["keep"][:n_seg].copy_(means_dev, non_blocking=True)
     elif seg_counts is not None:
         means_dev = model.encoder.segment_means(keep_dev, seg_dev)

@@ -1553,16 +1553,23 @@ class OpenProvenceModel:
         return self.encoder.assemble_rows(corpus["ids"], corpus["frag_off"], corpus["frag_off_np"], queries["ids"], queries["off"],
                                           queries["off_np"], corpus["pieces"], plan_dev, plan_np, cu_dev, cu_np)
 
-    def _planned_means_on_device(self, planned: dict[str, Any], cu_dev, cu_np, keep_dev) -> torch.Tensor:
+    def _planned_means_on_device(self, planned: dict[str, Any], cu_dev, cu_np, keep_dev, ids_dev=None) -> torch.Tensor:
         """The fragment means of one forward of a prepared request, from its plan (``planned``: the forward's ``assemble``
-        with ``plan_dev``) -> the forward's slice of the request's means buffer (``means["values"]``)."""
+        with ``plan_dev``) -> the forward's slice of the request's means buffer (``means["values"]``).  With
+        ``means["locate"]`` every context is looked up in its row first (``ids_dev``: the launch's assembled rows;
+        ``op_located_fragment_means``), its place landing in the forward's slice of ``means["ctx_start"]``."""
 
         corpus, queries, means = planned["corpus"], planned["queries"], planned["means"]
         first, last = means["rows"]
-        self.encoder.planned_fragment_means(
-            corpus["frag_off"], corpus["frag_off_np"], queries["off"], queries["off_np"], corpus["pieces"], planned["plan_dev"], planned["plan"],
-            cu_dev, cu_np, keep_dev, corpus["frag_shift"], means["slot_off"][first: last + 1], means["slot_off_np"][first: last + 1],
-            means["values"], means["slot_frag"])
+        shared = (corpus["frag_off"], corpus["frag_off_np"], queries["off"], queries["off_np"], corpus["pieces"], planned["plan_dev"], planned["plan"],
+                  cu_dev, cu_np, keep_dev, corpus["frag_shift"], means["slot_off"][first: last + 1], means["slot_off_np"][first: last + 1],
+                  means["values"], means["slot_frag"])
+        if means.get("locate"):
+            if ids_dev is None:
+                raise RuntimeError("a located launch without its assembled rows")
+            self.encoder.located_fragment_means(*shared, ids_dev, means["ctx_start"][first:last])
+        else:
+            self.encoder.planned_fragment_means(*shared)
         slot_off = means["slot_off_np"]
         return means["values"][int(slot_off[first]): int(slot_off[last])]
 

@@ -313,11 +313,15 @@ def _plan_prepared_forward(model, layout: _RowLayout, rows: list[tuple], lengths
 
 # -- prepared requests whose fragment means and sentence decisions are taken on the device ---------------------------------------
 # OPEN_PROVENCE_PREPARED_DECISIONS, read at call time: "0" keeps the host stages (_plan_prepared_forward, score_fragments,
-# postprocess_contexts) for every prepared request; anything else lets an eligible request take the device path.  Unset = "0":
-# on the request the switch was to be judged by (scripts/process_e2e.py --prepared with its own question, whose letters begin
-# nearly every context under the char tokenizer) no request is eligible and the wall time does not fall; where requests are
-# eligible it falls by 16-23 % (profiles/prepared_decisions.txt).
-PREPARED_DECISIONS_DEFAULT = "0"
+# postprocess_contexts) for every prepared request; anything else lets an eligible request take the device path.  Under "1" a
+# request is not eligible when a block begins with a token id of its question -- nearly every request of scripts/process_e2e.py
+# --prepared with its own question under the char tokenizer (profiles/prepared_decisions.txt).  "2": as "1", and the device
+# looks every context up in its assembled row as the host path does (op_located_fragment_means), so such a request runs on the
+# device too; on a library without that call "2" is "1".  Unset = "2": on the request the switch was to be judged by (that
+# script with its own question, parent commit and this tree in turns) the wall time falls from 13.9 to 9.2, 43.4 to 35.0 and 162
+# to 133-139 ms at 256 / 1024 / 4096 contexts, more than the parent's spread at every size (profiles/prepared_lookup.txt,
+# DESIGN.md section 7).
+PREPARED_DECISIONS_DEFAULT = "2"
 
 
 @dataclass
@@ -344,6 +348,15 @@ def prepared_decisions_on_device(model, corpus) -> bool:
     return (os.getenv("OPEN_PROVENCE_PREPARED_DECISIONS", PREPARED_DECISIONS_DEFAULT) != "0"
             and hasattr(lib, "op_planned_fragment_means") and hasattr(lib, "op_sentence_decisions")
             and corpus.decision_tables() is not None)
+
+
+def prepared_contexts_located(model) -> bool:
+    """``OPEN_PROVENCE_PREPARED_DECISIONS=2`` on a library with ``op_located_fragment_means``: the device looks every context up
+    in its row, so a context that begins with an id of its question no longer sends the request to the host stages.  Without
+    the symbol "2" behaves as "1"."""
+
+    return (os.getenv("OPEN_PROVENCE_PREPARED_DECISIONS", PREPARED_DECISIONS_DEFAULT) == "2"
+            and hasattr(model.encoder.lib, "op_located_fragment_means"))
 
 
 def _plan_decided(model, views: Sequence[PreparedView], q_lens: list[int], sep_len: int, n_fixed: int):
@@ -389,7 +402,8 @@ def _plan_decided(model, views: Sequence[PreparedView], q_lens: list[int], sep_l
 def _run_decided(model, request: Request, run: Run, batch_size: int, query_token_ids: list[list[int]], t_asm: float) -> bool:
     """The device path of :func:`run_prepared_request`; False (nothing enqueued, ``run`` untouched) when a row of the request
     rules it out: a row without fragments or context tokens, or a first fragment that begins with an id of its query's
-    ``heads`` (its place in the row then does not follow from lengths alone)."""
+    ``heads`` (its place in the row then does not follow from lengths alone) -- the last one unless the device looks the
+    contexts up itself (:func:`prepared_contexts_located`)."""
 
     views = request.views
     corpus = views[0].corpus
@@ -407,10 +421,13 @@ def _run_decided(model, request: Request, run: Run, batch_size: int, query_token
     first_ids = tables["frag_first_id"][plan_np[:, 1]]
     if (first_ids < 0).any():  # (a block that begins with a fragment without tokens)
         return False
-    for q_idx, query in enumerate(query_token_ids):
-        heads = np.fromiter(set(template.prefix) | set(query) | set(template.middle), dtype=np.int64)
-        if heads.size and np.isin(first_ids[q_of_row == q_idx], heads).any():
-            return False
+    # "2": every forward looks its contexts up in the rows it assembled (op_located_fragment_means), as the host path does
+    located = prepared_contexts_located(model)
+    if not located:
+        for q_idx, query in enumerate(query_token_ids):
+            heads = np.fromiter(set(template.prefix) | set(query) | set(template.middle), dtype=np.int64)
+            if heads.size and np.isin(first_ids[q_of_row == q_idx], heads).any():
+                return False
 
     run.blocks += n_rows
     spans = pl.plan_forward_chunks(lengths.tolist(), batch_size, model.forward_token_budget)
@@ -421,6 +438,8 @@ def _run_decided(model, request: Request, run: Run, batch_size: int, query_token
     n_slots = int(slot_off_np[-1])
     means = {"values": torch.empty(n_slots, dtype=torch.float32, device=dev), "slot_frag": torch.empty(n_slots, dtype=torch.int32, device=dev),
              "slot_off": torch.from_numpy(slot_off_np).to(dev), "slot_off_np": slot_off_np}
+    if located:  # (per row, where its context was found: written by the kernel, read by nobody on the host)
+        means.update(locate=True, ctx_start=torch.empty(n_rows, dtype=torch.int32, device=dev))
     assemble = {"corpus": corpus_dev, "queries": _upload_queries(model, query_token_ids, q_lens)}
     counts = plan_np[:, 2].tolist()
     decided = Decided(tables, corpus_dev, items, instance_of, instance_item, instance_rows, instance_slots, means,
@@ -507,7 +526,8 @@ def run_prepared_request(model, request: Request, run: Run, batch_size: int) -> 
     # An eligible corpus (prepared.decision_tables) on a library with op_planned_fragment_means / op_sentence_decisions: the
     # fragments' ranges and means follow on the device from the plan of op_assemble_rows, the sentence decisions from the means
     # (postprocess_decided_request) -- the host keeps four plan words and a length per row.  A request it does not fit (a row
-    # without context tokens, a context that begins with a token of its query or of the template) goes on below, as before.
+    # without context tokens; under "1", a context that begins with a token of its query or of the template) goes on below, as
+    # before.  Under "2" (the default) the device looks the contexts up itself: op_located_fragment_means.
     run.prepared_decisions = "host"
     if on_device and prepared_decisions_on_device(model, corpus) and _run_decided(model, request, run, batch_size, query_token_ids, t_asm):
         run.prepared_decisions = "device"

@@ -107,9 +107,10 @@ def main():
                     help="prepare the contexts once, outside the timed region (OpenProvenceModel.prepare_contexts), and time requests on the "
                     "prepared object; in-process only.  The line gains the one-off preparation time and the forwards of a request")
     ap.add_argument("--question", default=None,
-                    help="the question, instead of the lower-case default.  With the char tokenizer every context begins with a letter of the "
-                    "default question, which keeps a prepared request on the host stages (INTEGRATION.md section 6, "
-                    "OPEN_PROVENCE_PREPARED_DECISIONS); an upper-case question shares no token id with the contexts")
+                    help="the question, instead of the lower-case default.  With the char tokenizer nearly every context begins with a letter "
+                    "of the default question: under OPEN_PROVENCE_PREPARED_DECISIONS=1 that keeps a prepared request on the host stages, "
+                    "under =2 the device looks the contexts up in their rows and the request runs there (INTEGRATION.md section 6); an "
+                    "upper-case question shares no token id with the contexts and is eligible under either value")
     args = ap.parse_args()
     if args.prepared and (args.front_end or args.host_front_end):
         raise SystemExit("--prepared runs in this process: prepared contexts take no front-end")
