@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import hashlib
 import os
+import re
 import shutil
 import subprocess
 from concurrent.futures import ThreadPoolExecutor
@@ -20,46 +21,58 @@ INCLUDE = PKG_DIR.parent / "include" / "open_provence_hip.h"
 BUILD_DIR = PKG_DIR.parent / "build" / "hip"
 OUTPUT = PKG_DIR / "libopenprovence_hip.so"
 
-_COMMON = [CSRC / "opk_common.hip.h"]
-# opk_rowgemm.hip.h = parameters / pack kernels + stream helpers + the kernel, whose body is cut by phase into .inc files
-_ROWGEMM = [CSRC / name for name in ("opk_rowgemm.hip.h", "opk_rowgemm_pack.hip.h", "opk_rowgemm_stream.hip.h", "opk_rowgemm_ln.hip.h", "opk_kstream.hip.h",
-                                     "opk_rowgemm_phase1.hip.h", "opk_rowgemm_mlp.hip.h", "opk_rowgemm_mlp_ops.inc", "opk_rowgemm_mlp_loop.inc",
-                                     "opk_rowgemm_qkv_pairs.hip.h", "opk_rowgemm_chunks.hip.h")]
-_INTERNAL = _COMMON + [INCLUDE, CSRC / "op_internal.h", CSRC / "op_policy.h", CSRC / "opk_f32.hip.h", CSRC / "opk_attn.hip.h", CSRC / "opk_attn_probs.hip.h", CSRC / "opk_panel.hip.h", CSRC / "opk_layer32.hip.h", CSRC / "opk_layer16p.hip.h", CSRC / "opk_layer16p_body.inc"] + _ROWGEMM
+_INCLUDE = re.compile(r'^[ \t]*#[ \t]*include[ \t]+"([^"]+)"', re.MULTILINE)
 
-_PADDED = CSRC / "opk_padded.hip.h"  # the padded [B, L] boundary: pack / unpack on the device
-_AUDIT = CSRC / "opk_audit.hip.h"  # the running audit: coverage bitmap, row gather, logit comparison
-_LOSS = CSRC / "opk_loss.hip.h"  # the evaluation losses: fp64 terms, fixed-order reduction
-_POOL = CSRC / "opk_pool.hip.h"  # pooled hidden states: the reduction of the scratch entry, fixed-order fp64 mean
-_ASSEMBLE = CSRC / "opk_assemble.hip.h"  # prepared contexts: rows laid out on the device from a resident corpus
-_PAIRWISE = CSRC / "opk_pairwise.hip.h"  # numpy's pairwise sums, float32 and float64
-_DECIDE = CSRC / "opk_decide.hip.h"  # prepared requests: fragment means from the row plan, sentence decisions
 
-# (object name, source, extra defines, headers it depends on)
+def scan_includes(src: Path) -> list[Path]:
+    """Every file ``src`` reaches through quoted ``#include "..."`` lines, transitively (headers, ``.inc`` bodies and the C
+    header alike), each name resolved against the including file's directory.  A name that resolves to no file is listed too."""
+
+    found: set[Path] = set()
+    todo = [src]
+    while todo:
+        path = todo.pop()
+        for name in _INCLUDE.findall(path.read_text()):
+            inc = Path(os.path.normpath(path.parent / name))
+            if inc not in found:
+                found.add(inc)
+                if inc.is_file():
+                    todo.append(inc)
+    return sorted(found)
+
+
+# (object name, source, extra defines); what an object depends on beside its source is scanned from the source (scan_includes)
 UNITS = [
-    ("op_api", CSRC / "op_api.hip", [], _INTERNAL + [CSRC / "op_plan.h", CSRC / "op_kernel_sets.h", CSRC / "op_sets.h", CSRC / "opk_small.hip.h",
-                                                      CSRC / "opk_tiled.hip.h", _PADDED, _LOSS, _POOL, _PAIRWISE]),
-    ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"], _INTERNAL),
-    ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"], _INTERNAL),
-    ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"], _INTERNAL),
-    ("op_launch_row3", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=3"], _INTERNAL),
-    ("op_launch_row4", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=4"], _INTERNAL),
-    ("op_launch_row5", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=5"], _INTERNAL),
-    ("op_launch_row6", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=6"], _INTERNAL),
-    ("op_launch_layer32", CSRC / "op_launch_layer32.hip", [], _INTERNAL),
-    ("op_launch_attn", CSRC / "op_launch_attn.hip", [], _INTERNAL),
-    ("op_launch_panel", CSRC / "op_launch_panel.hip", [], _INTERNAL),
-    ("op_launch_padded", CSRC / "op_launch_padded.hip", [], _INTERNAL + [_PADDED]),
-    ("op_launch_audit", CSRC / "op_launch_audit.hip", [], _INTERNAL + [_AUDIT]),
-    ("op_launch_f32", CSRC / "op_launch_f32.hip", [], _INTERNAL),
-    ("op_launch_attn_probs", CSRC / "op_launch_attn_probs.hip", [], _INTERNAL),
-    ("op_launch_probe", CSRC / "op_launch_probe.hip", [], _INTERNAL + [CSRC / "opk_probe.hip.h"]),
-    ("op_launch_loss", CSRC / "op_launch_loss.hip", [], [_LOSS]),
-    ("op_launch_assemble", CSRC / "op_launch_assemble.hip", [], _INTERNAL + [_ASSEMBLE]),
-    ("op_launch_decide", CSRC / "op_launch_decide.hip", [], _INTERNAL + [_DECIDE, _PAIRWISE]),
+    # the C ABI, cut by concern; op_handle.h is what they share
+    ("op_api", CSRC / "op_api.hip", []),
+    ("op_weights", CSRC / "op_weights.hip", []),
+    ("op_select", CSRC / "op_select.hip", []),
+    ("op_forward", CSRC / "op_forward.hip", []),
+    ("op_forward_layers", CSRC / "op_forward_layers.hip", []),
+    ("op_attention_side", CSRC / "op_attention_side.hip", []),
+    ("op_services", CSRC / "op_services.hip", []),
+    # one launch unit per kernel family
+    ("op_launch_row0", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=0"]),
+    ("op_launch_row1", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=1"]),
+    ("op_launch_row2", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=2"]),
+    ("op_launch_row3", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=3"]),
+    ("op_launch_row4", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=4"]),
+    ("op_launch_row5", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=5"]),
+    ("op_launch_row6", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=6"]),
+    ("op_launch_layer32", CSRC / "op_launch_layer32.hip", []),
+    ("op_launch_attn", CSRC / "op_launch_attn.hip", []),
+    ("op_launch_panel", CSRC / "op_launch_panel.hip", []),
+    ("op_launch_padded", CSRC / "op_launch_padded.hip", []),
+    ("op_launch_audit", CSRC / "op_launch_audit.hip", []),
+    ("op_launch_f32", CSRC / "op_launch_f32.hip", []),
+    ("op_launch_attn_probs", CSRC / "op_launch_attn_probs.hip", []),
+    ("op_launch_probe", CSRC / "op_launch_probe.hip", []),
+    ("op_launch_loss", CSRC / "op_launch_loss.hip", []),
+    ("op_launch_assemble", CSRC / "op_launch_assemble.hip", []),
+    ("op_launch_decide", CSRC / "op_launch_decide.hip", []),
 ]
 SOURCES = sorted({u[1] for u in UNITS})
-HEADERS = sorted({h for u in UNITS for h in u[3]})
+HEADERS = sorted({h for src in SOURCES for h in scan_includes(src)})
 
 FLAGS = [
     "--offload-arch=gfx950",
@@ -81,9 +94,9 @@ def _hipcc() -> str:
 
 
 def _unit_digest(unit) -> str:
-    _, src, defines, headers = unit
+    _, src, defines = unit
     digest = hashlib.sha256(" ".join(FLAGS + defines).encode())
-    for path in [src, *headers]:
+    for path in [src, *scan_includes(src)]:
         digest.update(path.read_bytes())
     return digest.hexdigest()
 
@@ -110,7 +123,7 @@ def build(force: bool = False, verbose: bool = False) -> Path:
     BUILD_DIR.mkdir(parents=True, exist_ok=True)
 
     def compile_unit(unit) -> None:
-        name, src, defines, _ = unit
+        name, src, defines = unit
         obj = BUILD_DIR / f"{name}.o"
         cmd = [hipcc, *FLAGS, *defines, "-c", str(src), "-o", str(obj)]
         if verbose:

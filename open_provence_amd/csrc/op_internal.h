@@ -1,4 +1,4 @@
-// op_internal.h -- host-side declarations shared by op_api.hip and the kernel-launch translation units
+// op_internal.h -- host-side declarations shared by the units of the C ABI (op_handle.h) and the kernel-launch translation units
 // (op_launch_*.hip).  The library is built from several translation units so that the large kernel templates
 // compile in parallel; each launch unit instantiates one kernel family for every curated precision policy.
 #pragma once

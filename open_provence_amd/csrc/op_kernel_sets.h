@@ -1,6 +1,6 @@
 // op_kernel_sets.h -- kKernelSets: what each OP_KS_* kernel set is: the kernels it runs, the operand format of each part of a
 // layer, the terms it evaluates, what it needs from a handle and what it costs.  THE place a set is defined.  Host-only and
-// free of HIP: op_plan.h decides on it, op_api.hip launches by it.
+// free of HIP: op_plan.h decides on it, op_forward.hip launches by it.
 #pragma once
 
 #include "../../include/open_provence_hip.h"

@@ -22,7 +22,7 @@ namespace opp {
 using opl::Policy;
 using namespace ops;
 
-constexpr int ROW_ALIGN = 32;  // = opk::ROW_ALIGN (op_api.hip holds the two together)
+constexpr int ROW_ALIGN = 32;  // = opk::ROW_ALIGN (op_handle.h holds the two together)
 
 inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 inline size_t align_up_sz(size_t v, size_t a) { return (v + a - 1) / a * a; }

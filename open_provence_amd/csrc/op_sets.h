@@ -1,4 +1,5 @@
-// op_sets.h -- the host-only table of the GEMM weight packs (op_api.hip allocates, builds and reads them):
+// op_sets.h -- the host-only table of the GEMM weight packs (op_api.hip allocates them, op_weights.hip builds them, the
+// forward's units read them):
 // kWeights / kPackElems / pack_exists, the packed forms of the four GEMM weights of a layer:
 // Weight x PackFmt.  Its rows name the kernels' pack modes, so it includes the kernel headers; the kernel sets
 // (op_kernel_sets.h) do not.

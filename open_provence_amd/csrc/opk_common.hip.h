@@ -271,7 +271,7 @@ __device__ __forceinline__ u16 f2h(float v) { return __builtin_bit_cast(u16, (_F
 // SQUARED differences of the weights below 2^-14 that miss fp16's subnormal grid (spacing 2^-24): neither plane can hold
 // that difference (it is below e4m3's reach even shifted), so a tensor made of such weights -- e.g. an output projection
 // scaled down by 2^-10 -- would be multiplied at fp16 single-pass accuracy (measured 2e-3 .. 4e-3 on logits), while the
-// handful of tiny weights of a normally scaled tensor are harmless.  f16_fit_close_tensor_kernel (opk_small.hip.h)
+// handful of tiny weights of a normally scaled tensor are harmless.  f16_fit_close_tensor_kernel (opk_load.hip.h)
 // compares fit[0] with the tensor's energy fit[1] (weight_energy_kernel) and raises flags[2] when the lost part exceeds
 // 2^-36 of it (the format's own relative error is ~2^-16, i.e. 2^-32 in energy); the library then keeps the (hi, lo)
 // bf16 sets for the model.

@@ -66,7 +66,7 @@ __device__ __forceinline__ f32x4 mfma_f32(float x, float y, f32x4 c) { return __
 __device__ __forceinline__ float gelu_erf_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 
 // ----------------------------------------------------------------------------------------------
-// y = (x - mean) / sqrt(var + eps) * w into an fp32 plane: one wave per row (the arithmetic of ln_kernel, opk_small.hip.h)
+// y = (x - mean) / sqrt(var + eps) * w into an fp32 plane: one wave per row (the arithmetic of ln_kernel, opk_layernorm.hip.h)
 // ----------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void ln_f32_kernel(const float* __restrict__ x, const float* __restrict__ lnw, float eps, int H,
                                                      int r_pad, float* __restrict__ out) {

@@ -18,7 +18,7 @@ namespace opk {
 // 1 KiB load straight into registers -- no LDS staging, no row-strided 8-byte accesses.
 // ----------------------------------------------------------------------------------------------
 
-#ifdef OPK_PACK_KERNELS  // weight re-packing runs in op_api.hip only
+#ifdef OPK_PACK_KERNELS  // weight re-packing runs in op_weights.hip only
 // dst[ks][plane][nf][g][i][e] <- W[nf*16 + i][ks*32 + g*8 + e]   (W is [N][K]; chunk = one k-step of all N)
 __global__ void pack_kstream_kernel(const float* __restrict__ src, int N, int K, int permute, u16* __restrict__ dst,
                                     int zero_lo, int* __restrict__ any_lo, int f16 = 0) {

@@ -39,7 +39,7 @@ __device__ __forceinline__ int panel_source_row(int mode, int tile, int nf, int 
   return (nf < 8 ? 0 : I) + tile * 128 + 32 * (nn >> 1) + within + 4 * (nn & 1);
 }
 
-#ifdef OPK_PACK_KERNELS  // weight re-packing runs in op_api.hip only
+#ifdef OPK_PACK_KERNELS  // weight re-packing runs in op_weights.hip only
 // dst[tile][ks][plane][nf 0..15][lane = 16 g + i][8] <- W[source_row(tile, nf, i)][ks*32 + g*8 + e]
 // f16 = 1 (kernel set "f16"): hi plane = RNE_fp16(w), lo plane zeros, any_lo untouched
 __global__ void pack_panel_kernel(const float* __restrict__ src, int n_tiles, int K, int mode, int H, int I,

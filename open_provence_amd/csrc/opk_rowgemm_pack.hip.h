@@ -116,7 +116,7 @@ __device__ __forceinline__ int rowgemm_source_row(int mode, int c, int pr, int H
   return c * ROW_CHUNK + pr;
 }
 
-#ifdef OPK_PACK_KERNELS  // weight re-packing runs in op_api.hip only
+#ifdef OPK_PACK_KERNELS  // weight re-packing runs in op_weights.hip only
 // dst[chunk][ks][plane][nf][g][i][e] <- src[source_row(chunk, nf*16+i)][ks*32 + g*8 + e]
 // f16 = 1 (kernel set "f16"): the hi plane holds RNE_fp16(w), the lo plane zeros; any_lo is not touched
 __global__ void pack_rowgemm_kernel(const float* __restrict__ src, int n_rows, int K, int mode, int H, int I,

@@ -12,15 +12,21 @@ ROOT = Path(__file__).resolve().parents[1]
 CSRC = ROOT / "open_provence_amd" / "csrc"
 
 
+def unit_table() -> dict:
+    """The units of the library's build description, by short name: op_api -> api, op_launch_row0 -> row0, ..."""
+
+    sys.path.insert(0, str(ROOT))
+    from open_provence_amd import build_ext
+
+    return {name.removeprefix("op_launch_").removeprefix("op_"): (src.name, defines) for name, src, defines in build_ext.UNITS}
+
+
 def main() -> None:
-    """usage: kernel_resources.py <unit: api|row0|row1|row2|row3|attn|panel|padded> [name filter]"""
+    """usage: kernel_resources.py <unit: api|weights|forward|forward_layers|...|row0|...|attn|panel|padded|...> [name filter]"""
 
     unit = sys.argv[1] if len(sys.argv) > 1 else "attn"
     pattern = sys.argv[2] if len(sys.argv) > 2 else ""
-    src, defines = {"api": ("op_api.hip", []), "attn": ("op_launch_attn.hip", []), "panel": ("op_launch_panel.hip", []),
-                    "padded": ("op_launch_padded.hip", []),
-                    "row0": ("op_launch_row.hip", ["-DOPL_ROW_PART=0"]), "row1": ("op_launch_row.hip", ["-DOPL_ROW_PART=1"]),
-                    "row2": ("op_launch_row.hip", ["-DOPL_ROW_PART=2"]), "row3": ("op_launch_row.hip", ["-DOPL_ROW_PART=3"])}[unit]
+    src, defines = unit_table()[unit]
     cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-slp-vectorize", "-c", *defines,
            "-Rpass-analysis=kernel-resource-usage", "-o", "/tmp/op_resources.o", str(CSRC / src)]
     out = subprocess.run(cmd, capture_output=True, text=True, cwd="/tmp").stderr

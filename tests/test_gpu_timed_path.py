@@ -96,7 +96,7 @@ def test_bench_configuration_matches_the_oracle(weights, kernel_set):
 
 # ---- the panel path (hidden 512 / 768: BASELINE configs 3-5) at the sizes bench.py times it ------------------------------
 # Full depth, default flags, both checkpoint dtypes.  At >= 256 row blocks the XCD-aware block maps of the panel GEMMs
-# (op_api.hip: per_xcd / groups / row_group all follow r_pad / 128), the XCD-grouped attention map and the 256-query
+# (op_forward_layers.hip: per_xcd / groups / row_group all follow r_pad / 128), the XCD-grouped attention map and the 256-query
 # attention blocks take the values they have in the bench -- none of which the 1..7-row-block fixtures reach.  Checked
 # pairs: first / last of the batch and pairs whose 4 row blocks sit at the boundaries of the 8-row-block XCD groups.
 

@@ -90,9 +90,9 @@ def _encoder(model, kernel_set, flag=None, window=128, chunk_rows=None, weights=
 
 # -- the layout hook --------------------------------------------------------------------------------------------------------------
 def _workspace_members() -> list[str]:
-    """The pointer members of ``struct Workspace`` (op_api.hip), read from the source."""
+    """The pointer members of ``struct Workspace`` (op_forward.h), read from the source."""
 
-    text = (Path(__file__).resolve().parents[1] / "open_provence_amd" / "csrc" / "op_api.hip").read_text()
+    text = (Path(__file__).resolve().parents[1] / "open_provence_amd" / "csrc" / "op_forward.h").read_text()
     body = re.search(r"struct Workspace \{(.*?)\n\};", text, flags=re.S).group(1)
     body = re.sub(r"//[^\n]*", "", body)
     names = []

@@ -1,4 +1,4 @@
-"""The RoPE tables the library builds (op_create -> build_rope_host in op_api.hip, reached through op_debug_rope_tables)
+"""The RoPE tables the library builds (op_create -> build_rope_host, both in op_api.hip, reached through op_debug_rope_tables)
 against the reference's recipe in torch fp32 (``oracle.modernbert_oracle.rope_tables``: inv_freq = 1 / theta ** (arange(0, 64,
 2, fp32) / 64), an fp32 power and an fp32 reciprocal; angle = fp32(pos) * inv_freq; cos / sin of that fp32 angle), for both
 thetas of the published checkpoints, head_dim 64 and positions 0 .. 8191.
