@@ -481,6 +481,52 @@ int op_pack_padded(op_handle* h, const void* ids_dev, int ids_dtype, const void*
 int op_unpack_padded(op_handle* h, const float* packed_dev, const int32_t* cu_seqlens_dev, int n_rows, int width, int channels,
                      float* padded_dev, void* hip_stream);
 
+/* A forward under ANY [n_rows][width] attention mask: left padding, holes, ones behind the padding.  Replaces: the reference
+ * forward handing whatever mask it is given to the encoder under eager attention (standalone.py:1666-1739); additive to ABI 10
+ * (op_abi_version() is unchanged: detect the two calls by symbol).  The packed calls above derive RoPE positions and the sliding
+ * window from token order and so take ones-then-zeros rows only (op_pack_padded status bit 0); this one runs DENSE:
+ *   - every one of the n_rows * width positions is a row of the forward, at position = its column; masked positions are
+ *     queries too (the reference pools column 0 under cls pooling, and under left padding column 0 is a pad token);
+ *   - the mask removes KEYS: a query sees the positions with mask != 0, on a sliding-window layer those of them with
+ *     |q - k| <= local_attention / 2;
+ *   - a query left without a key (a masked position of a sliding-window layer whose whole window is masked) gets what the
+ *     reference's softmax over masked_fill(finfo.min) gives it: uniform weights over all `width` columns of its row, i.e. the
+ *     plain mean of v over the row, per head.  Such a position is never a key: it shows in the cls-pooled ranking logit only;
+ *   - mean pooling sums the final-norm output over the mask != 0 positions and divides by their count.
+ * Outputs: prune_logits_dev [n_rows][width][2] fp32, exactly +0.0 wherever mask == 0 (the reference holds values there);
+ * rank_logits_dev [n_rows][num_labels].  A row whose mask is all zeros gives zeros in both (the reference: a finite cls value,
+ * a NaN mean).  EVERY element of both outputs is written.
+ * Arithmetic: kernel set "fp32" (OP_KS_F32) whatever set the handle has selected -- its LayerNorm, GEMM epilogues and RoPE
+ * lookup, with the attention kernel and the ranking head taking the key mask.  Under a ones-then-zeros mask the outputs at
+ * mask != 0 and the ranking logits are BIT-IDENTICAL to that set's op_forward_packed on the packed rows.  The dense pass
+ * computes the pads and runs at the fp32 MFMA rate: a capability, not a fast path.  Needs the fp32 weight packs:
+ * OP_ERR_UNSUPPORTED on a handle created without OP_FLAG_F32_PACKS (the message names the flag).
+ *   ids_dev   [n_rows][width] int32, contiguous.  EVERY position is embedded, so an id outside 0 <= id < vocab_size is refused
+ *             wherever it sits, under a zero of the mask too (as nn.Embedding does): OP_ERR_INVALID, report->status = 2 and
+ *             (id_row, id_col, id_value) = the first one in row-major order, named in op_last_error; nothing else has run
+ *   mask_dev  [n_rows][width] uint8, contiguous; != 0 means "key"
+ *   report    struct_bytes set by the caller; the call fills the rest
+ * The workspace is the call's own: op_masked_workspace_bytes (the dense cu_seqlens, the id check's status word, the row means
+ * of v, and a forward workspace of kernel set "fp32" for n_rows sequences of `width` tokens; large batches go through in
+ * chunks of rows, as in the forward).  It may hold anything on entry, and nothing outside it and the two outputs is written;
+ * op_workspace_bytes and op_debug_workspace_layout are unchanged.  The id check is read back before the forward is enqueued:
+ * the call SYNCHRONISES hip_stream ONCE, and a stream that is being captured is refused (OP_ERR_STATE).  No handle state is
+ * stored: as stream-safe as op_forward_packed.
+ * Refused before anything is enqueued: OP_ERR_INVALID for a NULL report, a wrong struct_bytes, n_rows < 0, width < 0,
+ * n_rows * width >= 2^31, a NULL buffer of a non-empty batch (all before the handle is looked at), a NULL handle,
+ * width > max_position_embeddings; OP_ERR_UNSUPPORTED without the fp32 packs; OP_ERR_WORKSPACE for a workspace that is too
+ * small or not 256-byte aligned.  n_rows == 0 or width == 0 returns OP_OK with nothing written. */
+typedef struct op_masked_report {
+  uint32_t struct_bytes;  /* sizeof(op_masked_report) */
+  int32_t status;         /* bit 1 (= 2, as op_padded_report): an id outside the embedding table */
+  int32_t id_row, id_col; /* its first offender (row-major); -1 when clear */
+  int64_t id_value;
+} op_masked_report;
+size_t op_masked_workspace_bytes(const op_handle* h, int n_rows, int width);
+int op_forward_masked(op_handle* h, const int32_t* ids_dev, const uint8_t* mask_dev, int n_rows, int width, void* workspace_dev,
+                      size_t workspace_bytes, float* prune_logits_dev, float* rank_logits_dev, op_masked_report* report,
+                      void* hip_stream);
+
 /* Evaluation losses on the device.  Replaces: the losses the reference's inference file computes in its own forward when it
  * is handed labels -- nn.BCEWithLogitsLoss / nn.CrossEntropyLoss on the ranking logits (standalone.py:1707-1722) and
  * nn.CrossEntropyLoss over the pruning logits of the attention_mask == 1 positions (standalone.py:3870-3881) -- plus the

@@ -67,6 +67,8 @@ EXPORTED_SYMBOLS = (
     "op_attention_rows",
     "op_pack_padded",
     "op_unpack_padded",
+    "op_masked_workspace_bytes",
+    "op_forward_masked",
     "op_loss",
     "op_coverage_scan",
     "op_coverage_commit",
@@ -212,6 +214,18 @@ class OpPaddedReport(ctypes.Structure):
         ("status", ctypes.c_int32),
         ("mask_row", ctypes.c_int32),
         ("mask_col", ctypes.c_int32),
+        ("id_row", ctypes.c_int32),
+        ("id_col", ctypes.c_int32),
+        ("id_value", ctypes.c_int64),
+    ]
+
+
+class OpMaskedReport(ctypes.Structure):
+    """``op_masked_report``: what ``op_forward_masked``'s id check found."""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32),
+        ("status", ctypes.c_int32),
         ("id_row", ctypes.c_int32),
         ("id_col", ctypes.c_int32),
         ("id_value", ctypes.c_int64),
@@ -460,6 +474,11 @@ def load_library() -> ctypes.CDLL:
         lib.op_pack_padded.argtypes = [vp, vp, ci, vp, ci, ci, ci, vp, vp, vp, ctypes.POINTER(OpPaddedReport), vp]
         lib.op_unpack_padded.restype = ci
         lib.op_unpack_padded.argtypes = [vp, vp, vp, ci, ci, ci, vp, vp]
+    if hasattr(lib, "op_forward_masked"):  # (additive to ABI 10; the workspace is the call's own)
+        lib.op_masked_workspace_bytes.restype = cs
+        lib.op_masked_workspace_bytes.argtypes = [vp, ci, ci]
+        lib.op_forward_masked.restype = ci
+        lib.op_forward_masked.argtypes = [vp, vp, vp, ci, ci, vp, cs, vp, vp, ctypes.POINTER(OpMaskedReport), vp]
     if hasattr(lib, "op_loss"):  # (additive to ABI 10)
         lib.op_loss.restype = ci
         lib.op_loss.argtypes = [vp, ctypes.POINTER(OpLossRequest), vp, ctypes.POINTER(OpLossReport), vp]

@@ -49,6 +49,7 @@ UNITS = [
     ("op_select", CSRC / "op_select.hip", []),
     ("op_forward", CSRC / "op_forward.hip", []),
     ("op_forward_layers", CSRC / "op_forward_layers.hip", []),
+    ("op_forward_masked", CSRC / "op_forward_masked.hip", []),
     ("op_attention_side", CSRC / "op_attention_side.hip", []),
     ("op_services", CSRC / "op_services.hip", []),
     # one launch unit per kernel family
@@ -65,6 +66,7 @@ UNITS = [
     ("op_launch_padded", CSRC / "op_launch_padded.hip", []),
     ("op_launch_audit", CSRC / "op_launch_audit.hip", []),
     ("op_launch_f32", CSRC / "op_launch_f32.hip", []),
+    ("op_launch_f32_masked", CSRC / "op_launch_f32_masked.hip", []),
     ("op_launch_attn_probs", CSRC / "op_launch_attn_probs.hip", []),
     ("op_launch_probe", CSRC / "op_launch_probe.hip", []),
     ("op_launch_loss", CSRC / "op_launch_loss.hip", []),

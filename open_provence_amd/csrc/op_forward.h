@@ -39,6 +39,7 @@ struct ChunkPass {
   int s0, ns, rows, max_len;  // this chunk: sequences [s0, s0 + ns), its rows and its longest sequence
   const AttnPlan& plan;
   const HiddenReq* hid;  // per-call hidden-state request, or nullptr
+  const MaskedReq* msk;  // op_forward_masked: kernel set "fp32" with the key mask's attention and heads, or nullptr
 
   int H, I;
   bool fp_layout;  // fragment-packed activations, attn_fp_kernel
@@ -63,7 +64,7 @@ struct ChunkPass {
   int hidden_stored = -1;  // the hidden-state entry the last layer launch stored itself (wave-pair kernel), -1: none
 
   ChunkPass(op_handle* h_, Launcher& L_, const Workspace& ws_, const PackedBatch& b_, int s0_, int ns_, int rows_, int max_len_,
-            const AttnPlan& plan_, const HiddenReq* hid_);
+            const AttnPlan& plan_, const HiddenReq* hid_, const MaskedReq* msk_ = nullptr);
 
   // the pack of a GEMM weight of layer `li` in the format the constructor decided
   u16* weight(int li, Weight w, PackFmt f) const { return h->layers[li].pack[w][f]; }

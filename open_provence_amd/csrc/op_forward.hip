@@ -51,8 +51,8 @@ void launch_side_row_map(hipStream_t stream, const int32_t* cu_dev, int s0, int 
 }
 
 ChunkPass::ChunkPass(op_handle* h_, Launcher& L_, const Workspace& ws_, const PackedBatch& b_, int s0_, int ns_, int rows_, int max_len_,
-                     const AttnPlan& plan_, const HiddenReq* hid_)
-    : h(h_), L(L_), ws(ws_), b(b_), s0(s0_), ns(ns_), rows(rows_), max_len(max_len_), plan(plan_), hid(hid_) {
+                     const AttnPlan& plan_, const HiddenReq* hid_, const MaskedReq* msk_)
+    : h(h_), L(L_), ws(ws_), b(b_), s0(s0_), ns(ns_), rows(rows_), max_len(max_len_), plan(plan_), hid(hid_), msk(msk_) {
   H = h->H;
   I = h->I;
   // Row path: exactly the computed rows, rounded to the 128-row block -- no slack rows: a 131072-row batch is 1024
@@ -65,8 +65,8 @@ ChunkPass::ChunkPass(op_handle* h_, Launcher& L_, const Workspace& ws_, const Pa
   st = L.stream;
   // Evaluated policy E, instantiated kernel set V (V has every term of E).  Where V multiplies by a lo operand that
   // E does not have, that operand is cleared: weights at load time (op_load_weight), activations in the launch sequence.
-  const KernelSet& ks = *h->ks;
-  E = h->eff;
+  const KernelSet& ks = msk ? kKernelSets[OP_KS_F32] : *h->ks;  // (a masked forward: set "fp32" on any handle with its packs)
+  E = msk ? ks.terms : h->eff;
   pi = ks.pi;
   V = opl::kPolicies[pi];
   o_f8 = ks.side == FMT_F8;   // o = fp16 pieces (ws.o_hi) + e4m3 pieces (ws.o_lo); panel path: every GEMM in that format
@@ -167,7 +167,7 @@ int ChunkPass::prologue() {
 }
 
 int ChunkPass::capture(int index) {
-  if (!h->capture) return OP_OK;
+  if (!h->capture || msk) return OP_OK;  // (the test hook's buffer is sized for a packed batch: a masked pass leaves it alone)
   OP_TRY(L.begin(PK_CAPTURE));
   hipLaunchKernelGGL(capture_rows_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, ws.row_tok, H, r_pad,
                      h->capture + (size_t)index * b.total_tokens * H);
@@ -277,12 +277,17 @@ int ChunkPass::heads() {
     hipLaunchKernelGGL(final_ln_prune_kernel, dim3(row_blocks), dim3(256), 0, st, ws.x, h->final_norm, h->cfg.norm_eps, H,
                        r_pad, ws.row_tok, ws.row_seq, ws.row_pos, h->prune_w, h->prune_b, b.prune_out, b.keep_prob,
                        h->cfg.prune_pre_final_norm ? 1 : 0, mean_pool, ws.cls,
-                       h->capture ? h->capture + (size_t)h->N * b.total_tokens * H : nullptr,
+                       (h->capture && !msk) ? h->capture + (size_t)h->N * b.total_tokens * H : nullptr,
                        range_flagged ? ws.range_flag : nullptr);
     OP_TRY(L.end());
   }
   OP_TRY(L.begin(PK_RANK_HEAD));
-  if (f32)
+  if (msk) {
+    opl::launch_f32_rank_head_masked(st, ns, ws.cls, ws.x, b.cu_dev, s0, ws.roff, msk->key_ok, mean_pool, H, h->nl, h->dense_t,
+                                     h->head_norm, h->cfg.norm_eps, h->cls_w, h->cls_b, b.rank_out);
+    // (final_ln_prune_kernel wrote every position of the chunk's rows: tokens cu[s0] .. cu[s0 + ns])
+    opl::launch_prune_mask(st, b.prune_out, msk->key_ok, (size_t)msk->cu_host[s0], (size_t)(msk->cu_host[s0 + ns] - msk->cu_host[s0]));
+  } else if (f32)
     opl::launch_f32_rank_head(st, ns, ws.cls, ws.x, b.cu_dev, s0, ws.roff, mean_pool, H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps,
                               h->cls_w, h->cls_b, b.rank_out);
   else
@@ -327,7 +332,7 @@ int host_cu_seqlens(op_handle* h, const PackedBatch& b, std::vector<int32_t>& cu
 }
 
 // op_forward_packed, and op_forward_packed_hidden / _pooled with their validated request (hid; nullptr: none)
-int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid) {
+int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid, const MaskedReq* msk) {
   if (!h) return fail(nullptr, OP_ERR_INVALID, "op_forward_packed: NULL handle");
   if (b.n_seqs < 0 || b.total_tokens < 0 || b.max_seqlen < 0) return fail(h, OP_ERR_INVALID, "negative size");
   if (b.n_seqs == 0 || b.total_tokens == 0) {
@@ -341,7 +346,7 @@ int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid
   if (op_weights_ready(h) != OP_OK) return OP_ERR_STATE;
   if ((reinterpret_cast<uintptr_t>(b.workspace) & 255) != 0)
     return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-  const opp::Layout lay = forward_layout(h, b.n_seqs, b.total_tokens, b.max_seqlen, h->set == OP_KS_F32);  // (= op_workspace_bytes)
+  const opp::Layout lay = forward_layout(h, b.n_seqs, b.total_tokens, b.max_seqlen, msk || h->set == OP_KS_F32);  // (= op_workspace_bytes)
   if (b.workspace_bytes < lay.bytes)
     return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", b.workspace_bytes, lay.bytes);
 
@@ -362,7 +367,7 @@ int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid
     if (rows > cap) return fail(h, OP_ERR_WORKSPACE, "internal: chunk of %d rows exceeds capacity %d", rows, cap);
     const AttnPlan plan = opp::attention_plan(cu, s0, s1, max_len, h->nh, h->n_cus, h->cfg.flags);
     if (rows > 0) {
-      OP_TRY(ChunkPass(h, L, ws, b, s0, s1 - s0, rows, max_len, plan, hid).run());
+      OP_TRY(ChunkPass(h, L, ws, b, s0, s1 - s0, rows, max_len, plan, hid, msk).run());
     } else {
       // only empty sequences in this chunk
       OP_HIP(h, hipMemsetAsync(b.rank_out + (size_t)s0 * h->nl, 0, (size_t)(s1 - s0) * h->nl * sizeof(float), b.stream));

@@ -454,7 +454,18 @@ int ChunkPass::f32_layer(int li) {
   ap.roff = ws.roff;
   ap.H = H;
   ap.window = is_global ? -1 : h->cfg.local_attention / 2;
-  opl::launch_f32_attn(st, ap, dim3((unsigned)q_tiles, (unsigned)h->nh, (unsigned)ns));
+  const dim3 attn_grid((unsigned)q_tiles, (unsigned)h->nh, (unsigned)ns);
+  if (msk) {
+    // the mask removes keys; a query of a sliding-window layer left without one takes the row's mean of v
+    F32MaskedAttnParams mp;
+    mp.a = ap;
+    mp.key_ok = msk->key_ok;
+    mp.vmean = is_global ? nullptr : msk->vmean;
+    if (!is_global) opl::launch_f32_vmean(st, ws.f.v, b.cu_dev, s0, ws.roff, H, ns, msk->vmean);
+    opl::launch_f32_attn_masked(st, mp, attn_grid);
+  } else {
+    opl::launch_f32_attn(st, ap, attn_grid);
+  }
   OP_TRY(L.end());
 
   // x += o Wo^T

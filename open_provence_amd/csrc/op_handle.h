@@ -1,5 +1,5 @@
 // op_handle.h -- what the units of the C ABI share (op_api / op_weights / op_select / op_forward / op_forward_layers /
-// op_attention_side / op_services .hip): the handle, the error and launch helpers, a packed batch as an entry point receives
+// op_forward_masked / op_attention_side / op_services .hip): the handle, the error and launch helpers, a packed batch as an entry point receives
 // it, and the declarations of the functions one unit defines and another calls.  Host side only.
 #pragma once
 
@@ -208,6 +208,14 @@ struct PackedBatch {
   hipStream_t stream = nullptr;
 };
 
+// op_forward_masked's addition to a forward: the batch is dense (a sequence = a padded row of `width` positions), runs on kernel
+// set "fp32" whatever set the handle has selected, and the mask removes keys (opk_f32_masked.hip.h).
+struct MaskedReq {
+  const uint8_t* key_ok = nullptr;  // [total_tokens]
+  float* vmean = nullptr;           // [n_seqs][H]: the row means of v of the sliding-window layer in flight
+  const int32_t* cu_host = nullptr; // [n_seqs + 1]: the dense cu_seqlens on the host (a chunk's tokens, for the pruning logits' zeros)
+};
+
 // ---- defined once, in the unit named; called from others -------------------------------------------------------------------
 // op_api.hip
 int drain_profile(op_handle* h);
@@ -222,8 +230,9 @@ int chunk_row_capacity(const op_handle* h, int n_seqs, int total_tokens, int max
 // the regions of a forward's workspace for a batch of this geometry; f32: with the planes of kernel set "fp32"
 opp::Layout forward_layout(const op_handle* h, int n_seqs, int total_tokens, int max_seqlen, bool f32);
 int host_cu_seqlens(op_handle* h, const PackedBatch& b, std::vector<int32_t>& cu_copy, const int32_t** cu_out);
-// op_forward_packed, and op_forward_packed_hidden / _pooled with their validated request (hid; nullptr: none)
-int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid);
+// op_forward_packed, and op_forward_packed_hidden / _pooled with their validated request (hid; nullptr: none); msk: the dense
+// forward of op_forward_masked over its own workspace
+int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid, const MaskedReq* msk = nullptr);
 // the row map of the chunk [s0, s0 + ns) as the attention side passes take it: the forward's seq_offsets_kernel (aligned row
 // offsets into roff) and row_map_kernel, which only the forward unit holds
 void launch_side_row_map(hipStream_t stream, const int32_t* cu_dev, int s0, int ns, int r_pad, int32_t* roff, int32_t* row_seq,

@@ -12,6 +12,7 @@
 #include "opk_attn_probs.hip.h"
 #include "opk_common.hip.h"
 #include "opk_f32.hip.h"
+#include "opk_f32_masked.hip.h"
 #include "opk_layer32.hip.h"
 #include "opk_layer16p.hip.h"
 #include "opk_panel.hip.h"
@@ -69,6 +70,20 @@ void launch_f32_attn(hipStream_t st, const opk::F32AttnParams& p, dim3 grid);
 void launch_f32_rank_head(hipStream_t st, int n_seqs, const float* cls, const float* y, const int32_t* cu, int s0, const int32_t* roff,
                           int mean_pool, int H, int nl, const float* dense_t, const float* head_norm, float eps, const float* cls_w,
                           const float* cls_b, float* rank_out);
+
+// op_forward_masked (opk_f32_masked.hip.h; op_launch_f32_masked.hip) beside the launches above.
+// cu[n_rows + 1] = r * width, and *status (preset to opk::MASKED_ST_NONE) = the linear index of the first id outside [0, vocab)
+void launch_masked_prepare(hipStream_t st, const int32_t* ids, int n_rows, int width, int vocab, int32_t* cu, uint32_t* status);
+// vmean[n_seqs][H]: the mean of v over each sequence's positions (the n_seqs sequences from s0 on)
+void launch_f32_vmean(hipStream_t st, const float* v, const int32_t* cu, int s0, const int32_t* roff, int H, int n_seqs, float* vmean);
+// launch_f32_attn's grid
+void launch_f32_attn_masked(hipStream_t st, const opk::F32MaskedAttnParams& p, dim3 grid);
+// launch_f32_rank_head's arguments and key_ok[total_tokens]
+void launch_f32_rank_head_masked(hipStream_t st, int n_seqs, const float* cls, const float* y, const int32_t* cu, int s0,
+                                 const int32_t* roff, const uint8_t* key_ok, int mean_pool, int H, int nl, const float* dense_t,
+                                 const float* head_norm, float eps, const float* cls_w, const float* cls_b, float* rank_out);
+// prune[t][0 .. 1] = +0.0 where key_ok[t] == 0, t in [t0, t0 + n_tokens)
+void launch_prune_mask(hipStream_t st, float* prune, const uint8_t* key_ok, size_t t0, size_t n_tokens);
 
 // op_attention_probs (opk_attn_probs.hip.h; op_launch_attn_probs.hip) beside launch_f32_ln and launch_f32_gemm(F32_EPI_QKV).
 // packed [total_tokens][H] fp32 -> the row layout [r_pad][H] through row_tok (zero rows where row_tok < 0)

@@ -53,7 +53,7 @@ struct F32AttnParams {
   int window;  // < 0: full attention; else keys with |q - k| <= window
 };
 
-#ifdef OPK_F32_KERNELS
+#if defined(OPK_F32_KERNELS) || defined(OPK_F32_MASKED_KERNELS)  // (what opk_f32_masked.hip.h shares with the kernels below)
 
 constexpr int F32_LDS = 36;      // LDS row stride of a 32-float K slab (32 + 4 pad: 16-byte aligned rows, spread over the banks)
 constexpr int F32_ACC_SLABS = 4; // K slabs (of 32) summed in one fmaf chain before the chain is added to the running total
@@ -64,6 +64,20 @@ constexpr int F32_ATT_LDS = 68;  // LDS row stride of a 64-float K / V row (4 ro
 __device__ __forceinline__ f32x4 mfma_f32(float x, float y, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0); }
 
 __device__ __forceinline__ float gelu_erf_exact(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
+// the sum of a 256-thread block (the ranking heads)
+__device__ __forceinline__ float block_sum_f32(float v, float* red) {
+  v = wave_sum(v);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) red[wave] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+#endif
+
+#ifdef OPK_F32_KERNELS
 
 // ----------------------------------------------------------------------------------------------
 // y = (x - mean) / sqrt(var + eps) * w into an fp32 plane: one wave per row (the arithmetic of ln_kernel, opk_layernorm.hip.h)
@@ -475,15 +489,6 @@ __global__ __launch_bounds__(256, 2) void attn_f32_kernel(F32AttnParams p) {
 // logit when the dense layer's outputs are small (mean pooling, reference-initialised head) -- and with the sums over
 // tokens and over k taken in chunks of 16 / 128.  One block per sequence; dense weight transposed [k][n].
 // ----------------------------------------------------------------------------------------------
-__device__ __forceinline__ float block_sum_f32(float v, float* red) {
-  v = wave_sum(v);
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return (red[0] + red[1]) + (red[2] + red[3]);
-}
-
 __global__ __launch_bounds__(256) void rank_head_f32_kernel(const float* __restrict__ cls, const float* __restrict__ y,
                                                             const int32_t* __restrict__ cu, int s0, const int32_t* __restrict__ roff,
                                                             int mean_pool, int H, int nl, const float* __restrict__ dense_t,

@@ -205,6 +205,18 @@ def check_arithmetic_arguments(kernel_set: "str | None", calibration_reference: 
     return (None if kernel_set in (None, "auto") else str(kernel_set)), reference
 
 
+ATTENTION_MASKS = ("prefix", "any")
+
+
+def check_attention_masks(attention_masks: "str | None") -> str:
+    """Validate ``attention_masks=`` before anything touches the device: ``"prefix"`` (None: the default) or ``"any"``."""
+
+    value = "prefix" if attention_masks is None else attention_masks
+    if not isinstance(value, str) or value not in ATTENTION_MASKS:
+        raise ValueError(f"unknown attention_masks {attention_masks!r}; expected one of {ATTENTION_MASKS}")
+    return value
+
+
 def require_gpu(device: torch.device | str | int | None = None) -> torch.device:
     """Resolve a HIP device or fail loudly (the product has no CPU path)."""
 
@@ -241,6 +253,7 @@ class HipEncoder:
         kernel_set: "str | None" = None,
         calibration_reference: str = "bf16x3",
         attention_outputs: bool = False,
+        attention_masks: str = "prefix",
     ) -> None:
         """``audit`` / ``audit_every`` / ``audit_tokens``: how a kernel set chosen by :meth:`calibrate` is re-checked on real
         batches -- ``"first"`` (default; ``None`` reads ``OPEN_PROVENCE_AUDIT``): once, on the first real batch
@@ -252,9 +265,12 @@ class HipEncoder:
         ``"fp32"`` (kernel set "fp32"; keeps the fp32 weights too).
         ``attention_outputs``: keep the fp32 GEMM weights (4 bytes per weight element more on the device) so that
         :meth:`attention_probs` / ``forward_packed(attentions=...)`` can run; it changes nothing else.  ``kernel_set="fp32"``
-        and ``calibration_reference="fp32"`` imply it."""
+        and ``calibration_reference="fp32"`` imply it.
+        ``attention_masks``: ``"prefix"`` (default: right-padded masks only) or ``"any"`` -- :meth:`forward_masked` takes any
+        ``[B, L]`` mask on the fp32 kernels; implies the fp32 weights, as ``attention_outputs=True`` does."""
 
         self.kernel_set, self.calibration_reference = check_arithmetic_arguments(kernel_set, calibration_reference)
+        self.attention_masks = check_attention_masks(attention_masks)
         self.audit_mode = resolve_audit_mode(audit)
         self.audit_every = int(audit_every)
         self.audit_tokens = int(audit_tokens)
@@ -292,7 +308,7 @@ class HipEncoder:
                 flags |= _lib.OP_FLAG_ATT_WAVES_4 if int(waves) == 4 else _lib.OP_FLAG_ATT_WAVES_8
         if "fp32" in (self.kernel_set, self.calibration_reference) or os.environ.get("OPEN_PROVENCE_KERNEL_SET") == "fp32":
             flags |= _lib.OP_FLAG_F32_PACKS
-        if attention_outputs:
+        if attention_outputs or self.attention_masks == "any":
             flags |= _lib.OP_FLAG_F32_PACKS
         self.attention_outputs = bool(flags & _lib.OP_FLAG_F32_PACKS)  # the fp32 weight packs op_attention_probs reads exist
         cfg.flags = int(flags)
@@ -311,6 +327,7 @@ class HipEncoder:
         self._split_state: dict | None = None  # the two pipeline streams + their workspaces (forward_packed_on)
         self._workspace: torch.Tensor | None = None
         self._attention_workspace: torch.Tensor | None = None  # op_attention_probs' own, reused across layers and calls
+        self._masked_workspace: torch.Tensor | None = None  # op_forward_masked's own
         self._audit_workspace: torch.Tensor | None = None  # of an audit's reference forward, when the batch's own is too small for it
         self._capture: torch.Tensor | None = None
         self._capture_result: torch.Tensor | None = None
@@ -1395,6 +1412,69 @@ class HipEncoder:
                 f"vocab_size is {self.dims.vocab_size}"
             )
 
+    # -- any attention mask: the dense forward on the fp32 kernels (op_forward_masked) ------------------------------------------
+    def forward_masked(self, input_ids: torch.Tensor, attention_mask: torch.Tensor,
+                       workspace: "torch.Tensor | None" = None) -> "tuple[torch.Tensor, torch.Tensor]":
+        """``input_ids[B, L]`` + ANY ``attention_mask[B, L]`` (left padding, holes; CPU or this device) -> ``(pruning_logits[B, L,
+        2], ranking_logits[B, num_labels])`` fp32 on the device, on an encoder created with ``attention_masks="any"``.  Every
+        position is a row at position = its column and the mask removes keys only, as in the reference under eager attention;
+        a query left without a key in a sliding-window layer takes the mean of ``v`` over its row.  Pruning logits are exact
+        zeros where the mask is 0; a row whose mask is all zeros gives zeros in both outputs.  fp32 arithmetic of kernel set
+        "fp32" whatever set the forward runs on; the dense pass computes the pads.  Every position is embedded: an id outside
+        the table raises ``IndexError`` wherever it sits.  The current torch stream is synchronised once (the id check).
+        ``workspace``: a uint8 device tensor to carve instead of the encoder's own (concurrent calls on several streams)."""
+
+        if self.attention_masks != "any":
+            raise ValueError('forward_masked needs the fp32 weight packs: create the encoder / model with attention_masks="any"')
+        if not hasattr(self.lib, "op_forward_masked"):
+            raise _lib.HipLibraryError("this library has no op_forward_masked")
+        input_ids, attention_mask = torch.as_tensor(input_ids), torch.as_tensor(attention_mask)
+        if input_ids.ndim != 2:
+            raise ValueError("input_ids must be [B, L]")
+        n_rows, width = int(input_ids.shape[0]), int(input_ids.shape[1])
+        if tuple(attention_mask.shape) != (n_rows, width):
+            raise ValueError("attention_mask shape must match input_ids")
+        if n_rows * width >= 2**31:
+            raise ValueError("batch has more than 2^31 positions")
+        if width > self.dims.max_position_embeddings:
+            raise ValueError(f"width {width} exceeds max_position_embeddings {self.dims.max_position_embeddings}")
+        ids_in = input_ids.detach()
+        if ids_in.dtype.is_floating_point or ids_in.dtype in (torch.bool, torch.complex64, torch.complex128):
+            raise TypeError(f"input_ids must be an integer tensor, got {ids_in.dtype}")
+        ids_in = ids_in.to(self.device)
+        if ids_in.dtype != torch.int32:  # (an id beyond int32 is outside every table: it stays outside, -1 or 2^31 - 1)
+            ids_in = ids_in.to(torch.int64).clamp(-1, 2**31 - 1).to(torch.int32)
+        ids_in = ids_in.contiguous()
+        mask_in = attention_mask.detach().to(self.device).ne(0).contiguous().view(torch.uint8)
+        vp = ctypes.c_void_p
+        report = _lib.OpMaskedReport()
+        report.struct_bytes = ctypes.sizeof(_lib.OpMaskedReport)
+        with torch.cuda.device(self.device):
+            prune = torch.empty((n_rows, width, 2), dtype=torch.float32, device=self.device)
+            rank = torch.empty((n_rows, self.dims.num_labels), dtype=torch.float32, device=self.device)
+            if prune.numel() == 0:
+                return prune, rank.zero_()
+            need = int(self.lib.op_masked_workspace_bytes(self._handle, n_rows, width)) + 256
+            ws = workspace if workspace is not None else self._masked_workspace
+            if ws is None or ws.numel() < need:
+                if workspace is not None:
+                    raise ValueError(f"workspace has {ws.numel()} bytes, need {need}")
+                ws = self._masked_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+            base = ws.data_ptr()
+            aligned = (base + 255) // 256 * 256
+            code = self.lib.op_forward_masked(
+                self._handle, vp(ids_in.data_ptr()), vp(mask_in.data_ptr()), n_rows, width, vp(aligned),
+                ctypes.c_size_t(ws.numel() - (aligned - base)), vp(prune.data_ptr()), vp(rank.data_ptr()), ctypes.byref(report),
+                vp(torch.cuda.current_stream(self.device).cuda_stream),
+            )
+        if code == _lib.OP_ERR_INVALID and int(report.status) & _lib.OP_PADDED_BAD_ID:
+            raise IndexError(
+                f"token id out of range for the embedding table: id {int(report.id_value)} at row {int(report.id_row)}, "
+                f"column {int(report.id_col)}; vocab_size is {self.dims.vocab_size}"
+            )
+        _lib.check(self.lib, self._handle, code, "op_forward_masked")
+        return prune, rank
+
     # -- the padded boundary on the device (op_pack_padded / op_unpack_padded) -----------------------------------------
     def pack_padded_device(self, input_ids: torch.Tensor, attention_mask: "torch.Tensor | None"
                            ) -> "tuple[torch.Tensor, torch.Tensor, np.ndarray, int]":
@@ -1404,6 +1484,13 @@ class HipEncoder:
         run in HIP kernels on the current stream, which is synchronised once (the forward needs T and ``max_len`` on the host).
         Raises what the host path raises: ``NotImplementedError`` for a mask that is not ones-then-zeros (it wins when both
         faults are present, as on the host), ``IndexError`` for an id outside the embedding table at an unmasked position."""
+
+        return self._pack_padded_device(input_ids, attention_mask, non_prefix_ok=False)
+
+    def _pack_padded_device(self, input_ids, attention_mask, non_prefix_ok: bool):
+        """:meth:`pack_padded_device`; ``non_prefix_ok``: a mask that is not ones-then-zeros returns None instead of raising
+        (forward() on an ``attention_masks="any"`` model then runs :meth:`forward_masked`: the same single synchronisation
+        has decided the route)."""
 
         if input_ids.ndim != 2:
             raise ValueError("input_ids must be [B, L]")
@@ -1445,6 +1532,8 @@ class HipEncoder:
             )
         status = int(report.status)
         if code == _lib.OP_ERR_INVALID and status & _lib.OP_PADDED_BAD_MASK:
+            if non_prefix_ok:
+                return None
             raise NotImplementedError(
                 "attention_mask must be right-padded (ones then zeros): the packed HIP path derives positions "
                 "from token order, exactly what the reference's process() produces (standalone.py:2832-2880)."

@@ -34,7 +34,7 @@ import torch
 
 from . import launches, pipeline as pl, request as rq
 from .config import DEFAULT_PROCESS_THRESHOLD, EncoderDims, OpenProvenceConfig
-from .engine import AttentionRequest, HiddenRequest, HipEncoder, check_arithmetic_arguments, require_gpu
+from .engine import AttentionRequest, HiddenRequest, HipEncoder, check_arithmetic_arguments, check_attention_masks, require_gpu
 from .packing import pack_padded, pack_rows, unpack_to_padded
 from .pipeline import ContextState, FragmentRecord, RawPrediction
 from .prepared import PreparedContexts, PreparedItem, as_request as _as_prepared_request, derive_row_template
@@ -227,14 +227,18 @@ class OpenProvenceModel:
         audit_tokens: int | None = None,
         calibration_reference: str | None = None,
         attention_outputs: bool = False,
+        attention_masks: str = "prefix",
     ) -> None:
         # attention_outputs: keep the fp32 GEMM weights on the device so that forward(output_attentions=True) can run
         # (HipEncoder; nothing else changes);
+        # attention_masks: "prefix" (right-padded masks only) or "any": forward() also takes left padding and holes, on the
+        # fp32 kernels (HipEncoder.forward_masked; keeps the fp32 weights too);
         # kernel_set / calibrate / calibration_rows: how the arithmetic is chosen from the loaded weights
         # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615);
         # calibration_reference: what a calibration compares with, "bf16x3" (default) or "fp32" (kernel set "fp32");
         # audit / audit_every / audit_tokens: how a calibrated choice is re-checked on real batches (audit.maybe_audit)
         kernel_set, calibration_reference = check_arithmetic_arguments(kernel_set, calibration_reference)
+        attention_masks = check_attention_masks(attention_masks)
         self._kernel_set_request = kernel_set
         self._calibrate_request = calibrate
         self._calibration_rows = calibration_rows
@@ -262,6 +266,7 @@ class OpenProvenceModel:
             prune_pre_final_norm=self.pruning_hidden_state == "pre_final_norm",
             audit=audit, audit_every=audit_every, **({} if audit_tokens is None else {"audit_tokens": audit_tokens}),
             kernel_set=kernel_set, calibration_reference=calibration_reference, attention_outputs=attention_outputs,
+            attention_masks=attention_masks,
         )
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -541,6 +546,7 @@ class OpenProvenceModel:
             audit_tokens=kwargs.pop("audit_tokens", None),
             calibration_reference=kwargs.pop("calibration_reference", None),
             attention_outputs=bool(kwargs.pop("attention_outputs", False)),
+            attention_masks=kwargs.pop("attention_masks", "prefix"),
         )
         if max_length is not None:
             model.max_length = int(max_length)
@@ -656,11 +662,15 @@ class OpenProvenceModel:
             raise TypeError(f"class labels must be an integer tensor, got {labels.dtype}")
         return labels
 
-    def _forward_padded(self, input_ids, attention_mask, output_hidden_states, output_attentions, reduced=None):
+    def _forward_padded(self, input_ids, attention_mask, output_hidden_states, output_attentions, reduced=None, token_loss=False):
         """The forward of a padded batch without its losses: ``(ranking_logits, pruning_logits, hidden_states, attentions,
         packed)``; ``packed`` = the pruning logits as the kernels left them, ``[T, 2]`` on the device, with the batch's
         ``cu_seqlens`` on the device and the token count -- what the token-classification loss reads.  ``reduced``
-        (:meth:`_reduced_requests`): the pooled hidden states and / or attention rows go into its ``results``."""
+        (:meth:`_reduced_requests`): the pooled hidden states and / or attention rows go into its ``results``.
+
+        On a model created with ``attention_masks="any"`` a batch with a row that is not ones-then-zeros goes through
+        :meth:`HipEncoder.forward_masked` (``packed`` is then None); a prefix-mask batch takes the packed path as ever.
+        ``token_loss``: the caller wants ``packed`` for the token-classification loss."""
 
         if output_attentions and not self.encoder.attention_outputs:
             raise ValueError("output_attentions=True needs the fp32 weight packs: create the model with attention_outputs=True")
@@ -671,10 +681,21 @@ class OpenProvenceModel:
         on_device = (dev.type == "cuda" and isinstance(input_ids, torch.Tensor) and input_ids.device == dev
                      and (attention_mask is None or (isinstance(attention_mask, torch.Tensor) and attention_mask.device == dev)))
         ids_np = None  # (a device-resident batch has no host copy: the running audit scans it on the device)
+        any_mask = attention_mask is not None and getattr(self.encoder, "attention_masks", "prefix") == "any"
         if on_device:
-            ids, cu, cu_np, max_len = self.encoder.pack_padded_device(input_ids, attention_mask)
+            # (op_pack_padded's one synchronisation reports the mask's shape too: no second round trip decides the route)
+            packed_batch = (self.encoder._pack_padded_device(input_ids, attention_mask, non_prefix_ok=True) if any_mask
+                            else self.encoder.pack_padded_device(input_ids, attention_mask))
+            if packed_batch is None:
+                return self._forward_any_mask(input_ids, attention_mask, output_hidden_states, output_attentions, reduced, token_loss)
+            ids, cu, cu_np, max_len = packed_batch
         else:
-            ids_np, cu_np, max_len = pack_padded(input_ids, attention_mask)
+            try:
+                ids_np, cu_np, max_len = pack_padded(input_ids, attention_mask)
+            except NotImplementedError:  # (a row that is not ones-then-zeros)
+                if not any_mask:
+                    raise
+                return self._forward_any_mask(input_ids, attention_mask, output_hidden_states, output_attentions, reduced, token_loss)
             self.encoder.check_ids(ids_np)
             ids = torch.from_numpy(ids_np).to(dev)
             cu = torch.from_numpy(cu_np).to(dev)
@@ -710,6 +731,22 @@ class OpenProvenceModel:
         else:
             pruning_logits = unpack_to_padded(prune, cu_np, width)
         return rank, pruning_logits, hidden_states, attentions, (prune, cu, int(cu_np[-1]))
+
+    def _forward_any_mask(self, input_ids, attention_mask, output_hidden_states, output_attentions, reduced, token_loss):
+        """:meth:`_forward_padded` for a batch with a non-prefix row, on a model created with ``attention_masks="any"``: the
+        dense forward on the fp32 kernels.  The requests it does not serve yet raise ``NotImplementedError`` by name."""
+
+        requested = [name for name, on in (
+            ("output_hidden_states", output_hidden_states), ("output_attentions", output_attentions),
+            ("attention_rows", reduced is not None and reduced["query"] is not None),
+            ("pooled_hidden_states", reduced is not None and reduced["pool"] is not None),
+            ("the token-classification loss (labels)", token_loss)) if on]
+        if requested:
+            raise NotImplementedError(
+                f"{', '.join(requested)}: not available for an attention_mask that is not right-padded (ones then zeros); "
+                "forward() serves the logits and the ranking loss for such a batch")
+        prune, rank = self.encoder.forward_masked(input_ids, attention_mask)
+        return rank, prune, None, None, None
 
     @staticmethod
     def _attention_rows_request(reduced, width: int, n_rows: int) -> "AttentionRequest | None":
@@ -1926,11 +1963,13 @@ class OpenProvenceForTokenClassification(OpenProvenceModel):
                 raise ValueError(f"labels must have the shape of input_ids {tuple(input_ids.shape)}, got {tuple(token_labels.shape)}")
             token_labels = token_labels.detach().to(self._runtime_device)
         reduced: dict[str, Any] = {}
-        rank, pruning_logits, hidden_states, attentions, (prune, cu, total) = self._forward_padded(
+        rank, pruning_logits, hidden_states, attentions, packed = self._forward_padded(
             input_ids, attention_mask, output_hidden_states, output_attentions,
-            reduced=self._reduced_requests(pooled_hidden_states, attention_rows, attention_rows_reduce_heads, reduced))
+            reduced=self._reduced_requests(pooled_hidden_states, attention_rows, attention_rows_reduce_heads, reduced),
+            token_loss=token_labels is not None)
         loss = None
         if token_labels is not None:
+            prune, cu, total = packed
             if attention_mask is not None and total == 0:
                 loss = torch.zeros((), dtype=torch.float32, device=pruning_logits.device)
             else:
