@@ -527,6 +527,29 @@ int op_forward_masked(op_handle* h, const int32_t* ids_dev, const uint8_t* mask_
                       size_t workspace_bytes, float* prune_logits_dev, float* rank_logits_dev, op_masked_report* report,
                       void* hip_stream);
 
+/* op_forward_masked on the handle's SELECTED kernel set.  The same arguments, semantics, outputs, id check, single stream
+ * synchronisation and capturing-stream refusal; the refusals come in the same order with the same wording (under this call's
+ * name).  Additive to ABI 10 (op_abi_version() is unchanged: detect the call by symbol).
+ * Arithmetic: the kernel set the handle's op_forward_packed runs on (the default selection, op_select_kernel_set, op_calibrate;
+ * the layer mask of sets 8 / 9 and the range guard of the fp16 + e4m3 sets included: a flagged chunk leaves NaN logits at
+ * mask != 0) -- its RoPE, whole-layer kernels, embedding and head fusions unchanged.  Three places take the mask: the
+ * attention kernel (a key-mask form of the same instantiation: the same tiles in the same order), mean pooling in the
+ * ranking head, and the zeros of the outputs.  A query without a key takes the mean of v over its row AS THE SET STORES v
+ * (sliding-window layers) or +0.0 (full-attention layers: only in a row whose mask is all zeros).  Under a ones-then-zeros
+ * mask the outputs at mask != 0 and the ranking logits are BIT-IDENTICAL to the handle's op_forward_packed on the packed
+ * rows, given the same attention plan (OP_FLAG_ATT_WAVES_4 / _8 pin it; the default plan reads the row lengths).  The dense
+ * pass still computes the pads.  It does NOT need the fp32 weight packs.
+ * OP_ERR_UNSUPPORTED, in the place of op_forward_masked's check for the packs and with a message that names
+ * op_forward_masked: a handle on the tiled path (neither the row nor the panel path; OP_FLAG_FORCE_TILED included), and a
+ * handle whose selected set is "fp32" (that call IS its masked forward).
+ * The workspace is the call's own: op_masked_native_workspace_bytes (the dense cu_seqlens, the id check's status word, the
+ * mask in the row layout, the row means of v, and a forward workspace of the selected set for n_rows sequences of `width`
+ * tokens).  It may hold anything on entry; op_workspace_bytes and op_debug_workspace_layout are unchanged. */
+size_t op_masked_native_workspace_bytes(const op_handle* h, int n_rows, int width);
+int op_forward_masked_native(op_handle* h, const int32_t* ids_dev, const uint8_t* mask_dev, int n_rows, int width,
+                             void* workspace_dev, size_t workspace_bytes, float* prune_logits_dev, float* rank_logits_dev,
+                             op_masked_report* report, void* hip_stream);
+
 /* Evaluation losses on the device.  Replaces: the losses the reference's inference file computes in its own forward when it
  * is handed labels -- nn.BCEWithLogitsLoss / nn.CrossEntropyLoss on the ranking logits (standalone.py:1707-1722) and
  * nn.CrossEntropyLoss over the pruning logits of the attention_mask == 1 positions (standalone.py:3870-3881) -- plus the

@@ -69,6 +69,8 @@ EXPORTED_SYMBOLS = (
     "op_unpack_padded",
     "op_masked_workspace_bytes",
     "op_forward_masked",
+    "op_masked_native_workspace_bytes",
+    "op_forward_masked_native",
     "op_loss",
     "op_coverage_scan",
     "op_coverage_commit",
@@ -479,6 +481,11 @@ def load_library() -> ctypes.CDLL:
         lib.op_masked_workspace_bytes.argtypes = [vp, ci, ci]
         lib.op_forward_masked.restype = ci
         lib.op_forward_masked.argtypes = [vp, vp, vp, ci, ci, vp, cs, vp, vp, ctypes.POINTER(OpMaskedReport), vp]
+    if hasattr(lib, "op_forward_masked_native"):  # (additive to ABI 10: op_forward_masked on the selected kernel set)
+        lib.op_masked_native_workspace_bytes.restype = cs
+        lib.op_masked_native_workspace_bytes.argtypes = [vp, ci, ci]
+        lib.op_forward_masked_native.restype = ci
+        lib.op_forward_masked_native.argtypes = [vp, vp, vp, ci, ci, vp, cs, vp, vp, ctypes.POINTER(OpMaskedReport), vp]
     if hasattr(lib, "op_loss"):  # (additive to ABI 10)
         lib.op_loss.restype = ci
         lib.op_loss.argtypes = [vp, ctypes.POINTER(OpLossRequest), vp, ctypes.POINTER(OpLossReport), vp]

@@ -62,6 +62,7 @@ UNITS = [
     ("op_launch_row6", CSRC / "op_launch_row.hip", ["-DOPL_ROW_PART=6"]),
     ("op_launch_layer32", CSRC / "op_launch_layer32.hip", []),
     ("op_launch_attn", CSRC / "op_launch_attn.hip", []),
+    ("op_launch_attn_masked", CSRC / "op_launch_attn_masked.hip", []),
     ("op_launch_panel", CSRC / "op_launch_panel.hip", []),
     ("op_launch_padded", CSRC / "op_launch_padded.hip", []),
     ("op_launch_audit", CSRC / "op_launch_audit.hip", []),

@@ -39,7 +39,7 @@ struct ChunkPass {
   int s0, ns, rows, max_len;  // this chunk: sequences [s0, s0 + ns), its rows and its longest sequence
   const AttnPlan& plan;
   const HiddenReq* hid;  // per-call hidden-state request, or nullptr
-  const MaskedReq* msk;  // op_forward_masked: kernel set "fp32" with the key mask's attention and heads, or nullptr
+  const MaskedReq* msk;  // op_forward_masked: kernel set "fp32" with the key mask's attention and heads (native: the selected set with them), or nullptr
 
   int H, I;
   bool fp_layout;  // fragment-packed activations, attn_fp_kernel

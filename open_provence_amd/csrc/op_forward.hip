@@ -1,9 +1,10 @@
 // op_forward.hip -- C ABI: op_forward_packed / _hidden / _pooled.  Workspace carving, chunking of the packed batch, and the
 // launch sequence of one chunk around its layers (ChunkPass: prologue, hidden-state stores, attention, heads; the layers
-// themselves: op_forward_layers.hip).  The one unit that compiles the forward's non-GEMM kernels (opk_small / opk_pool .hip.h)
+// themselves: op_forward_layers.hip).  The one unit that compiles the forward's non-GEMM kernels (opk_small / opk_masked / opk_pool .hip.h)
 // and the tiled path's attention (attn_kernel of opk_tiled.hip.h, whose GEMM op_forward_layers.hip instantiates).
 #include "op_forward.h"
 #include "opk_small.hip.h"
+#include "opk_masked.hip.h"
 #include "opk_pool.hip.h"
 #include "opk_tiled.hip.h"
 
@@ -65,8 +66,10 @@ ChunkPass::ChunkPass(op_handle* h_, Launcher& L_, const Workspace& ws_, const Pa
   st = L.stream;
   // Evaluated policy E, instantiated kernel set V (V has every term of E).  Where V multiplies by a lo operand that
   // E does not have, that operand is cleared: weights at load time (op_load_weight), activations in the launch sequence.
-  const KernelSet& ks = msk ? kKernelSets[OP_KS_F32] : *h->ks;  // (a masked forward: set "fp32" on any handle with its packs)
-  E = msk ? ks.terms : h->eff;
+  // (a masked forward: set "fp32" on any handle with its packs -- unless it asks for the handle's own set, MaskedReq::native)
+  const bool msk_f32 = msk && !msk->native;
+  const KernelSet& ks = msk_f32 ? kKernelSets[OP_KS_F32] : *h->ks;
+  E = msk_f32 ? ks.terms : h->eff;
   pi = ks.pi;
   V = opl::kPolicies[pi];
   o_f8 = ks.side == FMT_F8;   // o = fp16 pieces (ws.o_hi) + e4m3 pieces (ws.o_lo); panel path: every GEMM in that format
@@ -131,6 +134,8 @@ int ChunkPass::prologue() {
   }
   hipLaunchKernelGGL(row_map_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, st, b.cu_dev, s0, ns, ws.roff,
                      r_pad, ws.row_seq, ws.row_pos, ws.row_tok);
+  if (msk && msk->native)  // the mask in this chunk's row layout: what the key-mask form of attn_fp_kernel reads
+    hipLaunchKernelGGL(key_row_kernel, dim3((unsigned)((r_pad + 255) / 256)), dim3(256), 0, st, msk->key_ok, ws.row_tok, r_pad, msk->key_row);
   OP_TRY(L.end());
 
   // rows >= `rows` are never produced by the attention kernel: keep its output finite there
@@ -224,7 +229,23 @@ int ChunkPass::attention(bool is_global) {
     const unsigned item_span = 8u * opk::ATT_ITEM_GROUP;
     const dim3 grid((ap.xcd_group ? ((unsigned)ap.n_items + item_span - 1) / item_span * item_span : (unsigned)ap.n_items) *
                     (unsigned)h->nh);
-    if (!opl::launch_attn(st, ap, is_global ? plan.waves_g : 4, is_global ? 2 : 1, pi, zero_p_lo, grid, attn16))
+    const int waves = is_global ? plan.waves_g : 4, kt = is_global ? 2 : 1;
+    if (msk && msk->native) {
+      // the mask removes keys; a query of a sliding-window layer left without one takes the row's mean of v as the set stores it
+      ap.key_row = msk->key_row;
+      ap.vmean = is_global ? nullptr : msk->vmean;
+      if (!is_global) {
+        const dim3 vgrid((unsigned)ns, (unsigned)h->nh);
+        if (attn16 || V.fmt == 2)
+          hipLaunchKernelGGL((vmean_fp_kernel<true, false>), vgrid, dim3(256), 0, st, ws.vt_hi, b.cu_dev, s0, ws.roff, H, r_pad, msk->vmean);
+        else if (V.pv & 2)
+          hipLaunchKernelGGL((vmean_fp_kernel<false, true>), vgrid, dim3(256), 0, st, ws.vt_hi, b.cu_dev, s0, ws.roff, H, r_pad, msk->vmean);
+        else
+          hipLaunchKernelGGL((vmean_fp_kernel<false, false>), vgrid, dim3(256), 0, st, ws.vt_hi, b.cu_dev, s0, ws.roff, H, r_pad, msk->vmean);
+      }
+      if (!opl::launch_attn_masked(st, ap, waves, kt, pi, zero_p_lo, grid, attn16))
+        return fail(h, OP_ERR_UNSUPPORTED, "internal: no masked attention kernel for this configuration");
+    } else if (!opl::launch_attn(st, ap, waves, kt, pi, zero_p_lo, grid, attn16))
       return fail(h, OP_ERR_UNSUPPORTED, "internal: no attention kernel for this configuration");
   } else {
     const dim3 grid((unsigned)q_tiles, (unsigned)h->nh, (unsigned)ns);
@@ -283,8 +304,13 @@ int ChunkPass::heads() {
   }
   OP_TRY(L.begin(PK_RANK_HEAD));
   if (msk) {
-    opl::launch_f32_rank_head_masked(st, ns, ws.cls, ws.x, b.cu_dev, s0, ws.roff, msk->key_ok, mean_pool, H, h->nl, h->dense_t,
-                                     h->head_norm, h->cfg.norm_eps, h->cls_w, h->cls_b, b.rank_out);
+    if (msk->native)
+      hipLaunchKernelGGL(rank_head_masked_kernel, dim3((unsigned)ns), dim3(256), 0, st, ws.cls, ws.x, b.cu_dev, s0, ws.roff, msk->key_ok,
+                         mean_pool, H, h->nl, h->dense_t, h->head_norm, h->cfg.norm_eps, h->cls_w, h->cls_b, b.rank_out,
+                         range_flagged ? ws.range_flag : nullptr);
+    else
+      opl::launch_f32_rank_head_masked(st, ns, ws.cls, ws.x, b.cu_dev, s0, ws.roff, msk->key_ok, mean_pool, H, h->nl, h->dense_t,
+                                       h->head_norm, h->cfg.norm_eps, h->cls_w, h->cls_b, b.rank_out);
     // (final_ln_prune_kernel wrote every position of the chunk's rows: tokens cu[s0] .. cu[s0 + ns])
     opl::launch_prune_mask(st, b.prune_out, msk->key_ok, (size_t)msk->cu_host[s0], (size_t)(msk->cu_host[s0 + ns] - msk->cu_host[s0]));
   } else if (f32)
@@ -346,7 +372,7 @@ int forward_packed_impl(op_handle* h, const PackedBatch& b, const HiddenReq* hid
   if (op_weights_ready(h) != OP_OK) return OP_ERR_STATE;
   if ((reinterpret_cast<uintptr_t>(b.workspace) & 255) != 0)
     return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
-  const opp::Layout lay = forward_layout(h, b.n_seqs, b.total_tokens, b.max_seqlen, msk || h->set == OP_KS_F32);  // (= op_workspace_bytes)
+  const opp::Layout lay = forward_layout(h, b.n_seqs, b.total_tokens, b.max_seqlen, (msk && !msk->native) || h->set == OP_KS_F32);  // (= op_workspace_bytes)
   if (b.workspace_bytes < lay.bytes)
     return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", b.workspace_bytes, lay.bytes);
 

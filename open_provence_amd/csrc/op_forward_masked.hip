@@ -1,7 +1,8 @@
 // op_forward_masked.hip -- C ABI: op_forward_masked / op_masked_workspace_bytes, the forward under an arbitrary [n_rows][width]
 // attention mask.  No kernel of its own: the call checks its arguments, carves its workspace, runs the id check with the dense
 // cu_seqlens (op_launch_f32_masked.hip) and hands a dense batch with its key mask to the forward unit (forward_packed_impl with
-// a MaskedReq: kernel set "fp32", the masked attention and heads swapped in).
+// a MaskedReq: kernel set "fp32", the masked attention and heads swapped in).  op_forward_masked_native /
+// op_masked_native_workspace_bytes: the same call on the handle's selected kernel set (MaskedReq::native; row and panel path).
 #include "op_handle.h"
 
 struct MaskedWorkspace {
@@ -28,7 +29,104 @@ static void carve_masked(const op_handle* h, char* base, int n_rows, int width, 
   ws.bytes = off;
 }
 
+// op_forward_masked_native's regions (opp::masked_native_layout) over `base`
+struct MaskedNativeWorkspace {
+  int32_t* cu;
+  uint32_t* status;
+  uint8_t* key_row;
+  float* vmean;
+  char* forward;
+  size_t forward_bytes, bytes;
+};
+static void carve_masked_native(const op_handle* h, char* base, int n_rows, int width, MaskedNativeWorkspace& ws) {
+  ws.forward_bytes = forward_layout(h, n_rows, n_rows * width, width, /*f32=*/false).bytes;
+  const opp::MaskedNativeLayout l = opp::masked_native_layout(h->H, h->chunk_rows, n_rows, width, ws.forward_bytes);
+  ws.cu = reinterpret_cast<int32_t*>(base + l.cu);
+  ws.status = reinterpret_cast<uint32_t*>(base + l.status);
+  ws.key_row = reinterpret_cast<uint8_t*>(base + l.key_row);
+  ws.vmean = reinterpret_cast<float*>(base + l.vmean);
+  ws.forward = base + l.forward;
+  ws.bytes = l.bytes;
+}
+
+// The id check of a dense batch on `stream` (synchronised once; a second time to read an offender's value): the dense cu_seqlens
+// into cu_dev, the first id outside the table into the report.  `fn`: the entry point the refusal names.
+static int masked_id_check(op_handle* h, const char* fn, const int32_t* ids_dev, int n_rows, int width, int32_t* cu_dev, uint32_t* status_dev,
+                           op_masked_report* report, hipStream_t stream) {
+  OP_HIP(h, hipMemsetAsync(status_dev, 0xff, sizeof(uint32_t), stream));
+  opl::launch_masked_prepare(stream, ids_dev, n_rows, width, h->V, cu_dev, status_dev);
+  OP_HIP(h, hipGetLastError());
+  uint32_t bad = opk::MASKED_ST_NONE;
+  OP_HIP(h, hipMemcpyAsync(&bad, status_dev, sizeof(bad), hipMemcpyDeviceToHost, stream));
+  OP_HIP(h, hipStreamSynchronize(stream));
+  if (bad == opk::MASKED_ST_NONE) return OP_OK;
+  int32_t value = 0;
+  OP_HIP(h, hipMemcpyAsync(&value, ids_dev + bad, sizeof(value), hipMemcpyDeviceToHost, stream));
+  OP_HIP(h, hipStreamSynchronize(stream));
+  report->status = 2;
+  report->id_row = (int32_t)(bad / (uint32_t)width);
+  report->id_col = (int32_t)(bad % (uint32_t)width);
+  report->id_value = value;
+  return fail(h, OP_ERR_INVALID, "%s: token id %lld at row %d, column %d is outside the embedding table (vocab_size %d)", fn,
+              (long long)report->id_value, report->id_row, report->id_col, h->V);
+}
+
 extern "C" {
+
+size_t op_masked_native_workspace_bytes(const op_handle* h, int n_rows, int width) {
+  if (!h || n_rows < 0 || width < 0 || (int64_t)n_rows * (int64_t)width > (int64_t)INT32_MAX) return 0;
+  MaskedNativeWorkspace ws;
+  carve_masked_native(h, nullptr, n_rows, width, ws);
+  return ws.bytes;
+}
+
+int op_forward_masked_native(op_handle* h, const int32_t* ids_dev, const uint8_t* mask_dev, int n_rows, int width, void* workspace,
+                             size_t workspace_bytes, float* prune_out, float* rank_out, op_masked_report* report, void* hip_stream) {
+  const char* const fn = "op_forward_masked_native";
+  // (the arguments' own fields first: none of them needs the handle)
+  const opp::Refusal bad_args = opp::check_masked_args(fn, report != nullptr, report ? report->struct_bytes : 0u, n_rows, width, ids_dev != nullptr,
+                                                       mask_dev != nullptr, prune_out != nullptr, rank_out != nullptr, workspace != nullptr);
+  if (bad_args.code != OP_OK) return fail(h, bad_args);
+  if (!h) return fail(nullptr, OP_ERR_INVALID, "%s: NULL handle", fn);
+  const int64_t cells = (int64_t)n_rows * (int64_t)width;
+  report->status = 0;
+  report->id_row = report->id_col = -1;
+  report->id_value = 0;
+  opp::Refusal unfit = opp::check_masked_native_handle(width, h->max_pos, h->row_path, h->panel_path, h->set);
+  if (unfit.code != OP_OK) return fail(h, unfit);
+  if (cells == 0) return OP_OK;
+  if (op_weights_ready(h) != OP_OK) return OP_ERR_STATE;
+  unfit = opp::check_masked_native_handle(width, h->max_pos, h->row_path, h->panel_path, h->set);  // (the selection may have been made just now)
+  if (unfit.code != OP_OK) return fail(h, unfit);
+  if ((reinterpret_cast<uintptr_t>(workspace) & 255) != 0) return fail(h, OP_ERR_WORKSPACE, "workspace must be 256-byte aligned");
+  MaskedNativeWorkspace ws;
+  carve_masked_native(h, reinterpret_cast<char*>(workspace), n_rows, width, ws);
+  if (workspace_bytes < ws.bytes) return fail(h, OP_ERR_WORKSPACE, "workspace has %zu bytes, need %zu", workspace_bytes, ws.bytes);
+
+  OP_HIP(h, hipSetDevice(h->cfg.device_id));
+  hipStream_t stream = reinterpret_cast<hipStream_t>(hip_stream);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  OP_HIP(h, hipStreamIsCapturing(stream, &capturing));
+  if (capturing != hipStreamCaptureStatusNone)
+    return fail(h, OP_ERR_STATE, "%s: the stream is being captured (the call synchronises it to read the id check back)", fn);
+  // the dense cu_seqlens and the id check; its word comes back before the forward is enqueued: the embedding kernels only clamp
+  OP_TRY(masked_id_check(h, fn, ids_dev, n_rows, width, ws.cu, ws.status, report, stream));
+
+  std::vector<int32_t> cu_host((size_t)n_rows + 1);
+  for (int r = 0; r <= n_rows; ++r) cu_host[(size_t)r] = r * width;
+  PackedBatch b;
+  b.ids_dev = ids_dev, b.cu_dev = ws.cu, b.cu_host = cu_host.data();
+  b.n_seqs = n_rows, b.total_tokens = (int)cells, b.max_seqlen = width;
+  b.prune_out = prune_out, b.rank_out = rank_out;
+  b.workspace = ws.forward, b.workspace_bytes = ws.forward_bytes, b.stream = stream;
+  MaskedReq msk;
+  msk.key_ok = mask_dev;
+  msk.vmean = ws.vmean;
+  msk.cu_host = cu_host.data();
+  msk.native = true;
+  msk.key_row = ws.key_row;
+  return forward_packed_impl(h, b, nullptr, &msk);
+}
 
 size_t op_masked_workspace_bytes(const op_handle* h, int n_rows, int width) {
   if (!h || n_rows < 0 || width < 0 || (int64_t)n_rows * (int64_t)width > (int64_t)INT32_MAX) return 0;
@@ -77,23 +175,7 @@ int op_forward_masked(op_handle* h, const int32_t* ids_dev, const uint8_t* mask_
     return fail(h, OP_ERR_STATE, "op_forward_masked: the stream is being captured (the call synchronises it to read the id check back)");
 
   // the dense cu_seqlens and the id check; its word comes back before the forward is enqueued: the embedding kernel only clamps
-  OP_HIP(h, hipMemsetAsync(ws.status, 0xff, sizeof(uint32_t), stream));
-  opl::launch_masked_prepare(stream, ids_dev, n_rows, width, h->V, ws.cu, ws.status);
-  OP_HIP(h, hipGetLastError());
-  uint32_t bad = opk::MASKED_ST_NONE;
-  OP_HIP(h, hipMemcpyAsync(&bad, ws.status, sizeof(bad), hipMemcpyDeviceToHost, stream));
-  OP_HIP(h, hipStreamSynchronize(stream));
-  if (bad != opk::MASKED_ST_NONE) {
-    int32_t value = 0;
-    OP_HIP(h, hipMemcpyAsync(&value, ids_dev + bad, sizeof(value), hipMemcpyDeviceToHost, stream));
-    OP_HIP(h, hipStreamSynchronize(stream));
-    report->status = 2;
-    report->id_row = (int32_t)(bad / (uint32_t)width);
-    report->id_col = (int32_t)(bad % (uint32_t)width);
-    report->id_value = value;
-    return fail(h, OP_ERR_INVALID, "op_forward_masked: token id %lld at row %d, column %d is outside the embedding table (vocab_size %d)",
-                (long long)report->id_value, report->id_row, report->id_col, h->V);
-  }
+  OP_TRY(masked_id_check(h, "op_forward_masked", ids_dev, n_rows, width, ws.cu, ws.status, report, stream));
 
   std::vector<int32_t> cu_host((size_t)n_rows + 1);
   for (int r = 0; r <= n_rows; ++r) cu_host[(size_t)r] = r * width;

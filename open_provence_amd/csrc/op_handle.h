@@ -210,10 +210,14 @@ struct PackedBatch {
 
 // op_forward_masked's addition to a forward: the batch is dense (a sequence = a padded row of `width` positions), runs on kernel
 // set "fp32" whatever set the handle has selected, and the mask removes keys (opk_f32_masked.hip.h).
+// native (op_forward_masked_native; row and panel path): the pass stays on the handle's selected kernel set -- attn_fp_kernel's
+// key-mask form over key_row, the row means of v^T, the ranking head's masked mean pooling (opk_masked.hip.h).
 struct MaskedReq {
   const uint8_t* key_ok = nullptr;  // [total_tokens]
   float* vmean = nullptr;           // [n_seqs][H]: the row means of v of the sliding-window layer in flight
   const int32_t* cu_host = nullptr; // [n_seqs + 1]: the dense cu_seqlens on the host (a chunk's tokens, for the pruning logits' zeros)
+  bool native = false;
+  uint8_t* key_row = nullptr;       // native: [padded row capacity] the mask in the row layout of the chunk in flight
 };
 
 // ---- defined once, in the unit named; called from others -------------------------------------------------------------------

@@ -52,6 +52,9 @@ bool launch_layer16p(hipStream_t st, const opk::Layer32Params& p, bool h16, bool
 // o written as fp16 + e4m3 pieces for the attention output projection of the fp16 + e4m3 format.
 bool launch_attn(hipStream_t st, const opk::AttnFpParams& p, int waves, int kt, int pi, bool zero_p_lo, dim3 grid,
                  bool f16_in_f8_out = false);
+// launch_attn's arguments on the key-mask form of the same kernels (p.key_row, p.vmean; op_launch_attn_masked.hip)
+bool launch_attn_masked(hipStream_t st, const opk::AttnFpParams& p, int waves, int kt, int pi, bool zero_p_lo, dim3 grid,
+                        bool f16_in_f8_out = false);
 bool launch_panel(hipStream_t st, const opk::PanelParams& p, int epi, int pi, dim3 grid);
 // q, k and v^T panels of one layer in one launch (p.n_tiles = 3 H / 256, p.n_qk_tiles = 2 H / 256, p.o2 = v^T)
 bool launch_panel_qkv(hipStream_t st, const opk::PanelParams& p, int pi, dim3 grid);

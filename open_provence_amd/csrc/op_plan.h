@@ -459,6 +459,61 @@ inline Layout workspace_layout(int hidden, int inter, int cap_rows_pad, int n_se
   return lay;
 }
 
+// ---- op_forward_masked_native: the arguments' own checks and the handle's fitness -----------------------------------------------------
+// What op_forward_masked checks before it looks at the handle, in its order and wording under the name `fn`: the report, the
+// sizes, the buffers of a non-empty batch.  report_bytes: the caller's op_masked_report.struct_bytes (has_report: it gave one).
+inline Refusal check_masked_args(const char* fn, bool has_report, uint32_t report_bytes, int n_rows, int width, bool ids, bool mask,
+                                 bool prune, bool rank, bool workspace) {
+  if (!has_report) return refuse(OP_ERR_INVALID, "%s: report is NULL", fn);
+  if (report_bytes != sizeof(op_masked_report))
+    return refuse(OP_ERR_INVALID, "%s: op_masked_report.struct_bytes is %u, expected %zu", fn, report_bytes, sizeof(op_masked_report));
+  if (n_rows < 0) return refuse(OP_ERR_INVALID, "%s: negative n_rows %d", fn, n_rows);
+  if (width < 0) return refuse(OP_ERR_INVALID, "%s: negative width %d", fn, width);
+  const int64_t cells = (int64_t)n_rows * (int64_t)width;
+  if (cells > (int64_t)INT32_MAX)  // (tokens and the first offending id are 32-bit linear indices)
+    return refuse(OP_ERR_INVALID, "%s: n_rows * width = %lld exceeds 2^31 - 1", fn, (long long)cells);
+  if (cells > 0 && !ids) return refuse(OP_ERR_INVALID, "%s: ids_dev is NULL", fn);
+  if (cells > 0 && !mask) return refuse(OP_ERR_INVALID, "%s: mask_dev is NULL", fn);
+  if (cells > 0 && !prune) return refuse(OP_ERR_INVALID, "%s: prune_logits_dev is NULL", fn);
+  if (cells > 0 && !rank) return refuse(OP_ERR_INVALID, "%s: rank_logits_dev is NULL", fn);
+  if (cells > 0 && !workspace) return refuse(OP_ERR_INVALID, "%s: workspace_dev is NULL", fn);
+  return Refusal{};
+}
+
+// ... and what it asks of the handle, once there is one: the width within the RoPE tables, the key-mask kernels' paths (row or
+// panel), a selected set that is not "fp32" (whose masked forward op_forward_masked is).
+inline Refusal check_masked_native_handle(int width, int max_pos, bool row_path, bool panel_path, int set) {
+  const char* const fn = "op_forward_masked_native";
+  if (width > max_pos) return refuse(OP_ERR_INVALID, "%s: width %d exceeds max_position_embeddings %d", fn, width, max_pos);
+  if (!row_path && !panel_path)
+    return refuse(OP_ERR_UNSUPPORTED, "%s: the handle runs the tiled path, which has no key-mask attention kernel: use op_forward_masked (the fp32 kernels)", fn);
+  if (set == OP_KS_F32)
+    return refuse(OP_ERR_UNSUPPORTED, "%s: the selected kernel set is \"fp32\": op_forward_masked is this handle's masked forward", fn);
+  return Refusal{};
+}
+
+// The call's own workspace: the dense cu_seqlens, the id check's word, the mask in the row layout, the row means of v, then the
+// selected set's forward workspace -- offsets from the 256-aligned base, each region rounded up to 256 bytes.
+struct MaskedNativeLayout {
+  size_t cu, status, key_row, vmean, forward, bytes;
+};
+inline MaskedNativeLayout masked_native_layout(int hidden, int chunk_rows, int n_rows, int width, size_t forward_bytes) {
+  MaskedNativeLayout l{};
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = off;
+    off += align_up_sz(bytes, 256);
+    return at;
+  };
+  l.cu = take(((size_t)n_rows + 1) * 4);
+  l.status = take(sizeof(uint32_t));
+  l.key_row = take((size_t)padded_row_capacity(chunk_rows, n_rows, n_rows * width, width));
+  l.vmean = take((size_t)n_rows * (size_t)hidden * sizeof(float));
+  l.forward = take(forward_bytes);
+  l.bytes = off;
+  return l;
+}
+
 // ---- prepared requests: fragment means and sentence decisions (op_planned_fragment_means, op_located_fragment_means,
 // op_sentence_decisions) ----------------------------------------------------------------------------------------------------------
 // All look at the caller's HOST copies only, before anything is enqueued and before the handle is looked at.

@@ -35,6 +35,9 @@ struct AttnFpParams {
   int n_heads;
   int xcd_group;  // 0: item-major grid (n_items x n_heads blocks); 1: XCD-grouped map below
   int* range_flag;  // OF8 + H16 (kernel sets 10 / 11): raised when an output is not finite (see PanelParams::range_flag); may be NULL
+  // KM (a dense batch under a key mask, op_forward_masked_native) only:
+  const uint8_t* key_row = nullptr;  // [r_pad], one byte per row of the row layout: 1 = the key may be seen; 0 in alignment rows and at masked positions
+  const float* vmean = nullptr;      // [ns][H]: the output of a query without a key (the row's mean of v), or NULL: +0.0
 };
 
 // Block -> (work item, head), XCD-aware.  Neighbouring query blocks of a sequence read the same K / V^T rows (a
@@ -70,7 +73,12 @@ constexpr int ATT_ITEM_GROUP = 4;
 // (vmcnt retires in order) instead of draining everything.
 // H16 (kernel set "f16"): q / k / v^T / p / o are single-plane fp16 (the layouts of the single-pass bf16 set), products on
 // v_mfma_f32_16x16x32_f16.  p <= 2^6 by the lazy reference; a p below 2^-24 is flushed (it is summed into l_run in fp32).
-template <int TQK, int TPV, bool O_LO, int WAVES, int KT, bool ZP = false, bool OF8 = false, int NST = 2, bool H16 = false>
+// KM: the rows are DENSE padded rows and p.key_row removes keys.  A tile with a masked key takes the masked-tile path with the
+// key's byte ANDed into the predicate: its p is exactly 0, and a tile that is wholly masked for a query leaves the query's
+// reference, sums and accumulators as they were (-3e30 against the -1e30 sentinel, in both softmax forms).  A tile without one
+// stays on the mask-free path, so under a prefix mask every visible (query, key) pair goes the way it goes in the packed batch.
+// A query whose row sum is 0 saw no key at all: its output is p.vmean's row (sliding-window layers) or +0.0, never 0 x oacc.
+template <int TQK, int TPV, bool O_LO, int WAVES, int KT, bool ZP = false, bool OF8 = false, int NST = 2, bool H16 = false, bool KM = false>
 __global__ __launch_bounds__(WAVES * 64, 2) void attn_fp_kernel(AttnFpParams p) {
   if constexpr (OF8 && !H16) set_saturating_conversions();  // (H16: only in front of the output conversions, below)
   static_assert(!H16 || (TQK == 0 && TPV == 0 && !O_LO && !ZP), "fp16 operands: single pass only");
@@ -211,6 +219,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_fp_kernel(AttnFpParams p) 
 
   auto tile = [&](int kt, auto cur_tag) {
     constexpr int cur = decltype(cur_tag)::value;
+    // KM: this lane's key bytes of the tile, keys kbase + 16 m + 4 g + 0 .. 3 = one aligned dword per m (sequences start at
+    // multiples of 32 rows), requested in front of the DMA so that waiting for them does not wait for the prefetch; a tile
+    // may reach past the sequence's rows (and past r_pad): no key there
+    [[maybe_unused]] uint32_t kok[2 * KT];
+    if constexpr (KM) {
+#pragma unroll
+      for (int m = 0; m < 2 * KT; ++m) {
+        const int kr = kt * TILE_KEYS + 16 * m + 4 * g;
+        kok[m] = kr < alloc ? *reinterpret_cast<const uint32_t*>(p.key_row + r0 + kr) : 0u;
+      }
+    }
     // unconditional prefetch into the idle stage (NST = 3: of the tile after next, into the stage tile kt - 1 used)
     if constexpr (NST == 2) stage_tile(kt + 1 <= kt_hi ? kt + 1 : kt, cur ^ 1);
     else stage_tile(kt + 2 <= kt_hi ? kt + 2 : kt_hi, (cur + 2) % 3);
@@ -219,8 +238,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_fp_kernel(AttnFpParams p) 
     // wave-uniform tile classification: skip tiles entirely outside this wave's window (other waves of the block
     // may need them), and use the mask-free path when every (query, key) pair of the tile is visible
     const bool outside = (kbase > qbase + 31 + win) || (kbase + TILE_KEYS - 1 < qbase - win);
-    const bool all_valid =
+    bool all_valid =
         (kbase + TILE_KEYS - 1 < len) && (kbase + TILE_KEYS - 1 - qbase <= win) && (qbase + 31 - kbase <= win);
+    if constexpr (KM) {  // ... and the wave's tile holds no masked key
+      bool hole = false;
+#pragma unroll
+      for (int m = 0; m < 2 * KT; ++m) hole |= kok[m] != 0x01010101u;
+      all_valid = all_valid && __builtin_amdgcn_ballot_w64(hole) == 0;
+    }
     if (!outside) {
       f32x4 sacc[2 * KT][2];
       // FSM: the accumulators start at minus the softmax reference of their query (0 while it has none: sentinel -1e30)
@@ -265,7 +290,8 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_fp_kernel(AttnFpParams p) 
           for (int m = 0; m < 2 * KT; ++m)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const bool ok = (unsigned)(16 * m + r - lo_rel) <= uspan;
+              bool ok = (unsigned)(16 * m + r - lo_rel) <= uspan;
+              if constexpr (KM) ok = ok && ((kok[m] >> (8 * r)) & 0xffu) != 0u;
               sacc[m][qf][r] = ok ? sacc[m][qf][r] : -3e30f;
             }
         }
@@ -420,8 +446,20 @@ __global__ __launch_bounds__(WAVES * 64, 2) void attn_fp_kernel(AttnFpParams p) 
       float l_tot = l_run[qf] + __shfl_xor(l_run[qf], 16, 64);
       l_tot += __shfl_xor(l_tot, 32, 64);
       if constexpr (FSM) l_tot = lacc[qf][0];  // summed over all 32 keys of every k-step by the MFMA: complete in every lane
-      const float inv = l_tot > 0.f ? 1.0f / l_tot : 0.f;
+      // (packed batches: every query sees itself, l_tot > 0.  KM: a query without a key takes vmean's row or +0.0 -- as its
+      // accumulators, times 1, so that the products below and what the compiler contracts them with stay those of the other form)
+      const bool no_key = KM && !(l_tot > 0.f);
+      const float inv = no_key ? 1.0f : (l_tot > 0.f ? 1.0f / l_tot : 0.f);
       // oacc[n][qf][r]: d = 32(n>>1) + 8g + 4(n&1) + r  ->  lane owns d = 8g..8g+7 of k-step (n>>1) of this head
+      if constexpr (KM) {
+        if (no_key) {
+#pragma unroll
+          for (int n = 0; n < 4; ++n)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              oacc[n][qf][r] = p.vmean != nullptr ? p.vmean[(size_t)s * p.H + head * 64 + 32 * (n >> 1) + 8 * g + 4 * (n & 1) + r] : 0.f;
+        }
+      }
       if constexpr (OF8) {
         uint32_t lo8[4];
 #pragma unroll

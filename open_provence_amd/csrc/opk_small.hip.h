@@ -204,13 +204,17 @@ __device__ __forceinline__ float block_sum_256(float v, float* red) {
   return (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-__global__ __launch_bounds__(256) void rank_head_kernel(const float* __restrict__ cls, const float* __restrict__ y,
-                                                        const int32_t* __restrict__ cu, int s0,
-                                                        const int32_t* __restrict__ roff, int mean_pool, int H, int nl,
-                                                        const float* __restrict__ dense_t,
-                                                        const float* __restrict__ head_norm, float eps,
-                                                        const float* __restrict__ cls_w, const float* __restrict__ cls_b,
-                                                        float* __restrict__ rank_out, const int* __restrict__ range_flag) {
+// KM (rank_head_masked_kernel: a dense batch under a key mask, key_ok[total_tokens] indexed like the ids): mean pooling sums
+// the positions in the same order, a masked one contributing +0.0f, and divides by the number of valid positions -- under a
+// prefix mask the bits of the packed row; cls pooling reads column 0 whatever its mask says (the reference pools it).  A
+// sequence without a valid position gives zeros, as an empty one does.
+template <bool KM>
+__device__ __forceinline__ void rank_head_body(const float* __restrict__ cls, const float* __restrict__ y,
+                                               const int32_t* __restrict__ cu, int s0, const int32_t* __restrict__ roff,
+                                               const uint8_t* __restrict__ key_ok, int mean_pool, int H, int nl,
+                                               const float* __restrict__ dense_t, const float* __restrict__ head_norm, float eps,
+                                               const float* __restrict__ cls_w, const float* __restrict__ cls_b,
+                                               float* __restrict__ rank_out, const int* __restrict__ range_flag) {
   // range_flag (may be NULL): raised by a kernel of the fp16 + e4m3 format that met an activation beyond fp16's range (or a
   // non-finite one) where the format cannot say so itself -- under MODE.FP16_OVFL = 1 conversions clamp and the fp16 MFMA
   // takes a NaN operand for a finite number (microbench/mode_probe.hip).  The ranking logits of the chunk then leave as NaN:
@@ -222,7 +226,15 @@ __global__ __launch_bounds__(256) void rank_head_kernel(const float* __restrict_
   const int s = blockIdx.x;
   const int tid = threadIdx.x;
   const int len = cu[s0 + s + 1] - cu[s0 + s];
-  if (len <= 0) {
+  [[maybe_unused]] const uint8_t* ok = nullptr;
+  float count = (float)len;
+  if constexpr (KM) {
+    ok = key_ok + (size_t)cu[s0 + s];
+    float mine = 0.f;
+    for (int p = tid; p < len; p += 256) mine += ok[p] ? 1.f : 0.f;
+    count = block_sum_256(mine, red);  // (whole numbers below 2^24: exact)
+  }
+  if (KM ? !(count > 0.f) : len <= 0) {
     if (tid < nl) rank_out[(size_t)(s0 + s) * nl + tid] = 0.f;
     return;
   }
@@ -231,8 +243,13 @@ __global__ __launch_bounds__(256) void rank_head_kernel(const float* __restrict_
     if (mean_pool) {
       const float* base = y + (size_t)roff[s] * H + k;
       float acc = 0.f;
-      for (int p = 0; p < len; ++p) acc += base[(size_t)p * H];
-      v = acc / (float)len;
+      if constexpr (KM) {
+        for (int p = 0; p < len; ++p) acc += ok[p] ? base[(size_t)p * H] : 0.0f;
+        v = acc / count;
+      } else {
+        for (int p = 0; p < len; ++p) acc += base[(size_t)p * H];
+        v = acc / (float)len;
+      }
     } else {
       v = cls[(size_t)s * H + k];
     }
@@ -261,6 +278,26 @@ __global__ __launch_bounds__(256) void rank_head_kernel(const float* __restrict_
     const float tot = block_sum_256(part, red);
     if (tid == 0) rank_out[(size_t)(s0 + s) * nl + c] = poisoned ? __builtin_nanf("") : tot + cls_b[c];
   }
+}
+
+__global__ __launch_bounds__(256) void rank_head_kernel(const float* __restrict__ cls, const float* __restrict__ y,
+                                                        const int32_t* __restrict__ cu, int s0,
+                                                        const int32_t* __restrict__ roff, int mean_pool, int H, int nl,
+                                                        const float* __restrict__ dense_t,
+                                                        const float* __restrict__ head_norm, float eps,
+                                                        const float* __restrict__ cls_w, const float* __restrict__ cls_b,
+                                                        float* __restrict__ rank_out, const int* __restrict__ range_flag) {
+  rank_head_body<false>(cls, y, cu, s0, roff, nullptr, mean_pool, H, nl, dense_t, head_norm, eps, cls_w, cls_b, rank_out, range_flag);
+}
+
+__global__ __launch_bounds__(256) void rank_head_masked_kernel(const float* __restrict__ cls, const float* __restrict__ y,
+                                                               const int32_t* __restrict__ cu, int s0,
+                                                               const int32_t* __restrict__ roff, const uint8_t* __restrict__ key_ok,
+                                                               int mean_pool, int H, int nl, const float* __restrict__ dense_t,
+                                                               const float* __restrict__ head_norm, float eps,
+                                                               const float* __restrict__ cls_w, const float* __restrict__ cls_b,
+                                                               float* __restrict__ rank_out, const int* __restrict__ range_flag) {
+  rank_head_body<true>(cls, y, cu, s0, roff, key_ok, mean_pool, H, nl, dense_t, head_norm, eps, cls_w, cls_b, rank_out, range_flag);
 }
 
 // Numerics of a narrower precision policy on a wider kernel instantiation: clear the lo plane of a fragment-packed

@@ -217,6 +217,36 @@ def check_attention_masks(attention_masks: "str | None") -> str:
     return value
 
 
+MASKED_KERNELS = ("fp32", "selected")
+
+
+def check_masked_kernels(masked_kernels: "str | None") -> str:
+    """Validate ``masked_kernels=`` before anything touches the device: ``"fp32"`` (None: the default) or ``"selected"``."""
+
+    value = "fp32" if masked_kernels is None else masked_kernels
+    if not isinstance(value, str) or value not in MASKED_KERNELS:
+        raise ValueError(f"unknown masked_kernels {masked_kernels!r}; expected one of {MASKED_KERNELS}")
+    return value
+
+
+def check_masked_selected(dims: EncoderDims, flags: int, kernel_set: "str | None") -> None:
+    """``attention_masks="any"`` with ``masked_kernels="selected"``: what ``op_forward_masked_native`` would refuse on every
+    call is a ``ValueError`` at construction -- a handle pinned to kernel set "fp32" (whose masked forward is the fp32 one),
+    and a shape on the tiled path (neither row nor panel path: the rule of ``op_plan.h``'s ``paths_of``)."""
+
+    if kernel_set == "fp32":
+        raise ValueError('masked_kernels="selected" with kernel_set="fp32": that set\'s masked forward is masked_kernels="fp32"')
+    hidden, inter = int(dims.hidden_size), int(dims.intermediate_size)
+    tiled = bool(flags & _lib.OP_FLAG_FORCE_TILED)
+    row = hidden <= 256 and hidden % 64 == 0 and inter % 32 == 0 and not tiled
+    panel = not row and hidden % 256 == 0 and inter % 128 == 0 and not tiled
+    if not (row or panel):
+        raise ValueError(
+            f'masked_kernels="selected": hidden_size {hidden} / intermediate_size {inter}'
+            + (" under OP_FLAG_FORCE_TILED" if tiled else "")
+            + ' runs the tiled path, which has no key-mask attention kernel; use masked_kernels="fp32"')
+
+
 def require_gpu(device: torch.device | str | int | None = None) -> torch.device:
     """Resolve a HIP device or fail loudly (the product has no CPU path)."""
 
@@ -254,6 +284,7 @@ class HipEncoder:
         calibration_reference: str = "bf16x3",
         attention_outputs: bool = False,
         attention_masks: str = "prefix",
+        masked_kernels: str = "fp32",
     ) -> None:
         """``audit`` / ``audit_every`` / ``audit_tokens``: how a kernel set chosen by :meth:`calibrate` is re-checked on real
         batches -- ``"first"`` (default; ``None`` reads ``OPEN_PROVENCE_AUDIT``): once, on the first real batch
@@ -267,16 +298,31 @@ class HipEncoder:
         :meth:`attention_probs` / ``forward_packed(attentions=...)`` can run; it changes nothing else.  ``kernel_set="fp32"``
         and ``calibration_reference="fp32"`` imply it.
         ``attention_masks``: ``"prefix"`` (default: right-padded masks only) or ``"any"`` -- :meth:`forward_masked` takes any
-        ``[B, L]`` mask on the fp32 kernels; implies the fp32 weights, as ``attention_outputs=True`` does."""
+        ``[B, L]`` mask on the fp32 kernels; implies the fp32 weights, as ``attention_outputs=True`` does.
+        ``masked_kernels`` (with ``attention_masks="any"`` only): ``"fp32"`` (default) or ``"selected"`` -- :meth:`forward_masked`
+        runs on the kernel set the packed forward runs on (``op_forward_masked_native``; row and panel path) and the mask no longer
+        asks for the fp32 weights.  A tiled-path shape or ``kernel_set="fp32"`` is a ``ValueError`` here."""
 
         self.kernel_set, self.calibration_reference = check_arithmetic_arguments(kernel_set, calibration_reference)
         self.attention_masks = check_attention_masks(attention_masks)
+        self.masked_kernels = check_masked_kernels(masked_kernels)
+        self.masked_native = self.attention_masks == "any" and self.masked_kernels == "selected"
         self.audit_mode = resolve_audit_mode(audit)
         self.audit_every = int(audit_every)
         self.audit_tokens = int(audit_tokens)
         if self.audit_every < 0 or self.audit_tokens < 1:
             raise ValueError("audit_every must be >= 0 and audit_tokens >= 1")
         precision_code, terms = parse_precision(precision)
+        if flags is None:
+            flags = 0
+            for name, bit in _ENV_FLAGS.items():
+                if os.environ.get(name):
+                    flags |= bit
+            waves = os.environ.get("OPEN_PROVENCE_ATT_WAVES")
+            if waves:
+                flags |= _lib.OP_FLAG_ATT_WAVES_4 if int(waves) == 4 else _lib.OP_FLAG_ATT_WAVES_8
+        if self.masked_native:  # (before the device is touched)
+            check_masked_selected(dims, int(flags), self.kernel_set or os.environ.get("OPEN_PROVENCE_KERNEL_SET"))
         self.lib = _lib.load_library()
         self.device = require_gpu(device)
         self.dims = dims
@@ -298,17 +344,9 @@ class HipEncoder:
         cfg.precision = precision_code
         for i, mask in enumerate(terms):
             cfg.terms[i] = mask
-        if flags is None:
-            flags = 0
-            for name, bit in _ENV_FLAGS.items():
-                if os.environ.get(name):
-                    flags |= bit
-            waves = os.environ.get("OPEN_PROVENCE_ATT_WAVES")
-            if waves:
-                flags |= _lib.OP_FLAG_ATT_WAVES_4 if int(waves) == 4 else _lib.OP_FLAG_ATT_WAVES_8
         if "fp32" in (self.kernel_set, self.calibration_reference) or os.environ.get("OPEN_PROVENCE_KERNEL_SET") == "fp32":
             flags |= _lib.OP_FLAG_F32_PACKS
-        if attention_outputs or self.attention_masks == "any":
+        if attention_outputs or (self.attention_masks == "any" and not self.masked_native):
             flags |= _lib.OP_FLAG_F32_PACKS
         self.attention_outputs = bool(flags & _lib.OP_FLAG_F32_PACKS)  # the fp32 weight packs op_attention_probs reads exist
         cfg.flags = int(flags)
@@ -327,7 +365,7 @@ class HipEncoder:
         self._split_state: dict | None = None  # the two pipeline streams + their workspaces (forward_packed_on)
         self._workspace: torch.Tensor | None = None
         self._attention_workspace: torch.Tensor | None = None  # op_attention_probs' own, reused across layers and calls
-        self._masked_workspace: torch.Tensor | None = None  # op_forward_masked's own
+        self._masked_workspace: torch.Tensor | None = None  # op_forward_masked's / op_forward_masked_native's own
         self._audit_workspace: torch.Tensor | None = None  # of an audit's reference forward, when the batch's own is too small for it
         self._capture: torch.Tensor | None = None
         self._capture_result: torch.Tensor | None = None
@@ -1422,12 +1460,19 @@ class HipEncoder:
         zeros where the mask is 0; a row whose mask is all zeros gives zeros in both outputs.  fp32 arithmetic of kernel set
         "fp32" whatever set the forward runs on; the dense pass computes the pads.  Every position is embedded: an id outside
         the table raises ``IndexError`` wherever it sits.  The current torch stream is synchronised once (the id check).
-        ``workspace``: a uint8 device tensor to carve instead of the encoder's own (concurrent calls on several streams)."""
+        ``workspace``: a uint8 device tensor to carve instead of the encoder's own (concurrent calls on several streams).
+
+        On an encoder created with ``masked_kernels="selected"`` the same call runs ``op_forward_masked_native``: the arithmetic of
+        the kernel set the packed forward runs on (a query without a key: the mean of ``v`` as that set stores it), and on the
+        fp16 + e4m3 sets the range guard of :meth:`forward_packed_checked` -- a non-finite result is repeated on the (hi, lo)
+        bf16 sets, where the encoder then stays."""
 
         if self.attention_masks != "any":
             raise ValueError('forward_masked needs the fp32 weight packs: create the encoder / model with attention_masks="any"')
-        if not hasattr(self.lib, "op_forward_masked"):
-            raise _lib.HipLibraryError("this library has no op_forward_masked")
+        entry = "op_forward_masked_native" if self.masked_native else "op_forward_masked"
+        sizer = "op_masked_native_workspace_bytes" if self.masked_native else "op_masked_workspace_bytes"
+        if not hasattr(self.lib, entry):
+            raise _lib.HipLibraryError(f"this library has no {entry}")
         input_ids, attention_mask = torch.as_tensor(input_ids), torch.as_tensor(attention_mask)
         if input_ids.ndim != 2:
             raise ValueError("input_ids must be [B, L]")
@@ -1454,7 +1499,7 @@ class HipEncoder:
             rank = torch.empty((n_rows, self.dims.num_labels), dtype=torch.float32, device=self.device)
             if prune.numel() == 0:
                 return prune, rank.zero_()
-            need = int(self.lib.op_masked_workspace_bytes(self._handle, n_rows, width)) + 256
+            need = int(getattr(self.lib, sizer)(self._handle, n_rows, width)) + 256
             ws = workspace if workspace is not None else self._masked_workspace
             if ws is None or ws.numel() < need:
                 if workspace is not None:
@@ -1462,17 +1507,26 @@ class HipEncoder:
                 ws = self._masked_workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
             base = ws.data_ptr()
             aligned = (base + 255) // 256 * 256
-            code = self.lib.op_forward_masked(
-                self._handle, vp(ids_in.data_ptr()), vp(mask_in.data_ptr()), n_rows, width, vp(aligned),
-                ctypes.c_size_t(ws.numel() - (aligned - base)), vp(prune.data_ptr()), vp(rank.data_ptr()), ctypes.byref(report),
-                vp(torch.cuda.current_stream(self.device).cuda_stream),
-            )
+
+            def run() -> int:
+                return getattr(self.lib, entry)(
+                    self._handle, vp(ids_in.data_ptr()), vp(mask_in.data_ptr()), n_rows, width, vp(aligned),
+                    ctypes.c_size_t(ws.numel() - (aligned - base)), vp(prune.data_ptr()), vp(rank.data_ptr()), ctypes.byref(report),
+                    vp(torch.cuda.current_stream(self.device).cuda_stream),
+                )
+
+            code = run()
+            # (the range guard of forward_packed_checked: the selected set may be an fp16 + e4m3 one)
+            if code == _lib.OP_OK and self.masked_native and self.f8_active():
+                ok = torch.isfinite(rank).all() & torch.isfinite(prune).all()
+                if not bool(ok.item()) and self.fall_back_from_f8("forward_masked"):
+                    code = run()
         if code == _lib.OP_ERR_INVALID and int(report.status) & _lib.OP_PADDED_BAD_ID:
             raise IndexError(
                 f"token id out of range for the embedding table: id {int(report.id_value)} at row {int(report.id_row)}, "
                 f"column {int(report.id_col)}; vocab_size is {self.dims.vocab_size}"
             )
-        _lib.check(self.lib, self._handle, code, "op_forward_masked")
+        _lib.check(self.lib, self._handle, code, entry)
         return prune, rank
 
     # -- the padded boundary on the device (op_pack_padded / op_unpack_padded) -----------------------------------------

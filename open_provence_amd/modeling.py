@@ -34,7 +34,8 @@ import torch
 
 from . import launches, pipeline as pl, request as rq
 from .config import DEFAULT_PROCESS_THRESHOLD, EncoderDims, OpenProvenceConfig
-from .engine import AttentionRequest, HiddenRequest, HipEncoder, check_arithmetic_arguments, check_attention_masks, require_gpu
+from .engine import (AttentionRequest, HiddenRequest, HipEncoder, check_arithmetic_arguments, check_attention_masks,
+                     check_masked_kernels, require_gpu)
 from .packing import pack_padded, pack_rows, unpack_to_padded
 from .pipeline import ContextState, FragmentRecord, RawPrediction
 from .prepared import PreparedContexts, PreparedItem, as_request as _as_prepared_request, derive_row_template
@@ -228,17 +229,20 @@ class OpenProvenceModel:
         calibration_reference: str | None = None,
         attention_outputs: bool = False,
         attention_masks: str = "prefix",
+        masked_kernels: str = "fp32",
     ) -> None:
         # attention_outputs: keep the fp32 GEMM weights on the device so that forward(output_attentions=True) can run
         # (HipEncoder; nothing else changes);
         # attention_masks: "prefix" (right-padded masks only) or "any": forward() also takes left padding and holes, on the
-        # fp32 kernels (HipEncoder.forward_masked; keeps the fp32 weights too);
+        # fp32 kernels (HipEncoder.forward_masked; keeps the fp32 weights too) -- or, with masked_kernels="selected", on the
+        # kernel set the packed forward runs on (row and panel path; no fp32 weights on the mask's account);
         # kernel_set / calibrate / calibration_rows: how the arithmetic is chosen from the loaded weights
         # (HipEncoder.load_state_dict; the reference's counterpart: standalone.py:219-244, 1589-1615);
         # calibration_reference: what a calibration compares with, "bf16x3" (default) or "fp32" (kernel set "fp32");
         # audit / audit_every / audit_tokens: how a calibrated choice is re-checked on real batches (audit.maybe_audit)
         kernel_set, calibration_reference = check_arithmetic_arguments(kernel_set, calibration_reference)
         attention_masks = check_attention_masks(attention_masks)
+        masked_kernels = check_masked_kernels(masked_kernels)
         self._kernel_set_request = kernel_set
         self._calibrate_request = calibrate
         self._calibration_rows = calibration_rows
@@ -266,7 +270,7 @@ class OpenProvenceModel:
             prune_pre_final_norm=self.pruning_hidden_state == "pre_final_norm",
             audit=audit, audit_every=audit_every, **({} if audit_tokens is None else {"audit_tokens": audit_tokens}),
             kernel_set=kernel_set, calibration_reference=calibration_reference, attention_outputs=attention_outputs,
-            attention_masks=attention_masks,
+            attention_masks=attention_masks, masked_kernels=masked_kernels,
         )
         if state_dict is not None:
             self.load_state_dict(state_dict)
@@ -547,6 +551,7 @@ class OpenProvenceModel:
             calibration_reference=kwargs.pop("calibration_reference", None),
             attention_outputs=bool(kwargs.pop("attention_outputs", False)),
             attention_masks=kwargs.pop("attention_masks", "prefix"),
+            masked_kernels=kwargs.pop("masked_kernels", "fp32"),
         )
         if max_length is not None:
             model.max_length = int(max_length)
@@ -734,7 +739,7 @@ class OpenProvenceModel:
 
     def _forward_any_mask(self, input_ids, attention_mask, output_hidden_states, output_attentions, reduced, token_loss):
         """:meth:`_forward_padded` for a batch with a non-prefix row, on a model created with ``attention_masks="any"``: the
-        dense forward on the fp32 kernels.  The requests it does not serve yet raise ``NotImplementedError`` by name."""
+        dense forward on the fp32 kernels, or on the selected kernel set (``masked_kernels="selected"``).  The requests it does not serve yet raise ``NotImplementedError`` by name."""
 
         requested = [name for name, on in (
             ("output_hidden_states", output_hidden_states), ("output_attentions", output_attentions),

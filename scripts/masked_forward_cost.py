@@ -1,6 +1,7 @@
-"""What a left-padded batch costs on an ``attention_masks="any"`` model (``op_forward_masked``: dense, fp32 kernels) against the
-same rows right-padded on kernel set "fp32" and on the calibrated set.  xsmall dims, 32 x 512, lengths 128 .. 512; device-resident
-inputs; the three forwards alternate, each call ends in a device synchronise; median of the timed calls after warm-up.
+"""What a left-padded batch costs on an ``attention_masks="any"`` model -- on the fp32 kernels (``op_forward_masked``: dense, the
+default) and on the calibrated set (``masked_kernels="selected"``: ``op_forward_masked_native``, dense) -- against the same rows
+right-padded on kernel set "fp32" and on the calibrated set.  xsmall dims, 32 x 512, lengths 128 .. 512; device-resident
+inputs; the four forwards alternate, each call ends in a device synchronise; median of the timed calls after warm-up.
 
     python scripts/masked_forward_cost.py [--out profiles/masked_forward_cost.txt]
 """
@@ -50,10 +51,14 @@ def main() -> None:
 
     any_model = model(attention_masks="any", calibrate=True)
     f32_model = model(kernel_set="fp32", calibrate=False)
+    sel_model = model(attention_masks="any", masked_kernels="selected", calibrate=True)
+    chosen = any_model.encoder.effective_policy()["kernel_set"]
+    assert sel_model.encoder.effective_policy()["kernel_set"] == chosen and not sel_model.encoder.attention_outputs
     runs = {
         'left-padded, attention_masks="any" (op_forward_masked)': lambda: any_model(input_ids=left_ids, attention_mask=left),
         'right-padded, kernel set "fp32"': lambda: f32_model(input_ids=ids_d, attention_mask=right),
-        f'right-padded, calibrated set "{any_model.encoder.effective_policy()["kernel_set"]}"': lambda: any_model(input_ids=ids_d, attention_mask=right),
+        f'right-padded, calibrated set "{chosen}"': lambda: any_model(input_ids=ids_d, attention_mask=right),
+        f'left-padded, masked_kernels="selected" ("{chosen}")': lambda: sel_model(input_ids=left_ids, attention_mask=left),
     }
     times = {name: [] for name in runs}
     for i in range(args.warmup + args.calls):
@@ -72,7 +77,20 @@ def main() -> None:
     for name, ts in times.items():
         med = statistics.median(ts)
         lines.append(f"  {name:62s} {med:8.3f} ms  ({min(ts):.3f} .. {max(ts):.3f})   x {med / base:5.2f} of the fp32 set right-padded")
-    lines += ["", f"The dense pass computes all {cells} positions ({cells / tokens:.2f} x the tokens) and synchronises the stream once per call (id check)."]
+    lines += ["", f"The dense passes compute all {cells} positions ({cells / tokens:.2f} x the tokens) and synchronise the stream once per call (id check)."]
+    # the reading, from the figures above: nothing here is fixed in advance
+    names = list(runs)
+    med = {name: statistics.median(ts) for name, ts in times.items()}
+    spread = {name: max(ts) - min(ts) for name, ts in times.items()}
+    masked_f32, packed_sel, masked_sel = names[0], names[2], names[3]
+    gap = med[masked_f32] - med[masked_sel]
+    widest = max(spread[masked_f32], spread[masked_sel])
+    lines += ["", f"Reading: the left-padded forward on the calibrated set takes {med[masked_sel] / med[masked_f32]:.2f} x the fp32 masked route's time "
+              f"({med[masked_f32] / med[masked_sel]:.2f} x faster); the medians differ by {gap:.3f} ms, the wider min .. max spread of the two is {widest:.3f} ms"
+              f" -- {'beyond' if gap > widest else 'WITHIN'} it.",
+              f"It costs {med[masked_sel] / med[packed_sel]:.2f} x the same rows right-padded on the same set, beside the {cells / tokens:.2f} x positions "
+              "the dense pass computes; the fp32 masked route costs "
+              f"{med[masked_f32] / med[packed_sel]:.2f} x that forward.  Skipping all-pad tiles or packing the valid queries is what would recover the rest."]
     text = "\n".join(lines) + "\n"
     print(text)
     if args.out:
